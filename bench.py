@@ -66,6 +66,44 @@ def source_hash():
     return h.hexdigest()[:16]
 
 
+DUMP_BUDGET = 64 << 20         # --dump-outputs: bytes over all files
+DUMP_SEED = 0                  # --dump-outputs: which frames are kept when the whole result exceeds the budget
+
+
+def dump_outputs(out_dir, result, budget=DUMP_BUDGET, seed=DUMP_SEED):
+    """--dump-outputs: what a step of the timed path hands its caller, as DIR/<name>.npy.  `result`: numpy arrays whose first axis is
+    the frame -- the detection records (counts, boxes, scores, cls, src) and the heads (head_large, head_small).  An array may cover
+    only the first frames (N > 1: rank 0's heads beside the gathered records).  Integer records are written as float64 (exact for
+    int32), scores and heads as float32.  Record slots past a frame's count are zeroed (the post-process never writes them, so their
+    bits are whatever the buffer held).  When the arrays exceed `budget` bytes, a fixed seeded sample of frames is kept, in frame
+    order, and its indices are written as frames.npy.  -> the names written."""
+    import numpy as np
+    out = {}
+    counts = np.asarray(result["counts"])
+    n = counts.shape[0]
+    kmax = np.asarray(result["cls"]).shape[1]
+    valid = np.arange(kmax)[None, :] < np.clip(counts, 0, kmax)[:, None]
+    for k, v in result.items():
+        v = np.asarray(v)
+        if v.ndim == 0 or v.shape[0] > n:
+            raise ValueError(f"dump_outputs: {k} has shape {v.shape}, expected at most {n} frames first")
+        v = v.astype(np.float32 if v.dtype.kind == "f" and v.dtype.itemsize <= 4 else np.float64)
+        if k in ("boxes", "scores", "cls", "src"):
+            v = np.where(valid[:v.shape[0]].reshape(v.shape[:2] + (1,) * (v.ndim - 2)), v, 0).astype(v.dtype)
+        out[k] = v
+    total = sum(v.nbytes for v in out.values())
+    room = budget - 4096           # the .npy headers
+    if total > room:
+        keep = max(1, n * (room - 8 * n) // total)
+        frames = np.sort(np.random.default_rng(seed).choice(n, size=keep, replace=False))
+        out = {k: v[frames[frames < v.shape[0]]] for k, v in out.items()}
+        out["frames"] = frames.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(v))
+    return sorted(out)
+
+
 def cpu_baseline(seconds=12.0):
     """The oracle (CPU restatement of the reference's detect.py path; kind "port") timed on this host:
     batch 1 over the 20 bundled frames, model and post-process like detect.py:151-171, repeated for ~`seconds`."""
@@ -494,10 +532,15 @@ def main():
     ap.add_argument("--dump-ops", default=None, help="write the launch names of one forward pass to this JSON file")
     ap.add_argument("--dump-records", default=None,
                     help="rank 0 writes the LAST step's detection records of all frames (N > 1: as gathered over RCCL) to this .npz")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last step of the headline's timed region handed back -- detection records (N > 1: as "
+                         "gathered) and its own head logits -- as DIR/<name>.npy, float32 / float64, at most 64 MB (dump_outputs)")
     args = ap.parse_args()
     args.launch_repeats = max(1, min(64, args.launch_repeats))
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
@@ -647,7 +690,9 @@ def main():
                     if gather is not None:
                         pend.append(last.extra)
                 else:
-                    raw = p.detect_raw(forward(m), kmax=cur["kmax"], packed=bool(exchange))
+                    pred = forward(m)
+                    raw = p.detect_raw(pred, kmax=cur["kmax"], packed=bool(exchange))
+                    raw["head_large"], raw["head_small"] = pred      # as BatchPipeline's result carries them
                     last = raw
                     if gather is not None:
                         pend.append(gather(raw))
@@ -712,6 +757,11 @@ def main():
     model, post = make(args.dtype, lanes, branches)
     region_s = []
     elapsed, raw = timed(model, post, in_flight, args.steps, args.warmup, multi, regions=args.regions, region_times=region_s, settle=args.settle)
+    if rank == 0 and args.dump_outputs:
+        torch.cuda.synchronize(dev)
+        rec = cur.get("gathered") if multi else raw
+        dump_outputs(args.dump_outputs, dict({k: rec[k].cpu().numpy() for k in REC},
+                                             **{k: raw[k].cpu().numpy() for k in ("head_large", "head_small")}))
     if args.headline_only:
         if rank == 0:
             print(json.dumps({"metric": "frames/sec end-to-end (headline loop only)", "value": round(n_total * args.steps / elapsed, 1), "unit": "frames/s",

@@ -302,7 +302,48 @@ def test_bench_roofline_arithmetic():
     assert len(b.source_hash()) == 16
 
 
-CLASS_RGB = {0: (205, 90, 106), 1: (20, 97, 199), 2: (105, 128, 112)}   # detect.py:105 colours are BGR (cv2); these are what a viewer sees
+def test_bench_dump_outputs(tmp_path):
+    """bench.dump_outputs (--dump-outputs): the records and heads of a step as DIR/<name>.npy in float32 / float64, integer records exact,
+    the slots past a frame's count zeroed (never written by the post-process), and over the byte budget a seeded sample of frames that
+    is the same from call to call; an array covering only the first frames (N > 1: rank 0's heads) keeps the sampled frames it has."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec); spec.loader.exec_module(b)
+    rng = np.random.default_rng(1)
+    n, kmax = 40, 8
+    counts = np.array([3, 0, 9, -2] + [5] * (n - 4), np.int32)        # 9 > kmax: overflow, the first kmax stored; -2: no records
+    res = dict(counts=counts, boxes=rng.integers(-2**31, 2**31, (n, kmax, 4), dtype=np.int32),
+               scores=rng.standard_normal((n, kmax, 2)).astype(np.float32), cls=rng.integers(0, 3, (n, kmax), dtype=np.int32),
+               src=rng.integers(0, 2**31, (n, kmax), dtype=np.int32), head_large=rng.standard_normal((n, 24, 4, 5)).astype(np.float32),
+               head_small=rng.standard_normal((n, 24, 2, 3)).astype(np.float32))
+    names = b.dump_outputs(str(tmp_path / "all"), res)
+    assert names == sorted(res)
+    got = {k: np.load(tmp_path / "all" / (k + ".npy")) for k in names}
+    assert all(got[k].dtype == (np.float32 if k in ("scores", "head_large", "head_small") else np.float64) for k in names)
+    valid = np.arange(kmax)[None, :] < np.clip(counts, 0, kmax)[:, None]
+    assert valid[2].all() and not valid[3].any()
+    for k in ("boxes", "scores", "cls", "src"):
+        assert np.array_equal(got[k][valid], res[k][valid].astype(got[k].dtype)) and not got[k][~valid].any(), k
+    assert np.array_equal(got["counts"], counts) and np.array_equal(got["head_large"], res["head_large"])
+    # over the budget: a sample of frames, in frame order, every file within it, the same frames every time
+    budget = 16 << 10
+    for d in ("s1", "s2"):
+        names = b.dump_outputs(str(tmp_path / d), dict(res, head_small=res["head_small"][:10]), budget=budget)
+        assert "frames" in names and sum(os.path.getsize(tmp_path / d / (k + ".npy")) for k in names) <= budget
+    fr = np.load(tmp_path / "s1" / "frames.npy")
+    assert 1 <= len(fr) < n and np.all(np.diff(fr) > 0) and np.array_equal(fr, np.load(tmp_path / "s2" / "frames.npy"))
+    for k in names:
+        a = np.load(tmp_path / "s1" / (k + ".npy"))
+        assert np.array_equal(a, np.load(tmp_path / "s2" / (k + ".npy"))), k
+    fr = fr.astype(int)
+    assert np.array_equal(np.load(tmp_path / "s1" / "head_large.npy"), res["head_large"][fr])
+    assert np.array_equal(np.load(tmp_path / "s1" / "head_small.npy"), res["head_small"][fr[fr < 10]])
+    assert np.array_equal(np.load(tmp_path / "s1" / "counts.npy"), counts[fr])
+    with pytest.raises(ValueError):
+        b.dump_outputs(str(tmp_path / "bad"), dict(res, head_large=np.zeros((n + 1, 2), np.float32)))
+
+
+CLASS_RGB ={0: (205, 90, 106), 1: (20, 97, 199), 2: (105, 128, 112)}   # detect.py:105 colours are BGR (cv2); these are what a viewer sees
 
 
 def test_reference_result_images_carry_the_golden_boxes(golden):

@@ -1405,6 +1405,49 @@ def test_bench_line_and_multi_gpu_rehearsal(dev):
             assert j["variants"][0]["max_abs_logit_diff_vs_f32_on_this_batch"] < 1e-3
 
 
+def test_bench_dump_outputs_are_the_timed_steps_results(yf, dev, tmp_path):
+    """`bench.py --dump-outputs DIR` writes what the last timed step handed back: with two batches in flight and one at a time alike,
+    the heads and records of the 40 tiled fixture frames are bitwise what the model and post-process return for them in this process
+    (record slots past a frame's count zeroed), and the line reports the K timed steps and ms_per_step."""
+    import json
+    import subprocess
+    import sys
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "40", "--frames", "fixtures",
+            "--headline-only", "--no-live-traffic"]
+    dumps = {}
+    for extra in ([], ["--in-flight", "1"]):
+        d = tmp_path / ("in_flight_%s" % (extra[-1] if extra else "2"))
+        r = subprocess.run(base + extra + ["--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        j = json.loads(r.stdout.strip().splitlines()[-1])
+        assert j["steps"] == 3 and j["ms_per_step"] > 0
+        dumps[d.name] = {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+    a, b = dumps.values()
+    assert sorted(a) == ["boxes", "cls", "counts", "head_large", "head_small", "scores", "src"] and sorted(b) == sorted(a)
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], b[k]), k
+    io = yf.io_params_for(256)
+    m = yf.YoloFastest(io).to(dev).eval()
+    m.load_state_dict(torch.load(WEIGHTS[256], map_location=dev))
+    m.lanes, m.branches = 1, 0
+    post = yf.YOLO_post_process(io["conf_thre"], io["nms_thre"], io["num_anchors"], io["num_cls"], io["anchors"], io["input_shape"]).bind(m)
+    fx = np.load(os.path.join(ROOT, "tests", "golden", "golden_256.npz"))["input_u8"]
+    x = ((torch.from_numpy(fx[np.arange(40) % len(fx)]).float() - 128.0) / 255.0)[:, None].contiguous().to(dev)
+    with torch.no_grad():
+        hl, hs = m(x)
+    raw = post.detect_raw((hl, hs), kmax=64)
+    assert np.array_equal(a["head_large"], hl.cpu().numpy()) and np.array_equal(a["head_small"], hs.cpu().numpy())
+    counts = raw["counts"].cpu().numpy()
+    assert np.array_equal(a["counts"], counts) and counts.sum() > 40
+    valid = np.arange(64)[None, :] < np.clip(counts, 0, 64)[:, None]
+    for k in ("boxes", "scores", "cls", "src"):
+        want = raw[k].cpu().numpy()
+        assert np.array_equal(a[k][valid], want[valid]) and not a[k][~valid].any(), k
+
+
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs 2 GPUs: runs the day a multi-GPU node is leased")
 def test_two_gpu_bench_gathers_the_single_gpu_records(tmp_path):
     """SURVEY.md 8(e) parity on REAL RCCL with N = 2: `bench.py --gpus 2 --frames fixtures` (one rank per GPU, 20 bundled frames each, the
