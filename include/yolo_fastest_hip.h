@@ -297,6 +297,26 @@ int yf_cv_preprocess_u8(yf_handle h, const uint8_t *d_src, int N, int src_h, int
 int yf_forward_bgr_u8(yf_handle h, const uint8_t *d_bgr, int N, int src_h, int src_w, int gray_bits, float *d_head_large, float *d_head_small,
                       void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* The image half of the reference's DetectDataset.__getitem__ (src/model_training/dataloader/detect_dataset.py:90-103, :132-143) on the
+ * device, handle-free like the training operators (a dataset owns no model), for N same-size source frames in ONE launch:
+ *     x = fliplr?(GaussianBlur_k(resize(cvtColor_BGR2GRAY?(frame))))        per frame: k in {0 (none), 3, 5, 7}, flip in {0, 1}
+ *   d_src     u8 [n_src, src_h, src_w, src_c] (cv2.imread's BGR for src_c 3); d_index: NULL (output frame n = source frame n, n_src >= N) or
+ *             int32 [N] source frame per output frame (an entry outside 0 .. n_src - 1 leaves its output frame untouched)
+ *   gray      src_c 3 -> dst_c 1: OpenCV's 8-bit BGR2GRAY with gray_bits 15 (0 means 15) or 14 coefficients; otherwise src_c == dst_c (1 or 3)
+ *   resize    same size: none; exactly 2x: the 2x2 mean (INTER_AREA's fast path); any other size: INTER_LINEAR through the tables of
+ *             the resize-tables entry below for (src_h, src_w) -> (dst_h, dst_w) (d_xtab, d_ytab; not read otherwise, may be NULL)
+ *   blur      OpenCV's 8-bit fixed-point GaussianBlur(ksize k, sigma 0): taps /256 [64 128 64], [16 64 96 64 16], [8 28 56 72 56 28 8],
+ *             row pass exact, dst = (sum k_y row_y + 2^15) >> 16, BORDER_REFLECT_101, per channel
+ *   d_params  int32 [N]: k | flip << 8 (a k other than 3, 5, 7 means no blur); the flip is applied after the blur
+ *   outputs   d_u8 u8 [N, dst_h, dst_w, dst_c] and / or d_x float32 [N, dst_c, dst_h, dst_w] = (v - 128) / 255 (BGR order kept), NULL = not wanted
+ * Same bytes as the CPU restatement in tests/ composed with oracle/cv_oracle.py; parity with an actual OpenCV build is UNPINNED.
+ * No allocation or synchronisation; stream-ordered. */
+int yf_augment_u8(int device, const uint8_t *d_src, int src_h, int src_w, int src_c, const int *d_index, int n_src, int N, const void *d_xtab,
+                  const void *d_ytab, int dst_h, int dst_w, int dst_c, int gray_bits, const int *d_params, uint8_t *d_u8, float *d_x, void *stream);
+/* cv::resize's INTER_LINEAR tables for one (source, destination) size pair into caller-owned device memory: d_xtab int4 [dst_w],
+ * d_ytab int4 [dst_h] (16 bytes each entry).  One small kernel on `stream`, no allocation or synchronisation. */
+int yf_cv_resize_tables(int device, int src_h, int src_w, int dst_h, int dst_w, void *d_xtab, void *d_ytab, void *stream);
+
 /* Introspection used by tests / bench. */
 /* Name ("conv1_8+conv1_9+conv2_1"), layer-granular algorithmic bytes and flops per frame of launch `op` of the
  * current plan (each conv of the op reads its input and writes its output once, + residual read: SURVEY.md 8d). */

@@ -1,0 +1,162 @@
+#!/usr/bin/env python3
+"""DetectDataset throughput (dataset.py, csrc/yf_aug_kernels.hip).  GPU box:
+    python tools/dataset_bench.py --kernel            augment launch (640x512 BGR -> 256x320 gray, blur / flip drawn like the reference)
+                                                      at batch 16 and 512: event-timed ms and required bytes/s (source + float32 output)
+    python tools/dataset_bench.py --kernel --profile  the same under `rocprofv3 --kernel-trace --stats` (a child process, a run of its own):
+                                                      the kernel's own average duration from the stats file
+    python tools/dataset_bench.py --train             train() iterations (DataLoader + train_step) at batch 16, examples/s, interleaved:
+                                                      DetectDataset cache="device", cache=None, and tools/train_bench.py's no-data loop"""
+import argparse
+import csv
+import glob
+import json
+import os
+import random
+import subprocess
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+import yolo_fastest_amd as yf  # noqa: E402
+from yolo_fastest_amd import _lib, training, validation as val  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--kernel", action="store_true")
+ap.add_argument("--profile", action="store_true")
+ap.add_argument("--train", action="store_true")
+ap.add_argument("--reps", type=int, default=50)
+ap.add_argument("--steps", type=int, default=30)
+ap.add_argument("--rounds", type=int, default=3)
+ap.add_argument("--out", default=None, help="directory for the rocprofv3 output (default: a new temporary directory)")
+a = ap.parse_args()
+dev = torch.device("cuda:0")
+
+
+def kernel_bench():
+    lib = _lib.lib()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    res = {}
+    for N in (16, 512):
+        src = torch.randint(0, 256, (N, 512, 640, 3), dtype=torch.uint8, device=dev)
+        rng = random.Random(0)
+        prm = []
+        for _ in range(N):        # the reference's draws at its default probabilities (gussian_filter 0.3, fliplr 0.5)
+            k = (7 if rng.random() < 0.4 else 3) if rng.random() < 0.3 else 0
+            prm.append(k | (int(rng.random() < 0.5) << 8))
+        d_prm = torch.tensor(prm, dtype=torch.int32, device=dev)
+        x = torch.empty((N, 1, 256, 320), dtype=torch.float32, device=dev)
+
+        def launch():
+            _lib.check(lib.yf_augment_u8(dev.index, src.data_ptr(), 512, 640, 3, None, N, N, None, None, 256, 320, 1, 15, d_prm.data_ptr(),
+                                         None, x.data_ptr(), stream))
+        for _ in range(5):
+            launch()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(a.reps):
+            launch()
+        e1.record()
+        torch.cuda.synchronize()
+        ms = e0.elapsed_time(e1) / a.reps
+        need = N * (512 * 640 * 3 + 256 * 320 * 4)
+        res[N] = {"ms": round(ms, 4), "required_bytes": need, "TB_per_s": round(need / ms / 1e9, 3),
+                  "blurred_frames": sum(1 for p in prm if p & 15)}
+        print("augment batch %d: %.4f ms, %.1f MB required, %.3f TB/s (%d of %d frames blurred)"
+              % (N, ms, need / 1e6, need / ms / 1e9, res[N]["blurred_frames"], N))
+    return res
+
+
+def profile():
+    out = a.out or tempfile.mkdtemp(prefix="dataset_bench_")
+    os.makedirs(out, exist_ok=True)
+    cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", out, "-o", "aug", "--", sys.executable,
+           os.path.abspath(__file__), "--kernel", "--reps", str(a.reps)]
+    subprocess.check_call(cmd)
+    for f in glob.glob(os.path.join(out, "**", "*kernel_stats.csv"), recursive=True):
+        with open(f) as fh:
+            for row in csv.DictReader(fh):
+                if "aug_kernel" in row.get("Name", ""):
+                    print("rocprofv3 %s: calls %s, average %.4f ms, min %.4f ms, max %.4f ms" % (
+                        row["Name"][:60], row.get("Calls"), float(row.get("AverageNs", 0)) / 1e6, float(row.get("MinNs", 0)) / 1e6,
+                        float(row.get("MaxNs", 0)) / 1e6))
+
+
+def voc_tree_copies(root, copies=13):
+    """The 20 bundled frames with their fixture XMLs, linked `copies` times under new names: 260 items."""
+    import voc_tree
+    d = os.path.join(root, "train")
+    os.makedirs(os.path.join(d, "img")); os.makedirs(os.path.join(d, "xml"))
+    for c in range(copies):
+        for s in voc_tree.bundled_stems():
+            os.symlink(os.path.join(voc_tree.BUNDLED, s + ".jpg"), os.path.join(d, "img", "%s_%d.jpg" % (s, c)))
+            os.symlink(os.path.join(voc_tree.VOC, "xml", s + ".xml"), os.path.join(d, "xml", "%s_%d.xml" % (s, c)))
+    return d
+
+
+def train_bench():
+    from torch.utils.data import DataLoader
+    from yolo_fastest_amd.dataset import DetectDataset
+    io = yf.io_params_for(256)
+    torch.manual_seed(0)
+    m = yf.YoloFastest(io)
+    m.initialize_weights()
+    m = m.to(dev).train()
+    crit = [val.YOLOLossV3(io["anchors"][i], 3, io["input_shape"], dev, model=m) for i in range(2)]
+    opt = training.Adam(m.parameters(), lr=0.001)
+    B = 16
+    tmp = tempfile.mkdtemp()
+    d = voc_tree_copies(tmp)
+    aug = dict(yf.config_params["augment_params"], train_dataset_dir=d, val_dataset_dir=d)
+    loaders = {}
+    for cache in ("device", None):
+        ds = DetectDataset(io["input_shape"], io["origin_img_shape"], None, aug_params=aug, device=dev, cache=cache)
+        loaders["cache=%s" % cache] = DataLoader(ds, batch_size=B, num_workers=0, drop_last=True, pin_memory=True, shuffle=True,
+                                                  collate_fn=val.collate_fn)
+    x0 = torch.rand(B, 1, 256, 320, device=dev) - 0.5
+    t0 = torch.zeros(B, 64, 6, device=dev)
+    t0[:, 0] = torch.tensor([0.5, 0.5, 0.1, 0.1, 1.0, 255.0])
+
+    def batches(name):
+        while True:
+            if name == "no-data":
+                yield x0, t0
+            else:
+                for imgs, targets in loaders[name]:
+                    yield imgs.to(dev).float(), targets.to(dev).float()
+    gens = {n: batches(n) for n in ("cache=device", "cache=None", "no-data")}
+    for n, g in gens.items():                                        # warm-up: the device cache fills, engines and graphs are built
+        for _ in range(20):
+            imgs, targets = next(g)
+            training.train_step(m, crit, opt, imgs, targets)
+    torch.cuda.synchronize()
+    res = {n: [] for n in gens}
+    for r in range(a.rounds):
+        for n, g in gens.items():
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            for _ in range(a.steps):
+                imgs, targets = next(g)
+                training.train_step(m, crit, opt, imgs, targets)
+            torch.cuda.synchronize()
+            res[n].append(B * a.steps / (time.perf_counter() - t))
+    for n, v in res.items():
+        print("train batch %d, %s: %.0f examples/s (median of %d rounds: %s)" % (B, n, float(np.median(v)), len(v), ["%.0f" % x for x in v]))
+    print("cache=device / no-data = %.3f" % (np.median(res["cache=device"]) / np.median(res["no-data"])))
+    return {n: float(np.median(v)) for n, v in res.items()}
+
+
+out = {}
+if a.kernel and a.profile:
+    profile()
+elif a.kernel:
+    out["kernel"] = kernel_bench()
+if a.train:
+    out["train"] = train_bench()
+if out:
+    print(json.dumps(out))

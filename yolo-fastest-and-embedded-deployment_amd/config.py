@@ -1,6 +1,6 @@
 """`config_params` of the reference (src/model_training/_config.py): `io_params` (:2-20: anchors, shapes, thresholds, class names;
-save_path / log_path relative instead of the author's home directory) and `train_params` (:38-50), same names and meaning.
-`augment_params` belongs to the dataset code, which is not part of this package."""
+save_path / log_path relative instead of the author's home directory), `augment_params` (:23-36: the dataset directories, relative
+like save_path, and the augmentation probabilities DetectDataset reads -- dataset.py) and `train_params` (:38-50), same names and meaning."""
 import copy
 
 config_params = {
@@ -25,6 +25,19 @@ config_params = {
         "conf_thre": 0.5,
         "nms_thre": 0.2,
         "class_names": ["carrier", "defender", "destroyer"],
+    },
+    "augment_params": {
+        "train_dataset_dir": "./data/train_data/",   # Pascal-VOC trees: <dir>/xml/*.xml, <dir>/img/<stem>.jpg
+        "val_dataset_dir": "./data/val_data/",
+        "degrees": 0.0,                     # the reference does not implement these six (detect_dataset.py:131): kept for its config's shape
+        "translate": 0.0,
+        "scale": 1.0,
+        "shear": 0.0,
+        "perspective": 0.0,
+        "flipud": 0.0,
+        "fliplr": 0.5,                      # probability of a left-right flip
+        "mixup": 0.0,
+        "gussian_filter": 0.3,              # probability of a Gaussian blur (then 7x7 with probability 0.4, else 3x3); the reference's spelling
     },
     "train_params": {
         "pretrained_pth": "",               # a .pth to start from; otherwise initialize_weights()

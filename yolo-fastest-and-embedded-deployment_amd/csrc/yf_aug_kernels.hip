@@ -1,0 +1,292 @@
+// yf_aug_kernels.hip -- the image half of the reference's DetectDataset.__getitem__ (src/model_training/dataloader/detect_dataset.py:90-103,
+// :123-162) on the device, for a batch of same-size source frames in ONE launch:
+//     img = cv2.cvtColor(ori_img, cv2.COLOR_BGR2GRAY)        (:96-97, 1-channel net on BGR frames)
+//     img = cv2.resize(img, (input_shape[1], input_shape[0])) (:101-102)
+//     img = cv2.GaussianBlur(img, (k, k), 0)                  (:135-141, k = 7 or 3 per frame; 5 is accepted as well)
+//     img = np.fliplr(img)                                    (:142-143, per frame)
+// -> u8 [N, H, W, C] and / or float32 [N, C, H, W] = (v - 128) / 255 (what DetectDataset.collate_fn's `(u8 - 128.0) / 255` gives once cast to
+// float32, the same expression as the stem's fused u8 entry).  Channels keep cv2.imread's BGR order, as the reference's dataset does.
+//   gray / resize: the arithmetic of yf_cv_kernels.hip (OpenCV's 8-bit BGR2GRAY with 14- or 15-bit coefficients; same size: a copy; exactly
+//     1/2: the 2x2 mean (a + b + c + d + 2) >> 2; otherwise INTER_LINEAR through cv::resize's tables from launch_cv_tables).
+//   blur: OpenCV's 8-bit fixed-point GaussianBlur for sigma = 0 (the ufixedpoint16 row pass and ufixedpoint32 column pass of
+//     modules/imgproc/src/smooth.simd.hpp): taps in 1/256 units k3 = [64 128 64], k5 = [16 64 96 64 16], k7 = [8 28 56 72 56 28 8]; the row
+//     pass is exact in uint16, dst = (sum_y k_y * row_y + 2^15) >> 16; BORDER_REFLECT_101 on all four sides; every channel on its own.
+//   flip: after the blur (the taps and reflect-101 are symmetric, so the two commute; tests/test_gpu_dataset.py shows it).
+// One workgroup owns `tr` destination rows of one frame: it stages those rows plus a 3-row halo of the resized (gray) image in LDS (computed
+// straight from the source bytes, as cv_pre_kernel does), runs the row pass into a uint16 LDS buffer and the column pass out of it.  A frame
+// whose k is 0 stages no halo and skips both passes (k is uniform per workgroup).  Integer arithmetic only on the byte path.
+#include <hip/hip_runtime.h>
+#include <stdarg.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include "../../include/yolo_fastest_hip.h"
+#include "yf_kernels.h"
+
+namespace yf {
+int set_error(int code, const char* msg);   // yf_engine.hip: the slot yf_last_error_string() reads
+}
+
+namespace {
+
+int fail(int code, const char* fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    return yf::set_error(code, buf);
+}
+#define HIP_OK(expr)                                                                                     \
+    do {                                                                                                 \
+        hipError_t e_ = (expr);                                                                          \
+        if (e_ != hipSuccess) return fail(YF_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));      \
+    } while (0)
+
+constexpr int AUG_R = 3;                  // halo of the widest kernel (7 x 7)
+constexpr int AUG_MAX_TR = 16;            // destination rows per workgroup at most
+constexpr int AUG_LDS = 48 * 1024;        // LDS budget of one workgroup (tile + row-pass buffer)
+
+// the taps, centred in 7 slots (a shorter kernel has zeros at the ends, which add nothing)
+__constant__ int aug_taps[3][7] = {{0, 0, 64, 128, 64, 0, 0}, {0, 16, 64, 96, 64, 16, 0}, {8, 28, 56, 72, 56, 28, 8}};
+
+struct AugArgs {
+    const uint8_t* src;           // [n_src, sh, sw, sc]
+    const int* index;             // [n] frame of the source stack per output frame, or null (frame n)
+    int n_src, n, sh, sw, sc;
+    int dh, dw, dc;
+    int mode, gray;               // as CvArgs
+    const int4* xtab;             // mode 2
+    const int4* ytab;
+    const int* params;            // [n] k (0, 3, 5, 7) | flip << 8
+    uint8_t* u8;                  // [n, dh, dw, dc] or null
+    float* x;                     // [n, dc, dh, dw] or null
+    int tr, pitch;                // destination rows per workgroup; LDS row pitch of the u8 tile (bytes, multiple of 16)
+};
+
+// cv::borderInterpolate(p, n, BORDER_REFLECT_101)
+__device__ __forceinline__ int reflect101(int p, int n)
+{
+    if (n == 1) return 0;
+    while ((unsigned)p >= (unsigned)n) p = p < 0 ? -p : 2 * n - 2 - p;
+    return p;
+}
+
+template <int GRAY>   // 0: plain channel c; 14 / 15: BGR -> gray
+__device__ __forceinline__ int src_px(const uint8_t* __restrict__ row, int x, int sc, int c)
+{
+    if constexpr (GRAY == 0) {
+        return row[(long)x * sc + c];
+    } else {
+        const uint8_t* p = row + (long)x * 3;
+        constexpr int RY = GRAY == 14 ? 4899 : 9798, GY = GRAY == 14 ? 9617 : 19235, BY = GRAY == 14 ? 1868 : 3735;
+        return (p[0] * BY + p[1] * GY + p[2] * RY + (1 << (GRAY - 1))) >> GRAY;
+    }
+}
+
+template <int GRAY, int MODE, int C>
+__global__ void __launch_bounds__(256) aug_kernel(AugArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t aug_smem[];
+    const int groups = (a.dh + a.tr - 1) / a.tr;
+    const int n = blockIdx.x / groups, dy0 = (blockIdx.x - n * groups) * a.tr;
+    const int f = a.index ? a.index[n] : n;
+    if (f < 0 || f >= a.n_src) return;                       // an index outside the stack leaves its output frame untouched
+    const int p = a.params[n];
+    const int k = ((p & 15) == 3 || (p & 15) == 5 || (p & 15) == 7) ? (p & 15) : 0;
+    const bool flip = (p >> 8) & 1;
+    const int* const taps = k ? aug_taps[(k - 3) >> 1] : aug_taps[0];
+    const int rows = min(a.tr, a.dh - dy0);
+    const int halo = k ? AUG_R : 0;
+    const int T = rows + 2 * halo;                            // staged rows: destination rows dy0 - halo .. dy0 + rows + halo - 1 (reflected)
+    const uint8_t* const src = a.src + (long)f * a.sh * a.sw * a.sc;
+    const long rs = (long)a.sw * a.sc;
+    const int quads = (a.dw + 3) >> 2;
+    uint8_t* const tile = aug_smem;                                                              // [T][pitch]
+    uint16_t* const hb = reinterpret_cast<uint16_t*>(aug_smem + (size_t)(a.tr + 2 * AUG_R) * a.pitch);   // [T][dw * C]
+    const int re = a.dw * C;
+
+    // ---- stage: cvtColor + resize of the tile's rows, 4 destination pixels (all channels) per task, one 4-byte LDS store per channel ----
+#pragma unroll 1
+    for (int t = threadIdx.x; t < T * quads; t += 256) {
+        const int r = t / quads, dx0 = (t - r * quads) * 4;
+        const int y = reflect101(dy0 - halo + r, a.dh);
+        int y0 = y, y1 = y, b0 = 0, b1 = 0;
+        if constexpr (MODE == 1) { y0 = 2 * y; y1 = 2 * y + 1; }
+        if constexpr (MODE == 2) { const int4 ty = a.ytab[y]; y0 = ty.x; y1 = ty.y; b0 = ty.z; b1 = ty.w; }
+        const uint8_t* const row0 = src + y0 * rs;
+        const uint8_t* const row1 = src + y1 * rs;
+        uint32_t packed[C];
+#pragma unroll
+        for (int w = 0; w < C; ++w) packed[w] = 0u;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int dx = dx0 + i;
+            if (dx >= a.dw) break;
+            int x0 = dx, x1 = dx, a0 = 0, a1 = 0;
+            if constexpr (MODE == 1) { x0 = 2 * dx; x1 = 2 * dx + 1; }
+            if constexpr (MODE == 2) { const int4 tx = a.xtab[dx]; x0 = tx.x; x1 = tx.y; a0 = tx.z; a1 = tx.w; }
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                int v;
+                if constexpr (MODE == 0) {
+                    v = src_px<GRAY>(row0, x0, a.sc, c);
+                } else if constexpr (MODE == 1) {
+                    v = (src_px<GRAY>(row0, x0, a.sc, c) + src_px<GRAY>(row0, x1, a.sc, c) + src_px<GRAY>(row1, x0, a.sc, c) +
+                         src_px<GRAY>(row1, x1, a.sc, c) + 2) >> 2;
+                } else {
+                    const int r0 = src_px<GRAY>(row0, x0, a.sc, c) * a0 + src_px<GRAY>(row0, x1, a.sc, c) * a1;
+                    const int r1 = src_px<GRAY>(row1, x0, a.sc, c) * a0 + src_px<GRAY>(row1, x1, a.sc, c) * a1;
+                    v = (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2;
+                }
+                const int kk = i * C + c;
+                packed[kk >> 2] |= (uint32_t)(v & 255) << (8 * (kk & 3));
+            }
+        }
+        uint32_t* const o = reinterpret_cast<uint32_t*>(tile + r * a.pitch + dx0 * C);   // the pitch holds quads * 4 * C bytes
+#pragma unroll
+        for (int w = 0; w < C; ++w) o[w] = packed[w];
+    }
+    __syncthreads();
+
+    // ---- row pass (blurred frames only): sum_x k_x * tile, exact in uint16 (at most 255 * 256) ----
+    if (k) {
+#pragma unroll 1
+        for (int e = threadIdx.x; e < T * a.dw; e += 256) {
+            const int r = e / a.dw, x = e - r * a.dw;
+            const uint8_t* const tr = tile + r * a.pitch;
+            int acc[C];
+#pragma unroll
+            for (int c = 0; c < C; ++c) acc[c] = 0;
+#pragma unroll
+            for (int i = 0; i < 7; ++i) {
+                const int xs = reflect101(x + i - AUG_R, a.dw);
+#pragma unroll
+                for (int c = 0; c < C; ++c) acc[c] += taps[i] * tr[xs * C + c];
+            }
+#pragma unroll
+            for (int c = 0; c < C; ++c) hb[r * re + x * C + c] = (uint16_t)acc[c];
+        }
+        __syncthreads();
+    }
+
+    // ---- column pass + flip + stores: 4 destination pixels per task ----
+#pragma unroll 1
+    for (int t = threadIdx.x; t < rows * quads; t += 256) {
+        const int r = t / quads, dx0 = (t - r * quads) * 4, dy = dy0 + r;
+        uint32_t packed[C];
+        float fv[C][4];
+#pragma unroll
+        for (int w = 0; w < C; ++w) packed[w] = 0u;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int dx = dx0 + i;
+            if (dx >= a.dw) break;
+            const int sx = flip ? a.dw - 1 - dx : dx;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                int v;
+                if (k) {
+                    int acc = 0;
+#pragma unroll
+                    for (int j = 0; j < 7; ++j) acc += taps[j] * (int)hb[(r + j) * re + sx * C + c];
+                    v = (acc + (1 << 15)) >> 16;
+                } else {
+                    v = tile[r * a.pitch + sx * C + c];
+                }
+                const int kk = i * C + c;
+                packed[kk >> 2] |= (uint32_t)v << (8 * (kk & 3));
+                fv[c][i] = ((float)v - 128.0f) / 255.0f;
+            }
+        }
+        const int nb = a.dw - dx0 < 4 ? a.dw - dx0 : 4;
+        if (a.u8) {
+            uint8_t* o = a.u8 + (((long)n * a.dh + dy) * a.dw + dx0) * C;
+            if (nb == 4 && ((reinterpret_cast<uintptr_t>(o) & 3) == 0)) {
+#pragma unroll
+                for (int w = 0; w < C; ++w) reinterpret_cast<uint32_t*>(o)[w] = packed[w];
+            } else {
+                for (int kk = 0; kk < nb * C; ++kk) o[kk] = (uint8_t)(packed[kk >> 2] >> (8 * (kk & 3)));
+            }
+        }
+        if (a.x) {
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                float* o = a.x + (((long)n * C + c) * a.dh + dy) * a.dw + dx0;
+                if (nb == 4 && ((reinterpret_cast<uintptr_t>(o) & 15) == 0)) {
+                    *reinterpret_cast<float4*>(o) = make_float4(fv[c][0], fv[c][1], fv[c][2], fv[c][3]);
+                } else {
+                    for (int i = 0; i < nb; ++i) o[i] = fv[c][i];
+                }
+            }
+        }
+    }
+}
+
+template <int GRAY, int C>
+void launch_aug_mode(const AugArgs& a, size_t lds, hipStream_t s)
+{
+    const unsigned grid = (unsigned)((long)a.n * ((a.dh + a.tr - 1) / a.tr));
+    if (a.mode == 0) hipLaunchKernelGGL((aug_kernel<GRAY, 0, C>), dim3(grid), dim3(256), lds, s, a);
+    else if (a.mode == 1) hipLaunchKernelGGL((aug_kernel<GRAY, 1, C>), dim3(grid), dim3(256), lds, s, a);
+    else hipLaunchKernelGGL((aug_kernel<GRAY, 2, C>), dim3(grid), dim3(256), lds, s, a);
+}
+
+}  // namespace
+
+extern "C" {
+
+int yf_cv_resize_tables(int device, int src_h, int src_w, int dst_h, int dst_w, void* d_xtab, void* d_ytab, void* stream)
+{
+    if (src_h <= 0 || src_w <= 0 || dst_h <= 0 || dst_w <= 0 || src_h > 16384 || src_w > 16384 || dst_h > 16384 || dst_w > 16384 || !d_xtab || !d_ytab)
+        return fail(YF_E_INVALID, "yf_cv_resize_tables: bad argument");
+    HIP_OK(hipSetDevice(device));
+    yf::launch_cv_tables(src_h, src_w, dst_h, dst_w, static_cast<int4*>(d_xtab), static_cast<int4*>(d_ytab), (hipStream_t)stream);
+    HIP_OK(hipGetLastError());
+    return YF_OK;
+}
+
+int yf_augment_u8(int device, const uint8_t* d_src, int src_h, int src_w, int src_c, const int* d_index, int n_src, int N, const void* d_xtab,
+                  const void* d_ytab, int dst_h, int dst_w, int dst_c, int gray_bits, const int* d_params, uint8_t* d_u8, float* d_x, void* stream)
+{
+    if (!d_src || !d_params || (!d_u8 && !d_x) || N <= 0 || n_src <= 0 || (!d_index && n_src < N))
+        return fail(YF_E_INVALID, "yf_augment_u8: null pointer, no output, N <= 0 or fewer source frames than N without an index table");
+    if (src_h <= 0 || src_w <= 0 || src_h > 16384 || src_w > 16384 || dst_h <= 0 || dst_w <= 0 || dst_h > 16384 || dst_w > 16384)
+        return fail(YF_E_INVALID, "yf_augment_u8: source %dx%d / destination %dx%d", src_h, src_w, dst_h, dst_w);
+    AugArgs a{};
+    a.src = d_src; a.index = d_index; a.n_src = n_src; a.n = N; a.sh = src_h; a.sw = src_w; a.sc = src_c; a.dh = dst_h; a.dw = dst_w; a.dc = dst_c;
+    a.params = d_params; a.u8 = d_u8; a.x = d_x;
+    if (src_c == 3 && dst_c == 1) {
+        if (gray_bits != 0 && gray_bits != 14 && gray_bits != 15) return fail(YF_E_INVALID, "gray_bits must be 14, 15 or 0 (= 15)");
+        a.gray = gray_bits == 14 ? 14 : 15;
+    } else if (src_c == dst_c && (src_c == 1 || src_c == 3)) {
+        a.gray = 0;
+    } else {
+        return fail(YF_E_INVALID, "yf_augment_u8: %d-channel frames from %d-channel sources (gray from BGR, or 1 / 3 channels as they are)", dst_c, src_c);
+    }
+    a.mode = (src_h == dst_h && src_w == dst_w) ? 0 : (src_h == 2 * dst_h && src_w == 2 * dst_w) ? 1 : 2;
+    if (a.mode == 2) {
+        if (!d_xtab || !d_ytab) return fail(YF_E_INVALID, "yf_augment_u8: a %dx%d -> %dx%d resize needs the tables of yf_cv_resize_tables", src_h, src_w, dst_h, dst_w);
+        a.xtab = static_cast<const int4*>(d_xtab); a.ytab = static_cast<const int4*>(d_ytab);
+    }
+    const int quads = (dst_w + 3) >> 2;
+    a.pitch = (quads * 4 * dst_c + 15) & ~15;
+    const long per_row = (long)a.pitch + 2L * dst_w * dst_c;   // u8 tile row + uint16 row-pass row
+    const long tr = AUG_LDS / per_row - 2 * AUG_R;
+    if (tr < 1) return fail(YF_E_INVALID, "yf_augment_u8: rows of %d x %d bytes do not fit the LDS tile", dst_w, dst_c);
+    a.tr = tr < AUG_MAX_TR ? (int)tr : AUG_MAX_TR;
+    const size_t lds = (size_t)(a.tr + 2 * AUG_R) * per_row;
+    const long groups = (long)N * ((dst_h + a.tr - 1) / a.tr);
+    if (groups > 0x7fffffffL) return fail(YF_E_INVALID, "yf_augment_u8: batch too large for one launch");
+    HIP_OK(hipSetDevice(device));
+    const hipStream_t s = (hipStream_t)stream;
+    if (a.gray == 14) launch_aug_mode<14, 1>(a, lds, s);
+    else if (a.gray == 15) launch_aug_mode<15, 1>(a, lds, s);
+    else if (dst_c == 1) launch_aug_mode<0, 1>(a, lds, s);
+    else launch_aug_mode<0, 3>(a, lds, s);
+    HIP_OK(hipGetLastError());
+    return YF_OK;
+}
+
+}  // extern "C"

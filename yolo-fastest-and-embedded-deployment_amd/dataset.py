@@ -1,0 +1,273 @@
+"""The reference's training data: `DetectDataset` of src/model_training/dataloader/detect_dataset.py:42-162 over a Pascal-VOC tree
+(`<dir>/xml/*.xml` + `<dir>/img/<stem>.jpg`), with the image work on the GPU (csrc/yf_aug_kernels.hip, `yf_augment_u8`).
+
+Same constructor, log lines, file order (os.listdir of xml/), label arithmetic and random draws (the global `random` module, in the
+reference's order: blur?, which blur, flip?) -- so `__getitem__` returns the reference's item exactly: a float64 HWC image `u8 - 128.0`
+(channels in cv2.imread's BGR order; gray for a 1-channel net) and float64 (max_boxes, 6) boxes (xc, yc, w, h, cls, 255.0), normalised
+by the CONFIGURED origin_img_shape.  The per-frame pixels -- BGR2GRAY, cv2.resize, cv2.GaussianBlur((7, 7) or (3, 3), 0), np.fliplr --
+are one kernel launch (OpenCV's 8-bit fixed-point arithmetic restated; parity with a real OpenCV build is unpinned).
+Decoding is PIL's (cv2 is not a dependency).  There is no CPU image path: labels work anywhere, images need the GPU.
+
+Additions: `device`, `gray_bits` (OpenCV's 15- or 14-bit BGR2GRAY coefficients, as YoloFastest.gray_bits), `cache="device"` (decoded
+frames kept in GPU memory, one uint8 stack per source size, filled on first access), `class_names` (the reference reads
+config_params["io_params"]["class_names"]) and `__getitems__`, which DataLoader calls with a whole batch of indices: the same draws in
+index order, ONE launch per source size, float32 device images [N, C, H, W] = collate_fn's `(u8 - 128.0) / 255` bit for bit.
+
+Deviation: the reference cannot return an image without objects -- `np.array([])` is 1-D, so a flip raises IndexError (`labels[:, 1]`,
+:143) and otherwise the box copy raises ValueError (:159); here such an image is blurred / flipped as drawn and gets all-zero boxes (the
+draws stay in the reference's order, so the items after it are the reference's)."""
+import ctypes
+import logging
+import os
+import random
+import xml.etree.ElementTree as xmlET
+
+import numpy as np
+import torch
+
+from . import _lib
+from .config import config_params
+
+
+def xyxy2xywh(x):
+    """utils/general.py:8-15 for numpy [n, 4]."""
+    y = np.zeros_like(x)
+    y[:, 0] = (x[:, 0] + x[:, 2]) / 2
+    y[:, 1] = (x[:, 1] + x[:, 3]) / 2
+    y[:, 2] = x[:, 2] - x[:, 0]
+    y[:, 3] = x[:, 3] - x[:, 1]
+    return y
+
+
+class DetectBatch:
+    """A batch from `DetectDataset.__getitems__`: `imgs` float32 device [N, C, H, W], `targets` float64 host [N, max_boxes, 6].
+    Unpacks as `imgs, targets`.  `pin_memory()` is a no-op: the images already live on the GPU (DataLoader(pin_memory=True) calls it;
+    this is deliberately not a tuple or Sequence, which torch would take apart first)."""
+    __slots__ = ("imgs", "targets")
+
+    def __init__(self, imgs, targets):
+        self.imgs, self.targets = imgs, targets
+
+    def __iter__(self):
+        return iter((self.imgs, self.targets))
+
+    def pin_memory(self, device=None):
+        return self
+
+
+class DetectDataset(torch.utils.data.Dataset):
+    def __init__(self, input_shape, origin_img_shape, logger, augment=True, aug_params=None, max_boxes=64, val=False, device=None,
+                 gray_bits=15, cache=None, class_names=None):
+        if aug_params is None:
+            aug_params = config_params["augment_params"]
+        self.aug_params = aug_params
+        self.origin_img_shape = list(origin_img_shape)
+        self.input_shape = list(input_shape)
+        if len(self.input_shape) != 3 or self.input_shape[2] not in (1, 3):
+            raise ValueError("input_shape[2] must be 1 or 3: image files decode to 3 channels (cv2.imread) and a 1-channel net gets them as gray")
+        if self.input_shape[2] == 1 and self.origin_img_shape[2] == 1:
+            raise ValueError("input_shape[2] == origin_img_shape[2] == 1: the reference skips BGR2GRAY then and yields [H, W, 3, 1] images")
+        if self.input_shape[0] <= 0 or self.input_shape[1] <= 0 or self.origin_img_shape[0] <= 0 or self.origin_img_shape[1] <= 0:
+            raise ValueError("image shapes must be positive")
+        if gray_bits not in (14, 15):
+            raise ValueError("gray_bits must be 14 or 15")
+        if cache not in (None, "device"):
+            raise ValueError('cache must be None or "device"')
+        self.logger = logger = logger or logging.getLogger(__name__)
+        if val:
+            logger.info(" Val Datasest Loading..")
+            self.dataset_dir = aug_params["val_dataset_dir"]
+        else:
+            logger.info("Training Datasest Loading..")
+            self.dataset_dir = aug_params["train_dataset_dir"]
+        self.fliplr = aug_params["fliplr"]
+        self.gussian_filter = aug_params["gussian_filter"]
+        self.max_boxes = max_boxes
+        self.augment = augment
+        self.gray_bits = gray_bits
+        self.cache = cache
+        self.classes = list(class_names if class_names is not None else config_params["io_params"]["class_names"])
+        if device is None:
+            device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+
+        self.file_path_img = os.path.join(self.dataset_dir, "img")
+        self.file_path_xml = os.path.join(self.dataset_dir, "xml")
+        self.dataset_dict = {}
+        pathDir = os.listdir(self.file_path_xml)
+        for idx in range(len(pathDir)):
+            if idx % 1000 == 0:
+                logger.info("Loading:%d/%d" % (idx, len(pathDir)))
+            filename = pathDir[idx]
+            tree = xmlET.parse(os.path.join(self.file_path_xml, filename))
+            _labels = []
+            for obj in tree.findall("object"):
+                _bbox = obj.find("bndbox")
+                x1 = float(_bbox.find("xmin").text)
+                y1 = float(_bbox.find("ymin").text)
+                x2 = float(_bbox.find("xmax").text)
+                y2 = float(_bbox.find("ymax").text)
+                _labels.append([self.classes.index(obj.find("name").text), x1, y1, x2, y2])
+            _image_name = os.path.join(self.file_path_img, os.path.splitext(filename)[0] + ".jpg")
+            self.dataset_dict.update({_image_name: _labels})
+        self.img_list = list(self.dataset_dict.keys())
+        logger.info("Loading finish！ dataset contain %d items" % (self.__len__()))
+        self._stacks = {}     # cache="device": (h, w) -> [uint8 tensor [cap, h, w, 3], filled count]
+        self._slot = {}       # cache="device": index -> ((h, w), slot in that stack)
+        self._tables = {}     # (h, w) -> uint8 device tensor holding cv::resize's int4 tables [dw + dh]
+
+    def __len__(self):
+        return len(self.img_list)
+
+    # ---- labels and draws (host; no GPU needed) ----
+    def draw(self, index):
+        """The host half of __getitem__ (:126-160): the label arithmetic and the random draws of one item, in the reference's order.
+        -> (blur kernel size: 0, 3 or 7; flip; float64 boxes [max_boxes, 6])."""
+        labels = np.array(self.dataset_dict[self.img_list[index]])
+        if len(labels):
+            labels[:, 1:5] = xyxy2xywh(labels[:, 1:5])
+            labels[:, [2, 4]] /= self.origin_img_shape[0]
+            labels[:, [1, 3]] /= self.origin_img_shape[1]
+        k, flip = 0, False
+        if self.augment:
+            if random.random() < self.gussian_filter:
+                _ret = random.random()
+                k = 7 if _ret < 0.4 else 3          # the reference's `elif _ret < 0.2` (5 x 5) cannot be reached
+            if random.random() < self.fliplr:
+                flip = True
+                if len(labels):                     # deviation: no IndexError for an image without objects (nor ValueError below)
+                    labels[:, 1] = 1 - labels[:, 1]
+        nL = len(labels)
+        if nL:
+            cls_id = labels[:, 0].copy()
+            labels[:, 0:4] = labels[:, 1:5]
+            labels[:, 4] = cls_id
+        out = np.zeros([self.max_boxes, 6])
+        m = min(nL, self.max_boxes)
+        if m:                                       # deviation: the reference's copy raises ValueError for no objects
+            out[:m, 0:5] = labels[:m]
+            out[:m, 5] = 255.0
+        return k, flip, out
+
+    # ---- images (GPU) ----
+    def _need_gpu(self):
+        if self.device.type != "cuda":
+            raise RuntimeError("DetectDataset images have no CPU path (csrc/yf_aug_kernels.hip): pass device='cuda'")
+
+    def _decode(self, index):
+        """cv2.imread's frame: uint8 [h, w, 3], BGR (PIL decode, channels reversed as detect.py does)."""
+        from PIL import Image
+        with Image.open(self.img_list[index]) as im:
+            rgb = np.asarray(im.convert("RGB"))
+        bgr = np.ascontiguousarray(rgb[:, :, ::-1])
+        hw = bgr.shape[:2]
+        if list(self.input_shape[0:2]) == list(self.origin_img_shape[0:2]) and list(hw) != list(self.input_shape[0:2]):
+            raise ValueError("%s is %dx%d, but origin_img_shape[:2] == input_shape[:2] = %s: the reference does not resize then and "
+                             "would yield a mis-shaped image" % (self.img_list[index], hw[0], hw[1], self.input_shape[0:2]))
+        return bgr
+
+    def _cached(self, index):
+        """cache='device': (source size, slot) of frame `index`, decoding and uploading it on first access."""
+        if index in self._slot:
+            return self._slot[index]
+        bgr = self._decode(index)
+        hw = bgr.shape[:2]
+        ent = self._stacks.get(hw)
+        if ent is None:
+            ent = self._stacks[hw] = [torch.empty((8,) + bgr.shape, dtype=torch.uint8, device=self.device), 0]
+        if ent[1] == ent[0].shape[0]:
+            grown = torch.empty((2 * ent[1],) + bgr.shape, dtype=torch.uint8, device=self.device)
+            grown[:ent[1]].copy_(ent[0])
+            ent[0] = grown
+        ent[0][ent[1]].copy_(torch.from_numpy(bgr))
+        self._slot[index] = (hw, ent[1])
+        ent[1] += 1
+        return self._slot[index]
+
+    def _resize_tables(self, hw, stream):
+        H, W = self.input_shape[0], self.input_shape[1]
+        if tuple(hw) in ((H, W), (2 * H, 2 * W)):
+            return None, None
+        t = self._tables.get(hw)
+        if t is None:
+            t = self._tables[hw] = torch.empty(((W + H) * 16,), dtype=torch.uint8, device=self.device)
+            _lib.check(_lib.lib().yf_cv_resize_tables(self.device.index, hw[0], hw[1], H, W, t.data_ptr(), t.data_ptr() + W * 16, stream))
+        return t.data_ptr(), t.data_ptr() + W * 16
+
+    def augment_images(self, indices, params, out_u8=False):
+        """The frames `indices` with per-frame (k, flip) `params` through yf_augment_u8, one launch per source size.
+        -> float32 device [N, C, H, W] ((v - 128) / 255), or uint8 device [N, H, W, C] with out_u8."""
+        self._need_gpu()
+        H, W, C = self.input_shape
+        N = len(indices)
+        dev = self.device
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        out = torch.empty((N, H, W, C) if out_u8 else (N, C, H, W), dtype=torch.uint8 if out_u8 else torch.float32, device=dev)
+        packed = [int(k) | (int(bool(f)) << 8) for k, f in params]
+        groups = {}
+        if self.cache == "device":
+            for pos, i in enumerate(indices):
+                hw, slot = self._cached(i)
+                groups.setdefault(hw, []).append((pos, slot))
+        else:
+            frames = {}
+            for pos, i in enumerate(indices):
+                bgr = self._decode(i)
+                frames.setdefault(bgr.shape[:2], []).append(bgr)
+                groups.setdefault(bgr.shape[:2], []).append((pos, len(frames[bgr.shape[:2]]) - 1))
+        lib = _lib.lib()
+        for hw, members in groups.items():
+            pos = [p for p, _ in members]
+            if self.cache == "device":
+                stack, n_src = self._stacks[hw][0], self._stacks[hw][1]
+                index = torch.tensor([s for _, s in members], dtype=torch.int32).to(dev)
+            else:
+                stack = torch.from_numpy(np.stack(frames[hw])).to(dev)
+                n_src, index = stack.shape[0], None
+            prm = torch.tensor([packed[p] for p in pos], dtype=torch.int32).to(dev)
+            whole = len(groups) == 1
+            dst = out if whole else torch.empty((len(pos),) + tuple(out.shape[1:]), dtype=out.dtype, device=dev)
+            xt, yt = self._resize_tables(hw, stream)
+            _lib.check(lib.yf_augment_u8(dev.index, stack.data_ptr(), hw[0], hw[1], 3, None if index is None else index.data_ptr(), n_src,
+                                         len(pos), xt, yt, H, W, C, self.gray_bits, prm.data_ptr(),
+                                         dst.data_ptr() if out_u8 else None, None if out_u8 else dst.data_ptr(), ctypes.c_void_p(stream)))
+            if not whole:
+                out.index_copy_(0, torch.tensor(pos, device=dev), dst)
+        return out
+
+    def __getitem__(self, index):
+        """The reference's item: (float64 [H, W, C] image u8 - 128.0, float64 [max_boxes, 6] boxes)."""
+        self._need_gpu()
+        k, flip, boxes = self.draw(index)
+        u8 = self.augment_images([index], [(k, flip)], out_u8=True)[0].cpu().numpy()
+        img = u8 - 128.0
+        return np.ascontiguousarray(img), boxes
+
+    def __getitems__(self, indices):
+        """A whole batch: the draws of `indices` in order (as item after item would make them), images in one launch per source size.
+        -> DetectBatch(float32 device [N, C, H, W], float64 host [N, max_boxes, 6]); collate_fn passes it through."""
+        self._need_gpu()
+        indices = [int(i) for i in indices]
+        draws = [self.draw(i) for i in indices]
+        imgs = self.augment_images(indices, [(k, f) for k, f, _ in draws])
+        targets = torch.from_numpy(np.stack([b for _, _, b in draws])) if draws else torch.zeros((0, self.max_boxes, 6), dtype=torch.float64)
+        return DetectBatch(imgs, targets)
+
+    @staticmethod
+    def collate_fn(batch):
+        """detect_dataset.py:105-117 (stack, NHWC -> NCHW, / 255: float64 images) for a list of items; a DetectBatch passes through."""
+        if isinstance(batch, DetectBatch):
+            return batch
+        images = []
+        bboxes = []
+        for img, box in batch:
+            images.append([img])
+            bboxes.append([box])
+        images = np.concatenate(images, axis=0)
+        bboxes = np.concatenate(bboxes, axis=0)
+        images = images.transpose(0, 3, 1, 2)
+        images = torch.from_numpy(images).div(255.0)
+        bboxes = torch.from_numpy(bboxes)
+        return images, bboxes

@@ -534,9 +534,11 @@ def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, l
     (:58-65), DataLoader(batch_size, drop_last, shuffle) (:71-73), Adam(lr0, betas (0.9, 0.999), eps 1e-8) (:84), the cosine
     LambdaLR stepped per epoch (:87-91), the linear warm-up of the first max(3 epochs, 1000 iterations) written into param_groups per
     iteration (:103-109), the log line every 10 iterations (:134-150, same format), get_mAP after epoch 4 (:153-154) and one
-    `YOLO-Fastest_epoch_N.pth` state-dict per epoch (:155).  Differences: the datasets are passed in (the reference builds its
-    DetectDataset -- cv2 augmentation over files that are not shipped -- from paths in the config); items are DetectDataset's
-    ((h, w, c) uint8-range image, (64, 6) boxes), batched by validation.collate_fn (= DetectDataset.collate_fn).  tbwriter may be None.
+    `YOLO-Fastest_epoch_N.pth` state-dict per epoch (:155).  Differences: the datasets are passed in (the reference builds them from
+    config paths, train.py:68-76; here: `dataset.DetectDataset(io["input_shape"], io["origin_img_shape"], logger,
+    aug_params=params["augment_params"])` and the same with `augment=False, val=True`); items are DetectDataset's ((h, w, c) uint8-range
+    image, (64, 6) boxes), batched by validation.collate_fn (= DetectDataset.collate_fn), or DetectDataset's whole-batch
+    `__getitems__` (device images), which the collate passes through.  tbwriter may be None.
     Returns the trained model."""
     import logging
     import os
@@ -547,7 +549,7 @@ def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, l
     from . import validation
     from .model import YoloFastest
     if train_dataset is None:
-        raise ValueError("pass train_dataset (the reference's DetectDataset needs its un-shipped data and cv2)")
+        raise ValueError("pass train_dataset (e.g. dataset.DetectDataset over a Pascal-VOC tree, as train.py:68-76 builds it)")
     logger = logger or logging.getLogger(__name__)
     io, tp = params["io_params"], params["train_params"]
     save_path = io["save_path"]

@@ -145,8 +145,12 @@ def non_max_suppression(prediction, num_classes, conf_thres=0.5, nms_thres=0.4, 
 
 def collate_fn(batch):
     """What the reference's DetectDataset.collate_fn does (dataloader/detect_dataset.py:106-117): stack (h,w,c) images and
-    (64,6) boxes, NHWC -> NCHW, divide the images by 255."""
+    (64,6) boxes, NHWC -> NCHW, divide the images by 255.  A batch that dataset.DetectDataset.__getitems__ built already (device
+    images, host boxes) passes through."""
     import numpy as np
+    from .dataset import DetectBatch
+    if isinstance(batch, DetectBatch):
+        return batch
     images = np.concatenate([[img] for img, _ in batch], axis=0).transpose(0, 3, 1, 2)
     bboxes = np.concatenate([[box] for _, box in batch], axis=0)
     return torch.from_numpy(images).div(255.0), torch.from_numpy(bboxes)
@@ -164,7 +168,7 @@ class Validation:
       * recall is float32 (target_num is a float32 tensor), precision a Python float; equal consecutive recalls keep the
         larger precision; AP = sum over the P-R points of (recall step) x (max precision from that point on) (:87-119).
     `dataset` is anything a DataLoader accepts; items are ((h,w,c) image, (64,6) boxes) like DetectDataset's, batched with
-    `collate_fn` above (images / 255)."""
+    `collate_fn` above (images / 255) -- dataset.DetectDataset(..., val=True, augment=False) itself, batch by batch on the GPU."""
 
     def __init__(self, params, logger, dataset, device, model_loss):
         from torch.utils.data import DataLoader
