@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric on BASELINE.json's config.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps, --dump-outputs / --dump-records if given,
+and ONE JSON line (metric, value, unit, ms_per_step, the configuration).  --full adds everything else, measured in the same process
+after the headline and never `value`: the counter passes before it, the per-launch times and the roofline, the other scheduling mode,
+the f16x3 variant, the other BASELINE configurations, the extra records, the training iteration and the CPU baseline (each of them can
+be left out again with its --no-* option).
 
 N = 1 runs in this process.  N > 1 and no WORLD_SIZE in the environment: this process starts
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py <same args>
@@ -14,14 +20,15 @@ boxes when N > 1]) over one batch of synthetic frames that is already resident i
 engine, so a batch's late per-frame stages run beside the next batch's early machine-filling ones.  Which two streams is decided by
 an untimed measurement before the warm-up (BatchPipeline.tune_streams: the overlap of two streams depends on the hardware queues the
 runtime happened to give them -- 253-261 k frames/s on an unlucky pair, 291-295 k on the others).
-All K steps (and exchanges) complete inside the timed region, `ms_per_step` is elapsed / K.  The one-step-at-a-time figure (two half-batch
-lanes) is reported beside it (`one_batch_in_flight`), as are the per-pass model / post-process times (`forward_chain.forward_ms`, `post_ms`).
+All K steps (and exchanges) complete inside the timed region, `ms_per_step` is elapsed / K.  With --full, the one-step-at-a-time figure
+(two half-batch lanes) is reported beside it (`one_batch_in_flight`), as are the per-pass model / post-process times
+(`forward_chain.forward_ms`, `post_ms`).
 Workload at N = 1: BASELINE.json configs[1], "YOLO-Fastest 320x256 batch=256 fp32, synthetic frames"
 (u8 ~ Uniform{0..255} i.i.d., x = (u8-128)/255, seed = rank).  N > 1: the same per GPU (weak
 scaling, frames are independent units; one RCCL all-gather of the fixed-capacity box records).
 Rank 0 prints ONE JSON line.
 
-The `roofline` object is the PHYSICAL roof of the dominant launch (README "Reading the bench line"):
+The `roofline` object (--full) is the PHYSICAL roof of the dominant launch (README "Reading the bench line"):
   * the launch's flops, split by the pipe they run on in the plan (matrix cores / vector ALU, yf_op_info_ex), over its
     average duration (HIP events on the launch stream), against the dense peak of that pipe and type;
   * its HBM bytes from the PMC counters (profiles/pmc_traffic.json, taken with tools/refresh_profiles.sh at the source hash
@@ -186,7 +193,7 @@ def live_pmc(res, batch, dtype, frames, kmax, with_issue=False):
         for pi, counters in enumerate(passes):
             d = os.path.join(work, "p%d" % pi)
             cmd = [prof, "--pmc"] + list(counters) + ["--kernel-trace", "-d", d, "-o", "p", "--output-format", "csv", "--", sys.executable,
-                   os.path.abspath(__file__), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-variants", "--no-configs",
+                   os.path.abspath(__file__), "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-variants", "--no-configs",
                    "--no-live-traffic", "--no-train", "--no-extras", "--in-flight", "1", "--lanes", "1", "--res", str(res), "--batch", str(batch),
                    "--dtype", dtype, "--frames", frames, "--kmax", str(kmax), "--launch-repeats", "1", "--dump-ops", os.path.join(work, "ops.json")]
             rc, tail = _run_child(cmd, 120)
@@ -511,9 +518,12 @@ def main():
                          "never a performance figure: the line says so (`rehearsal`)")
     ap.add_argument("--pin-cpus", type=int, nargs=2, default=None, metavar=("RANK", "OF"),
                     help="rehearse the multi-GPU CPU pinning on one GPU: pin this process like local rank RANK of OF ranks")
-    ap.add_argument("--regions", type=int, default=5,
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline as well (module docstring); a plain run times the headline alone")
+    ap.add_argument("--regions", type=int, default=0,
                     help="timed regions of --steps steps each, run back to back in the same loop after ONE warm-up: `value` is the first "
-                         "(the contract's K steps), `repeat_values` lists them all (the box-to-box and run-to-run spread in the record)")
+                         "(the contract's K steps), `repeat_values` lists them all (the box-to-box and run-to-run spread in the record); "
+                         "0 (default) = 5 with --full, else 1")
     ap.add_argument("--headline-only", action="store_true",
                     help="stop after the headline's timed regions and print a short line (kernel traces of exactly the headline loop: tools/refresh_profiles.sh)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -529,7 +539,7 @@ def main():
     ap.add_argument("--launch-repeats", type=int, default=4,
                     help="per-launch timing (forward_chain.per_launch, roofline.launch_ms): back-to-back launches of each kernel between the two "
                          "HIP events that time it; 1 = one launch per event pair (the counter passes, which match dispatches to ops by order, use 1)")
-    ap.add_argument("--dump-ops", default=None, help="write the launch names of one forward pass to this JSON file")
+    ap.add_argument("--dump-ops", default=None, help="write the launch names of one forward pass to this JSON file (needs --full)")
     ap.add_argument("--dump-records", default=None,
                     help="rank 0 writes the LAST step's detection records of all frames (N > 1: as gathered over RCCL) to this .npz")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
@@ -541,6 +551,11 @@ def main():
         raise SystemExit("--gpus must be >= 1")
     if args.steps < 1:
         raise SystemExit("--steps must be >= 1")
+    if args.dump_ops and not args.full:
+        raise SystemExit("--dump-ops needs --full (the launch list comes from the per-launch timing)")
+    if not args.full:      # a plain run: nothing but the headline
+        args.no_cpu_baseline = args.no_variants = args.no_live_traffic = args.no_train = args.no_configs = args.no_extras = True
+    args.regions = args.regions or (5 if args.full else 1)
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
@@ -762,12 +777,48 @@ def main():
         rec = cur.get("gathered") if multi else raw
         dump_outputs(args.dump_outputs, dict({k: rec[k].cpu().numpy() for k in REC},
                                              **{k: raw[k].cpu().numpy() for k in ("head_large", "head_small")}))
+    if rank == 0 and args.dump_records:
+        torch.cuda.synchronize(dev)
+        rec = cur.get("gathered") if multi else raw
+        np.savez(args.dump_records, world_size=world, **{k: rec[k].cpu().numpy() for k in REC})
     if args.headline_only:
         if rank == 0:
             print(json.dumps({"metric": "frames/sec end-to-end (headline loop only)", "value": round(n_total * args.steps / elapsed, 1), "unit": "frames/s",
                               "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 4),
                               "repeat_values": [round(n_total * args.steps / t, 1) for t in region_s], "dtype": args.dtype, "in_flight": in_flight,
                               "source_hash": source_hash()}))
+        if multi:
+            dist.destroy_process_group()
+        return
+
+    def headline_line():
+        """The headline's keys of the JSON line; --full adds its other records to them."""
+        counts = raw["counts"].cpu().numpy()
+        fps = n_total * args.steps / elapsed
+        return {
+            "metric": "frames/sec end-to-end (model forward + decode + per-class NMS), 320x256 batch=256 per GPU"
+                      if args.res == 256 else "frames/sec end-to-end, 640x512",
+            "value": round(fps, 1), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(1e3 * elapsed / args.steps, 4), "ms_per_frame": round(1e3 * elapsed / args.steps / n_total, 6),
+            # `value` is region 0; the same K-step region repeated in the same loop (no re-warm-up, same streams): the spread of the headline
+            "repeat_values": [round(n_total * args.steps / t, 1) for t in region_s],
+            "settle_steps": args.settle, "warmup_effective": args.warmup + args.settle,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype,
+            "data": "synthetic" if args.frames == "noise" else "the reference's 20 bundled frames tiled to the batch",
+            "config": {"workload": f"YOLO-Fastest {W}x{H} batch={args.batch} fp32 per GPU, synthetic uniform-u8 frames "
+                                   f"(BASELINE.json configs[1])" if args.res == 256 and args.batch == 256 and args.dtype == "f32" and args.frames == "noise" else
+                                   f"YOLO-Fastest {W}x{H} batch={args.batch} {args.dtype} per GPU, {args.frames} frames"
+                                   + (", dense synthetic head logits (SURVEY.md 8(d) config 5)" if args.dense else ""),
+                       "global_batch": n_total, "weights": wname, "kmax": args.kmax, "chunk": args.chunk, "in_flight": in_flight, "lanes": lanes, "branches": branches,
+                       "world_size": world, "cpu_affinity": affinity,
+                       "parallelism": (f"dp{world} REHEARSAL: {world} ranks share ONE GPU, records exchanged over gloo -- not a performance figure" if args.share_gpu and world > 1
+                                       else f"dp{world} (frames sharded, one RCCL all-gather of box records)" if world > 1 else "single GPU"),
+                       "survivors_per_frame_mean": round(float(np.clip(counts, 0, None).mean()), 3)},
+        }
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline_line()))
         if multi:
             dist.destroy_process_group()
         return
@@ -1065,14 +1116,7 @@ def main():
             del mc, pc
         cur.clear(); cur.update(saved)
 
-    if rank == 0 and args.dump_records:
-        torch.cuda.synchronize(dev)
-        rec = cur.get("gathered") if multi else raw
-        np.savez(args.dump_records, world_size=world, **{k: rec[k].cpu().numpy() for k in REC})
-
     if rank == 0:
-        counts = raw["counts"].cpu().numpy()
-        fps = n_total * args.steps / elapsed
         # per-launch timing, HIP events on the launch stream around every kernel of one forward pass (mean of 5 passes).  An event pair
         # around ONE launch also times the event packets and the dispatch gap behind them -- 5-7 us per launch on some hosts, which is why
         # rocprofv3's kernel durations of the same pass are shorter (profiles/r04_lanes1_kernel_stats.csv: 936 us against 1067 us over the
@@ -1156,25 +1200,8 @@ def main():
             roofline["traffic_note"] = traffic_note
         if traffic_source:
             roofline["traffic_source"] = traffic_source
-        out = {
-            "metric": "frames/sec end-to-end (model forward + decode + per-class NMS), 320x256 batch=256 per GPU"
-                      if args.res == 256 else "frames/sec end-to-end, 640x512",
-            "value": round(fps, 1), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(1e3 * elapsed / args.steps, 4), "ms_per_frame": round(1e3 * elapsed / args.steps / n_total, 6),
-            # `value` is region 0; the same K-step region repeated in the same loop (no re-warm-up, same streams): the spread of the headline
-            "repeat_values": [round(n_total * args.steps / t, 1) for t in region_s],
-            "settle_steps": args.settle, "warmup_effective": args.warmup + args.settle,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype,
-            "data": "synthetic" if args.frames == "noise" else "the reference's 20 bundled frames tiled to the batch",
-            "config": {"workload": f"YOLO-Fastest {W}x{H} batch={args.batch} fp32 per GPU, synthetic uniform-u8 frames "
-                                   f"(BASELINE.json configs[1])" if args.res == 256 and args.batch == 256 and args.dtype == "f32" and args.frames == "noise" else
-                                   f"YOLO-Fastest {W}x{H} batch={args.batch} {args.dtype} per GPU, {args.frames} frames"
-                                   + (", dense synthetic head logits (SURVEY.md 8(d) config 5)" if args.dense else ""),
-                       "global_batch": n_total, "weights": wname, "kmax": args.kmax, "chunk": args.chunk, "in_flight": in_flight, "lanes": lanes, "branches": branches,
-                       "world_size": world, "cpu_affinity": affinity,
-                       "parallelism": (f"dp{world} REHEARSAL: {world} ranks share ONE GPU, records exchanged over gloo -- not a performance figure" if args.share_gpu and world > 1
-                                       else f"dp{world} (frames sharded, one RCCL all-gather of box records)" if world > 1 else "single GPU"),
-                       "survivors_per_frame_mean": round(float(np.clip(counts, 0, None).mean()), 3)},
+        out = headline_line()
+        out.update({
             "roofline": roofline,
             # the whole forward pass (all launches)
             "forward_chain": {"launches": len(ops), "forward_ms": round(fwd_ms, 4), "post_ms": round(post_ms, 4),
@@ -1199,7 +1226,7 @@ def main():
                                                                                                   o["roof"]["counters"]["mfma_frac"],
                                                                                                   o["roof"]["counters"]["parked_frac"]]}
                                              for o in ops]},
-        }
+        })
         if single is not None:
             out["one_batch_in_flight"] = single
         if other is not None:

@@ -275,6 +275,13 @@ def test_bench_gpus_n_never_degrades_silently():
     assert r.returncode != 0 and '"n_gpus"' not in r.stdout
 
 
+def test_bench_dump_ops_needs_full():
+    """The launch list of --dump-ops comes from the per-launch timing, which only a --full run does: a plain run asking for it is
+    refused before it touches the GPU instead of finishing without the file."""
+    r = _run_bench(["--gpus", "1", "--steps", "1", "--warmup", "0", "--dump-ops", os.devnull])
+    assert r.returncode != 0 and "--dump-ops needs --full" in r.stderr and '"n_gpus"' not in r.stdout, (r.returncode, r.stderr[-300:])
+
+
 def test_bench_roofline_arithmetic():
     """The physical-roof arithmetic of bench.launch_roofline: fp32 prices all flops against the shared 157.3 TF issue rate, fp16
     prices MFMA flops against the fp16 MFMA peak (never against the fp32 peak: no fraction above 1 from a unit mix-up), and a

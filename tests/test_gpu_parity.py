@@ -1371,16 +1371,25 @@ def test_batch_pipeline_is_identical(yf, golden, dev, depth):
 
 
 def test_bench_line_and_multi_gpu_rehearsal(dev):
-    """bench.py end to end on the one GPU of the box: the default line (two batches in flight) carries the contract's keys, and
+    """bench.py end to end on the one GPU of the box: the --full line (two batches in flight) carries the contract's keys, and
     `--exchange-at-1` runs the N > 1 code path -- RCCL process group, the all-gather of every step's records started from inside each
-    batch's stream context, barrier + max-over-ranks timing -- with a 1-rank group."""
+    batch's stream context, barrier + max-over-ranks timing -- with a 1-rank group.  A plain run prints the headline's keys alone."""
     import json
     import subprocess
     import sys
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--batch", "64"]
+    plain = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--batch", "64"]
+    r = subprocess.run(plain, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    j = json.loads(r.stdout.strip().splitlines()[-1])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+              "data", "config"):
+        assert k in j, k
+    assert j["steps"] == 4 and j["value"] > 1000 and len(j["repeat_values"]) == 1 and j["config"]["in_flight"] == 2
+    assert not {"roofline", "forward_chain", "one_batch_in_flight", "variants", "configs", "training", "cpu_baseline"} & set(j)
+    base = plain + ["--full", "--no-cpu-baseline"]
     for extra in ([], ["--exchange-at-1", "--no-variants", "--no-configs", "--no-train"],
                   ["--exchange-at-1", "--no-variants", "--no-configs", "--no-train", "--in-flight", "1"]):
         r = subprocess.run(base + extra, env=env, capture_output=True, text=True, timeout=600)

@@ -7,15 +7,16 @@ LIBS=(); FILTER=""
 while [ $# -gt 0 ]; do if [ "$1" = "--" ]; then FILTER=$2; break; fi; LIBS+=($1); shift; done
 LIB=yolo-fastest-and-embedded-deployment_amd/libyolo_fastest_hip.so
 cp $LIB /tmp/orig.so
+T=$(mktemp -d)
 for r in $(seq $R); do for i in "${!LIBS[@]}"; do
   cp ${LIBS[$i]} $LIB
-  python bench.py --in-flight 1 --lanes 1 --no-cpu-baseline --no-variants --no-configs --no-train --no-live-traffic --no-extras $OPS_ARGS --steps 20 --dump-ops gpurun_out/ops_${i}_$r.json > /dev/null 2>&1
+  python bench.py --full --in-flight 1 --lanes 1 --no-cpu-baseline --no-variants --no-configs --no-train --no-live-traffic --no-extras $OPS_ARGS --steps 20 --dump-ops $T/ops_${i}_$r.json > /dev/null 2>&1
 done; done
 cp /tmp/orig.so $LIB
-python - "$R" "$FILTER" "${LIBS[@]}" <<'PY'
+python - "$T" "$R" "$FILTER" "${LIBS[@]}" <<'PY'
 import json, sys
-R, flt, libs = int(sys.argv[1]), sys.argv[2], sys.argv[3:]
-runs = [[json.load(open(f"gpurun_out/ops_{i}_{r}.json")) for r in range(1, R + 1)] for i in range(len(libs))]
+T, R, flt, libs = sys.argv[1], int(sys.argv[2]), sys.argv[3], sys.argv[4:]
+runs = [[json.load(open(f"{T}/ops_{i}_{r}.json")) for r in range(1, R + 1)] for i in range(len(libs))]
 print(" " * 40 + " ".join(f"{l.split('/')[-1][:14]:>14s}" for l in libs))
 for k, o in enumerate(runs[0][0]):
     if flt and flt not in o["name"]:
