@@ -760,79 +760,46 @@ def test_fp16_storage_variant_is_nonconforming_but_detects_identically(yf, golde
     assert np.abs(hh[0].float().cpu().numpy() - g["head_large"][:2]).max() < 1.5
 
 
-def test_fp16_storage_both_forms_of_the_stride2_block(yf, golden, dev, tmp_path):
+def _frames_and_noise(yf, res, dev, **attrs):
+    """Heads of the bundled frames and of a 192 x 224 noise batch, from a model with the given attributes (storage_dtype, precision)."""
+    m = yf.YoloFastest(yf.io_params_for(res)).to(dev).eval()
+    m.load_state_dict(torch.load(WEIGHTS[res], map_location=dev))
+    for k, v in attrs.items():
+        setattr(m, k, v)
+    g = np.load(os.path.join(ROOT, "tests", "golden", f"golden_{res}.npz"))
+    x = torch.from_numpy(((g["input_u8"].astype(np.float32) - 128.0) / 255.0)[:, None]).to(dev)
+    torch.manual_seed(11)
+    y = torch.rand(3, 1, 192, 224, device=dev) - 0.5
+    with torch.no_grad():
+        a = m(x)
+        b = m(y)
+    return {"hl": a[0].cpu().numpy(), "hs": a[1].cpu().numpy(), "nl": b[0].cpu().numpy(), "ns": b[1].cpu().numpy()}
+
+
+def test_fp16_storage_stride2_block(yf, golden, dev):
     """The fp16-storage plan runs conv1_8 + conv1_9 + conv2_1 as k19h_kernel (no region buffers, conv1_8 per tap on 4x4x4 fp16 MFMAs with its
-    weights rounded to fp16); YF_K19R=0 selects k19m_kernel<half_t> (rounds 2-4: conv1_8 on exact fp32 MFMAs, once per input pixel).
-    Both in child processes (the switch is read once per process) on the bundled frames and on a 192 x 224 noise batch: each stays inside the
-    fp16-storage bounds, and on the frames they differ from each other by no more than fp16 storage may cost against fp32."""
-    import subprocess
-    import sys
-    code = ("import sys, torch, numpy as np; sys.path.insert(0, %r)\n"
-            "import yolo_fastest_amd as yf\n"
-            "dev = torch.device('cuda:0'); io = yf.io_params_for(256)\n"
-            "m = yf.YoloFastest(io).to(dev).eval(); m.load_state_dict(torch.load(%r, map_location=dev)); m.storage_dtype = torch.float16\n"
-            "g = np.load(%r); x = torch.from_numpy(((g['input_u8'].astype(np.float32) - 128.0) / 255.0)[:, None]).to(dev)\n"
-            "torch.manual_seed(11); y = torch.rand(3, 1, 192, 224, device=dev) - 0.5\n"
-            "with torch.no_grad(): a = m(x); b = m(y)\n"
-            "np.savez(sys.argv[1], hl=a[0].cpu().numpy(), hs=a[1].cpu().numpy(), nl=b[0].cpu().numpy(), ns=b[1].cpu().numpy())\n"
-            "print('RESULT ok')\n") % (ROOT, WEIGHTS[256], os.path.join(ROOT, "tests", "golden", "golden_256.npz"))
-    out = {}
-    for old in (False, True):
-        env = dict(os.environ)
-        env.pop("YF_K19R", None)
-        env.pop("YF_K19H_FORM", None)
-        if old:
-            env["YF_K19R"] = "0"
-        f = str(tmp_path / ("old.npz" if old else "new.npz"))
-        r = subprocess.run([sys.executable, "-c", code, f], env=env, capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0 and "RESULT ok" in r.stdout, r.stderr[-2000:]
-        out[old] = np.load(f)
+    weights rounded to fp16).  On the bundled frames it stays inside the fp16-storage bounds; on a 192 x 224 noise batch its heads are finite
+    and stay within 6e-3 of the largest logit of the fp32 engine's heads on the same batch."""
+    out = _frames_and_noise(yf, 256, dev, storage_dtype=torch.float16)
+    ref = _frames_and_noise(yf, 256, dev)
     g = golden("golden_256")
-    for k, ref in (("hl", g["head_large"]), ("hs", g["head_small"])):
-        for old in (False, True):
-            assert np.abs(out[old][k] - ref).max() <= FP16_STORAGE_MAX[256], (k, old)
-        # (two roundings of the same tensor differ by one fp16 ulp -- 1.6e-2 .. 3.1e-2 at the largest activations -- wherever a value sits at a tie)
-        assert np.abs(out[False][k] - out[True][k]).max() <= FP16_STORAGE_MAX[256], k
-    assert any(not np.array_equal(out[False][k], out[True][k]) for k in ("hl", "hs"))      # two different kernels did run
+    for k, want in (("hl", g["head_large"]), ("hs", g["head_small"])):
+        assert np.abs(out[k] - want).max() <= FP16_STORAGE_MAX[256], k
     for k in ("nl", "ns"):      # noise drives the logits far beyond the frames' (one fp16 ulp at 40 is 3e-2): relative to the largest logit
-        assert np.isfinite(out[False][k]).all() and np.abs(out[False][k] - out[True][k]).max() <= 6e-3 * np.abs(out[True][k]).max(), k
+        assert np.isfinite(out[k]).all() and np.abs(out[k] - ref[k]).max() <= 6e-3 * np.abs(ref[k]).max(), k
 
 
-def test_f16x3_both_forms_of_the_stride2_block(yf, golden, dev, tmp_path):
-    """Round 6: the split-operand (f16x3) plan runs conv1_8 + conv1_9 + conv2_1 as k19m_kernel<x3_t> (region buffers, split once per region pixel);
-    YF_K19X=43 selects k19x_kernel (no region buffers: conv1_8 exact fp32 per tap, ONE hi/lo split per tap in registers, six K = 32 fp16 MFMAs per
-    tap -- built for VERDICT r5 item 3, measured a tie, kept as the A/B form).  Both in child processes (the switch is read once per process) on the bundled frames, at 640x512 and on a 192 x 224 noise batch: each
-    stays inside the fp32 golden bounds (_check_heads: the bounds of the fp32 path, SURVEY's 2e-2 by a factor of 100), and they agree with each other
-    like two fp32 evaluations do."""
-    import subprocess
-    import sys
-    code = ("import sys, torch, numpy as np; sys.path.insert(0, %r)\n"
-            "import yolo_fastest_amd as yf\n"
-            "dev = torch.device('cuda:0'); res = int(sys.argv[2]); io = yf.io_params_for(res)\n"
-            "m = yf.YoloFastest(io).to(dev).eval(); m.load_state_dict(torch.load(sys.argv[3], map_location=dev)); m.precision = 'f16x3'\n"
-            "g = np.load(sys.argv[4]); x = torch.from_numpy(((g['input_u8'].astype(np.float32) - 128.0) / 255.0)[:, None]).to(dev)\n"
-            "torch.manual_seed(11); y = torch.rand(3, 1, 192, 224, device=dev) - 0.5\n"
-            "with torch.no_grad(): a = m(x); b = m(y)\n"
-            "np.savez(sys.argv[1], hl=a[0].cpu().numpy(), hs=a[1].cpu().numpy(), nl=b[0].cpu().numpy(), ns=b[1].cpu().numpy())\n"
-            "print('RESULT ok')\n") % ROOT
+def test_f16x3_stride2_block(yf, golden, dev):
+    """The split-operand (f16x3) plan runs conv1_8 + conv1_9 + conv2_1 as k19m_kernel<x3_t> (region buffers, split once per region pixel).  On
+    the bundled frames, at 256 and 512, it stays inside the fp32 golden bounds (_check_heads: the bounds of the fp32 path, SURVEY's 2e-2 by a
+    factor of 100); on them and on a 192 x 224 noise batch its heads are finite and agree with the fp32 engine's like two fp32 evaluations do."""
     for res in (256, 512):
-        out = {}
-        for old in (False, True):
-            env = dict(os.environ)
-            for k in ("YF_K19R", "YF_K19X"):
-                env.pop(k, None)
-            env["YF_K19X"] = "0" if old else "43"
-            f = str(tmp_path / ("old_%d.npz" % res if old else "new_%d.npz" % res))
-            r = subprocess.run([sys.executable, "-c", code, f, str(res), WEIGHTS[res], os.path.join(ROOT, "tests", "golden", f"golden_{res}.npz")],
-                               env=env, capture_output=True, text=True, timeout=600)
-            assert r.returncode == 0 and "RESULT ok" in r.stdout, r.stderr[-2000:]
-            out[old] = np.load(f)
+        out = _frames_and_noise(yf, res, dev, precision="f16x3")
+        ref = _frames_and_noise(yf, res, dev)
         g = golden(f"golden_{res}")
-        for old in (False, True):
-            _check_heads(out[old]["hl"], out[old]["hs"], g["head_large"], g["head_small"], g["head_large_f64"], g["head_small_f64"], res == 256)
-        assert any(not np.array_equal(out[False][k], out[True][k]) for k in ("hl", "hs"))      # two different kernels did run
+        _check_heads(out["hl"], out["hs"], g["head_large"], g["head_small"], g["head_large_f64"], g["head_small_f64"], res == 256)
         for k in ("hl", "hs", "nl", "ns"):
-            assert np.isfinite(out[False][k]).all() and np.abs(out[False][k] - out[True][k]).max() <= 2e-5 * max(1.0, np.abs(out[True][k]).max()), (res, k)
+            assert np.isfinite(out[k]).all() and np.abs(out[k] - ref[k]).max() <= 2e-5 * max(1.0, np.abs(ref[k]).max()), (res, k)
 
 
 def test_validation_get_map_end_to_end(yf, models, golden, dev):
@@ -975,7 +942,8 @@ def test_dense_post_process_per_class_workgroups_give_the_same_records(yf, model
     """the per-(frame, class) form of the post-process (post_split_kernel; chosen automatically at kmax >= 256) against the
     one-workgroup-per-frame form on the same logits: identical counts, boxes, classes, sources, scores -- on dense synthetic fields (SURVEY.md
     8(d).5's recipe), with a capacity overflow (the count stays the true number, the first kmax records are stored), with the packed record
-    block, inside yf_detect on two lanes (each lane's frames use their own scratch rows), and launched repeatedly (the ticket is reset)."""
+    block, inside yf_detect on two lanes (each lane's frames use their own scratch rows), and launched repeatedly (each launch is the
+    per-class kernel followed by the assembly kernel, which leaves nothing behind for the next)."""
     m, post, io = models[512]
     H, W = io["input_shape"][:2]
     hl, hs = [], []

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-kernel means of the counters in rocprofv3 counter_collection csv files (tools/pmc_kbench.sh)."""
+"""Per-kernel means of the counters in rocprofv3 counter_collection csv files (e.g. from tools/pmc_bench.sh)."""
 import csv, sys, collections
 for path in sys.argv[1:]:
     acc = collections.defaultdict(lambda: collections.defaultdict(list))

@@ -151,7 +151,8 @@ struct yf_engine {
     enum { CV_SLOTS = 32 };
     struct CvTab { int sh = 0, sw = 0; bool built = false; hipStream_t stream = nullptr; hipEvent_t ready = nullptr; long used = 0; } cvtab[CV_SLOTS];
     int4* d_cvpool = nullptr;
-    // post_split_kernel (dense frames: one workgroup per frame AND class): scratch rows + per-frame tickets, grown on demand
+    // post_split_kernel (dense frames: one workgroup per frame AND class) writes one scratch row per (frame, class), which post_assemble_kernel
+    // concatenates in a second launch; grown on demand
     int post_split = 0;               // yf_set_post_split: 0 = auto (K_max >= 256 and <= 8 classes), 1 = always, 2 = never
     int32_t* d_post_tmp = nullptr; size_t post_tmp_ints = 0;
     long cv_tick = 0;

@@ -17,34 +17,16 @@
 
 #include "yf_kernels.h"
 
-#ifndef YF_FB_DW_UNROLL
-#define YF_FB_DW_UNROLL 1
-#endif
-
 // Output pixels per thread (BH x BW) of the two stride-2 / stride-4 VALU blocks: these kernels are LATENCY-bound (47-55 % of their wave
 // time parked, profiles/r02_wave_time_breakdown.txt) and their residency is set by the E tile in LDS; 16x32-pixel tiles (1 x 2 per
 // thread, 20.7 KB, 7 workgroups per CU) beat 32x32 (2 x 2, 39 KB, 4 per CU) although the halo share of the expansion grows from 13
-// to 20 %: stem 70.9 -> 66.8 us, res2 blocks 58 -> 54 us (A/B, tools/ops_ab.sh).
-#ifndef YF_STEM_BH
-#define YF_STEM_BH 1
-#endif
-#ifndef YF_STEM_BW
-#define YF_STEM_BW 2
-#endif
-#ifndef YF_RES2_BH
-#define YF_RES2_BH 2   // res2: 32x16 tiles (2 x 1 per thread) are another 6 % faster than 16x32 (54 -> 50 us)
-#endif
-#ifndef YF_RES2_BW
-#define YF_RES2_BW 1
-#endif
-#ifndef YF_FB_MED3
-#define YF_FB_MED3 1
-#endif
-#ifndef YF_FB_PK
-#define YF_FB_PK 1   // expansion / projection / conv0 FMAs over output-channel PAIRS as v_pk_fma_f32 (scalar weight pair x broadcast value)
-#endif
+// to 20 %: stem 70.9 -> 66.8 us, res2 blocks 58 -> 54 us (A/B, tools/ops_ab.sh).  The stem uses 1 x 2; res2 uses 32x16 tiles (2 x 1 per
+// thread), another 6 % faster than 16x32 (54 -> 50 us).
+// Expansion / projection / conv0 FMAs run over output-channel PAIRS as v_pk_fma_f32 (scalar weight pair x broadcast value).
 
 namespace yf {
+
+constexpr int RES2_BH = 2, RES2_BW = 1;
 
 typedef float fb_f32x2 __attribute__((ext_vector_type(2)));
 typedef float __attribute__((address_space(4))) cfloat;               // constant address space: scalar (s_load) reads of uniform data
@@ -52,28 +34,6 @@ typedef fb_f32x2 __attribute__((address_space(4))) cfloat2;
 
 __device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
 
-
-// Diagnostic build only (-DYF_STAMP, tools/kbench.hip): per-phase shader-clock sums, written to a buffer nothing else reads.
-#ifndef YF_FB_HOIST
-#define YF_FB_HOIST 2   // >= 1: the res2 pair keeps its region's input channels in registers across the expansion chunks; 2: single-chunk
-#endif                  // blocks (res1_1) request all their items' inputs together as well (A/B: DESIGN.md section 4)
-#ifdef YF_STAMP
-__device__ __forceinline__ unsigned long long yf_stamp()
-{
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-#define YF_STAMP_DECL unsigned long long st_[6] = {0, 0, 0, 0, 0, 0}, st_t_ = yf_stamp();
-#define YF_STAMP_AT(i) { unsigned long long n_ = yf_stamp(); st_[i] += n_ - st_t_; st_t_ = n_; }
-#define YF_STAMP_FLUSH(dbg) if (dbg && (threadIdx.x & 63) == 0) { for (int i_ = 0; i_ < 6; ++i_) atomicAdd(&dbg[i_], st_[i_]); }
-#else
-#define YF_STAMP_DECL
-#define YF_STAMP_AT(i)
-#define YF_STAMP_FLUSH(dbg)
-#endif
 
 // Weight stream of one block (host-packed, fb_pack_weights): per EC-channel chunk, contiguous
 //   [W1 chunk CIN x EC | b1 EC | wd 9 x EC | bd EC | W2 chunk EC x COUT], then b2[COUT]
@@ -155,7 +115,7 @@ __global__ void __launch_bounds__(TYB* TXB) fused_block_kernel(FbArgs a)
     // (load, wait, 16 / 32 packed FMAs, next item).  With HOIST the wave's MAXI items are loaded ONCE, all requests in flight together,
     // before the chunk loop, and stay in registers (MAXI x CIN VGPRs).
     constexpr int MAXI = (NITEM + NW - 1) / NW;
-    constexpr bool HOIST = YF_FB_HOIST && !PRE && !XL && (CEXP / EC > 1 || YF_FB_HOIST > 1) && NCG == 1 && PE == 1 && MAXI * CIN <= 32;
+    constexpr bool HOIST = !PRE && !XL && NCG == 1 && PE == 1 && MAXI * CIN <= 32;
     float xh[HOIST ? MAXI : 1][CIN];
     int hdst[HOIST ? MAXI : 1];       // ... and so are the item's E offset (-1: no pixel) and its ReLU limit (+inf inside the image, 0 outside):
     float hlim[HOIST ? MAXI : 1];     // 13 of the 64 VALU instructions of an item and chunk were this index arithmetic
@@ -177,9 +137,7 @@ __global__ void __launch_bounds__(TYB* TXB) fused_block_kernel(FbArgs a)
         }
     }
 
-    YF_STAMP_DECL
     for (int ch = 0; ch < CEXP / EC; ++ch) {
-        YF_STAMP_AT(0)
         const cfloat* __restrict__ wc = (const cfloat*)(a.wp + ch * CHF);  // this chunk's weights (wave-uniform, constant address space -> scalar loads)
         // ---------------- expansion of the halo'd region into LDS: PE pixels per lane per item ----------------
 #pragma unroll
@@ -271,7 +229,6 @@ __global__ void __launch_bounds__(TYB* TXB) fused_block_kernel(FbArgs a)
                                 for (int ci = 0; ci < C0; ++ci) v[(ky * 3 + kx) * C0 + ci] = ok ? src[ci * plane + (long)yy * (2 * a.W) + xx] : 0.f;
                             }
                     }
-#if YF_FB_PK
 #pragma unroll
                     for (int c = 0; c < CIN; c += 2) {
                         fb_f32x2 s2 = *(const cfloat2*)(const cfloat*)(a.b0 + c);
@@ -280,15 +237,6 @@ __global__ void __launch_bounds__(TYB* TXB) fused_block_kernel(FbArgs a)
                             s2 = __builtin_elementwise_fma(fb_f32x2{v[t], v[t]}, *(const cfloat2*)(const cfloat*)(a.w0 + t * CIN + c), s2);
                         x[p][c] = fmaxf(s2[0], 0.f); x[p][c + 1] = fmaxf(s2[1], 0.f);
                     }
-#else
-#pragma unroll
-                    for (int c = 0; c < CIN; ++c) {
-                        float s = a.b0[c];
-#pragma unroll
-                        for (int t = 0; t < 9 * C0; ++t) s = fmaf(v[t], a.w0[t * CIN + c], s);
-                        x[p][c] = fmaxf(s, 0.f);
-                    }
-#endif
                 } else if constexpr (XL) {
 #pragma unroll
                     for (int k = 0; k < CIN; k += 4) {
@@ -308,7 +256,6 @@ __global__ void __launch_bounds__(TYB* TXB) fused_block_kernel(FbArgs a)
                 }
             }
             float e[PE][CG];
-#if YF_FB_PK
             static_assert(CG % 2 == 0 && EC % 2 == 0, "channel pairs");
             fb_f32x2 e2[PE][CG / 2];
 #pragma unroll
@@ -329,22 +276,6 @@ __global__ void __launch_bounds__(TYB* TXB) fused_block_kernel(FbArgs a)
             for (int p = 0; p < PE; ++p)
 #pragma unroll
                 for (int j = 0; j < CG; ++j) e[p][j] = e2[p][j / 2][j & 1];
-#else
-#pragma unroll
-            for (int j = 0; j < CG; ++j) {
-                const float bv = wc[O_B1 + cg * CG + j];
-#pragma unroll
-                for (int p = 0; p < PE; ++p) e[p][j] = bv;
-            }
-#pragma unroll
-            for (int k = 0; k < CIN; ++k)
-#pragma unroll
-                for (int j = 0; j < CG; ++j) {
-                    const float wv = wc[k * EC + cg * CG + j];
-#pragma unroll
-                    for (int p = 0; p < PE; ++p) e[p][j] = fmaf(x[p][k], wv, e[p][j]);
-                }
-#endif
             // E holds channel PAIRS interleaved: [EC/2][RH][RWP][2] -- one 8-byte write per pair here, and the depthwise below runs
             // its taps on both channels of a pair with one v_pk_fma_f32
 #pragma unroll
@@ -358,18 +289,16 @@ __global__ void __launch_bounds__(TYB* TXB) fused_block_kernel(FbArgs a)
 #pragma unroll
                     for (int j = 0; j < CG; j += 2)
                         *reinterpret_cast<float2*>(dst + j * PLANE) =
-                            (YF_FB_MED3 && !PRE) ? make_float2(__builtin_amdgcn_fmed3f(e[p][j], 0.f, lim), __builtin_amdgcn_fmed3f(e[p][j + 1], 0.f, lim))
+                            !PRE ? make_float2(__builtin_amdgcn_fmed3f(e[p][j], 0.f, lim), __builtin_amdgcn_fmed3f(e[p][j + 1], 0.f, lim))
                                        : make_float2(inimg[p] ? fmaxf(e[p][j], 0.f) : 0.f, inimg[p] ? fmaxf(e[p][j + 1], 0.f) : 0.f);
                 }
         }
-        YF_STAMP_AT(1)
         __syncthreads();
-        YF_STAMP_AT(2)
         // ---------------- depthwise 3x3 from LDS + projection into registers ----------------
         // NOT fully unrolled: unrolled, the scalar loads of all EC channels' weights are hoisted to the top and, with the
         // expansion's, exceed the SGPR file -- the compiler then spills SGPRs to VGPR lanes and 30-50 % of the VALU
         // instructions of the stride-2 kernels were v_readlane / v_writelane (tools/isa_stats.py)
-#pragma unroll YF_FB_DW_UNROLL
+#pragma unroll 1
         for (int c = 0; c < EC; c += 2) {
             const float* Ec = E + c * PLANE + ((tyb * BH * S) * RWP + txb * BW * S) * 2;
             fb_f32x2 win[WR][WC];   // (channel c, channel c + 1) of every window pixel
@@ -410,9 +339,7 @@ __global__ void __launch_bounds__(TYB* TXB) fused_block_kernel(FbArgs a)
                     }
                 }
         }
-        YF_STAMP_AT(3)
         __syncthreads();
-        YF_STAMP_AT(4)
     }
     // ---------------- epilogue: bias (+ residual) (+ ReLU), NHWC store ----------------
     const cfloat* __restrict__ b2 = (const cfloat*)(a.wp + (CEXP / EC) * CHF);
@@ -439,19 +366,17 @@ __global__ void __launch_bounds__(TYB* TXB) fused_block_kernel(FbArgs a)
                 st4<T>(o + co, v);
             }
         }
-    YF_STAMP_AT(5)
-    YF_STAMP_FLUSH(a.dbg)
 }
 
 // ------------------------------------------------------------------------------------------------
 // conv1_8 (pw 4->24, ReLU) -> conv1_9 (dense 3x3 stride 2 pad 1, 24->24, ReLU) -> conv2_1 (pw 24->8, linear)
 //   tile: 16x16 output pixels (stride-4 resolution), 256 threads, one output pixel per thread.
-//   Measured alternatives that did NOT help (tools/kbench.hip, profiles/): two pixels per lane (each scalar weight feeding
+//   Measured alternatives that did NOT help (stand-alone kernel benchmark, profiles/): two pixels per lane (each scalar weight feeding
 //   two FMAs) and v_pk_fma_f32 over pixel pairs or output-channel pairs all land at the same ~250 us / 30 TMAC/s although the
 //   packed forms halve the VALU instruction count -- the kernel is not VALU-issue-bound (fully unrolled straight-line code,
 //   instruction fetch is the suspect).  Later finding (tools/isa_mix.py): this fully unrolled form also spills ~900 SGPR values to
 //   VGPR lanes (v_readlane / v_writelane are a third of its VALU instructions).  Superseded by k19m_kernel (yf_k19_kernels.hip);
-//   kept as the VALU reference point of tools/kbench.hip.
+//   kept as the VALU reference point.
 //   conv1_8's output over the (33x33) halo'd region goes to LDS in two halves of 12 channels, split into
 //   even-column and odd-column planes ("space to depth") so that lanes on consecutive output columns read
 //   consecutive 48-B pixel records: conflict-free ds_read_b128.
@@ -558,10 +483,10 @@ static int launch_fb_t(FbArgs a, int N, hipStream_t s)
 //     cin cexp cout S  res    relu   pre    TYB TXB BH BW EC CG PE XL      (XL: stage the input tile in LDS -- measured
 //     slower at these shapes: it costs occupancy and LDS bandwidth, the L2-served loads were already hidden)
 #define YF_FB_SHAPES(FB)                                                                                                 \
-    FB(8, 8, 4, 1, false, false, true, 16, 16, YF_STEM_BH, YF_STEM_BW, 8, 8, 1, false)     /* conv0 + conv1_2/1_3/1_4      @ H/2  */          \
+    FB(8, 8, 4, 1, false, false, true, 16, 16, 1, 2, 8, 8, 1, false)     /* conv0 + conv1_2/1_3/1_4      @ H/2  */          \
     FB(8, 8, 4, 1, false, false, false, 16, 16, 1, 2, 8, 8, 1, false)    /* conv1_2/1_3/1_4 behind a separate conv0 (input_channel > 4) */ \
     FB(4, 8, 4, 1, true, false, false, 16, 16, 1, 2, 8, 8, 1, false)     /* res1_1                        @ H/2  */          \
-    FB(8, 32, 8, 1, true, false, false, 16, 16, YF_RES2_BH, YF_RES2_BW, 8, 8, 1, false)    /* res2_1, res2_2                @ H/4  */          \
+    FB(8, 32, 8, 1, true, false, false, 16, 16, RES2_BH, RES2_BW, 8, 8, 1, false)          /* res2_1, res2_2                @ H/4  */          \
     FB(8, 32, 8, 2, false, false, false, 16, 20, 1, 1, 8, 8, 1, false)   /* conv2_2/2_3/3_1               H/4 -> H/8 */      \
     FB(8, 48, 8, 1, true, false, false, 16, 20, 1, 2, 8, 8, 2, false)    /* res3_1, res3_2                @ H/8  */          \
     FB(8, 48, 16, 1, false, false, false, 16, 20, 1, 2, 8, 8, 2, false)  /* conv3_2/3_3/3_4 (fallback)    @ H/8  */          \
@@ -578,8 +503,8 @@ int launch_fused_block(int cin, int cexp, int cout, int stride, bool res, bool r
         if (!(cin == 8 && cexp == 8 && cout == 4 && stride == 1 && !res && !relu_out)) return -1;
 #define YF_STEM_C0(C0_)                                                                                                                            \
         if (pre_c0 == C0_)                                                                                                                          \
-            return dtype == DT_F16 ? launch_fb_t<8, 8, 4, 1, false, false, true, 16, 16, YF_STEM_BH, YF_STEM_BW, 8, 8, 1, false, half_t, C0_>(a, N, s) \
-                                   : launch_fb_t<8, 8, 4, 1, false, false, true, 16, 16, YF_STEM_BH, YF_STEM_BW, 8, 8, 1, false, float, C0_>(a, N, s);
+            return dtype == DT_F16 ? launch_fb_t<8, 8, 4, 1, false, false, true, 16, 16, 1, 2, 8, 8, 1, false, half_t, C0_>(a, N, s) \
+                                   : launch_fb_t<8, 8, 4, 1, false, false, true, 16, 16, 1, 2, 8, 8, 1, false, float, C0_>(a, N, s);
         YF_STEM_C0(2) YF_STEM_C0(3) YF_STEM_C0(4)
 #undef YF_STEM_C0
         return -1;
@@ -588,9 +513,8 @@ int launch_fused_block(int cin, int cexp, int cout, int stride, bool res, bool r
     // larger tiling would leave more than half of the CUs idle -- one output pixel per lane instead of two; a pixel's arithmetic is the same.
     if (cin == 8 && cexp == 32 && cout == 8 && stride == 1 && res && !relu_out && !pre) {
         const int n_cu = device_cu_count(current_device());
-        const long big = (long)N * ((a.Ho + 16 * YF_RES2_BH - 1) / (16 * YF_RES2_BH)) * ((a.Wo + 16 * YF_RES2_BW - 1) / (16 * YF_RES2_BW));
-        static const bool off = getenv("YF_MRES_SMALL_OFF") != nullptr;
-        if (!off && n_cu > 0 && 2 * big <= n_cu)
+        const long big = (long)N * ((a.Ho + 16 * RES2_BH - 1) / (16 * RES2_BH)) * ((a.Wo + 16 * RES2_BW - 1) / (16 * RES2_BW));
+        if (n_cu > 0 && 2 * big <= n_cu)
             return dtype == DT_F16 ? launch_fb_t<8, 32, 8, 1, true, false, false, 16, 16, 1, 1, 8, 8, 1, false, half_t>(a, N, s)
                                    : launch_fb_t<8, 32, 8, 1, true, false, false, 16, 16, 1, 1, 8, 8, 1, false, float>(a, N, s);
     }

@@ -1,5 +1,6 @@
 // yf_k19_kernels.hip -- conv1_8 (pw 4->24, ReLU) -> conv1_9 (dense 3x3 stride 2 pad 1, 24->24, ReLU) -> conv2_1 (pw 24->8,
-// linear) in one launch, the dense 3x3 on the matrix cores.            (reference: src/model_training/model/yolo_fastest.py:86-89)
+// linear) in one launch, the dense 3x3 on the matrix cores.  k19r_kernel (fp32) and k19h_kernel (fp16 storage) are the buffer-free forms
+// of today; the region-buffer scheme below is k19m_kernel, which serves the split-operand (DT_F16X3) engine.            (reference: src/model_training/model/yolo_fastest.py:86-89)
 //
 // conv1_9 is 22 % of the network's MACs: an implicit GEMM  D[cout][pixel] = sum_k W[cout][k] X[k][pixel]  with k = (tap, cin),
 // K = 9 x 24 = 216.  The VALU version (k19_kernel, yf_fused_kernels.hip) runs at ~30 TMAC/s (250 us for 256 frames); this one
@@ -17,7 +18,7 @@
 //     are padding), 216 = 13.5 groups (the last half group has zero weights);
 //   * epilogue: the accumulator layout (lane: pixel p, channels 16 mt + 4 j + r) IS the B operand of conv2_1's GEMM with the
 //     k-order permuted on the host, so bias + ReLU + conv2_1 stay in registers; lanes j < 2 store 4 channels each.
-// Measured on the way (tools/kbench.hip k19, SQ counters): the fp32 MFMA floor of this shape is 128 us (SQ_VALU_MFMA_BUSY =
+// Measured on the way (a stand-alone kernel benchmark, SQ counters): the fp32 MFMA floor of this shape is 128 us (SQ_VALU_MFMA_BUSY =
 // 32.3 cycles per MFMA, 68 % busy); fp32 MFMAs and VALU instructions do not overlap (each VALU instruction adds its 4 cycles:
 // the fp32 matrix rate equals the packed fp32 vector rate), which is why phase 1 went from VALU (68 us) to MFMA and why its
 // loads carry no address arithmetic; two workgroups per CU with one buffer each run in lockstep and never overlap their
@@ -40,12 +41,9 @@ constexpr int RS = 24;                     // record stride in elements
 // plane / row strides in elements: padded so that BOTH the phase-2 reads (b128 / b64 lane groups, 64 banks) and the phase-1
 // writes (8- / 16-lane groups, 32 banks) are conflict-free -- unpadded, the writes are 2.3-way conflicted and the LDS write
 // path, not the VALU, is what phase 1 costs (measured: 47 us of 210)
-#ifndef YF_K19_HPAD
-#define YF_K19_HPAD 8
-#endif
 // (fp16 storage: multiples of 8 halves, the 16-byte pair records of the K = 32 MFMA fragments must stay 16-byte aligned)
-constexpr int plane_stride(bool h16) { return 17 * RS + (h16 ? YF_K19_HPAD : 4); }
-constexpr int row_stride(bool h16) { return 2 * plane_stride(h16) + (h16 ? YF_K19_HPAD : 4); }
+constexpr int plane_stride(bool h16) { return 17 * RS + (h16 ? 8 : 4); }
+constexpr int row_stride(bool h16) { return 2 * plane_stride(h16) + (h16 ? 8 : 4); }
 constexpr int NG = 14;                     // k groups
 constexpr int NU = 5;                      // px-tiles of phase 1 per wave (36 over 8 waves)
 constexpr int NCHUNK = 54;                 // 9 taps x 6 chunks of 4 channels
@@ -62,53 +60,25 @@ constexpr int NG2 = 7, NPAIR = 27;
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 }  // namespace
 
-#ifndef YF_K19_Q4
-#define YF_K19_Q4 1
-#endif
-#ifndef YF_K19R_DBG
-#define YF_K19R_DBG 0   // timing builds only (tools/build_variant.sh): 1 = no 4x4x1 MFMAs, 4 = no 16x16x4 k-steps of conv1_9
-#endif
-#ifndef YF_K19R_PIPE
-#define YF_K19R_PIPE 2   // k19r_kernel: the next tap's conv1_8 is issued in front of the current tap's k-steps (0: behind them; 2: in front, no scheduling barrier per tap)
-#endif
-#ifndef YF_K19_PF
-#define YF_K19_PF 1   // how many k groups ahead phase 2's LDS operands are requested
-#endif
-// Q4 (fp32): output channels 16..23 of conv1_9 do not ride in a second 16-row M-tile (half of whose rows are padding: 25 % of all
-// MFMA cycles) but in 4x4 blocks: v_mfma_f32_4x4x1_16B_f32 is 16 independent 4x4 outer products, block b = lanes 4b..4b+3, and
-// with lane = (pixel p, chunk j) block (j, p >> 2) multiplies 4 channels x the 4 pixels of its lanes at the k-value THAT lane
-// group holds anyway (the same B register as the 16x16x4 k-step).  Each lane group accumulates its own k-values, so the four
-// partial sums are added across lane groups once per tile (ds_bpermute), and conv2_1 takes channel 16 + 4 t + j from lane group
-// j.  Measured (tools/mfma4_probe.hip): a wave issues one 4x4x1 per 12 cycles and two waves of a SIMD do not slow each other,
-// against 32 cycles of pipe per 16x16x4.
-// DBG (tools/kbench.hip only): 1 = skip phase 1, 2 = skip phase 2's MFMAs
-template <typename TT, int DBG = 0>
 __global__ void __launch_bounds__(512) k19m_kernel(K19Args a)
 {
-    // X3 (DT_F16X3): fp32 in HBM; conv1_8 (K = 4) stays an exact fp32 MFMA; its result is SPLIT ONCE, where phase 1 stores it: a
-    // region record of 4 channels is 16 bytes either way -- four floats (fp32 mode) or [hi f16x4 | lo f16x4] -- so phase 2 reads
+    // DT_F16X3: fp32 in HBM; conv1_8 (K = 4) stays an exact fp32 MFMA; its result is SPLIT ONCE, where phase 1 stores it: a
+    // region record of 4 channels is 16 bytes, [hi f16x4 | lo f16x4], so phase 2 reads
     // both halves of its B operand with plain ds_read_b128s and spends no VALU on splitting; conv1_9's weights are register-resident
     // as hi and lo fragments (2 x 56 VGPRs) and a k group (32 k-values, v_mfma_f32_16x16x32_f16) issues w_lo*x_hi + w_hi*x_lo + w_hi*x_hi.
-    constexpr bool X3 = is_x3<TT>::value;
-    constexpr bool H16 = sizeof(TT) == 2;
-    constexpr bool M16 = H16 || X3;                // conv1_9 / conv2_1 on the fp16 matrix pipe
-    constexpr int PS = plane_stride(H16), RWS = row_stride(H16);
+    constexpr int PS = plane_stride(false), RWS = row_stride(false);
     constexpr int BUF = RH * RWS;  // elements per region buffer
     extern __shared__ __attribute__((aligned(16))) unsigned char k19_smem[];
-    TT* const R = reinterpret_cast<TT*>(k19_smem);  // [2][BUF]
-    constexpr bool Q4 = !M16 && YF_K19_Q4;
-    float* const WQ = reinterpret_cast<float*>(k19_smem + (size_t)2 * BUF * sizeof(TT));  // Q4: [NG][2][64][4]
+    x3_t* const R = reinterpret_cast<x3_t*>(k19_smem);  // [2][BUF]
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // = the tile's output row this wave owns
     const int p = lane & 15, j = lane >> 4;
 
     // ---- weights: registers for the lifetime of the workgroup ----
-    float wf[M16 ? 1 : NG][4][2];
-    f16x8 wh8[M16 ? NG2 : 1][2], wl8[X3 ? NG2 : 1][2];
-    float w21f[2][4];
+    f16x8 wh8[NG2][2], wl8[NG2][2];
     f16x4 w21h[2], w21l[2];
-    if constexpr (X3) {
+    {
         const f16x8* w = reinterpret_cast<const f16x8*>(a.wp);
         const f16x8* wlo = reinterpret_cast<const f16x8*>(a.wp + WX3_HALF);
 #pragma unroll
@@ -119,34 +89,6 @@ __global__ void __launch_bounds__(512) k19m_kernel(K19Args a)
         for (int mt = 0; mt < 2; ++mt) {
             w21h[mt] = reinterpret_cast<const f16x4*>(a.wp + W9_F16)[mt * 64 + lane];
             w21l[mt] = reinterpret_cast<const f16x4*>(a.wp + WX3_HALF + W9_F16)[mt * 64 + lane];
-        }
-    } else if constexpr (H16) {
-        const f16x8* w = reinterpret_cast<const f16x8*>(a.wp);
-#pragma unroll
-        for (int g = 0; g < NG2; ++g)
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt) wh8[g][mt] = w[(g * 2 + mt) * 64 + lane];
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) w21h[mt] = reinterpret_cast<const f16x4*>(a.wp + W9_F16)[mt * 64 + lane];
-    } else {
-#pragma unroll
-        for (int g = 0; g < NG; ++g)
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-#pragma unroll
-                for (int mt = 0; mt < (Q4 ? 1 : 2); ++mt) wf[g][s][mt] = a.wp[((g * 4 + s) * 2 + mt) * 64 + lane];
-#pragma unroll
-        for (int mt = 0; mt < (Q4 ? 1 : 2); ++mt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) w21f[mt][r] = a.wp[W9_F32 + (mt * 4 + r) * 64 + lane];
-    }
-    float w21q[2] = {0.f, 0.f}, biasq[2] = {0.f, 0.f};
-    if constexpr (Q4) {
-        stage_to_lds<WQ_F32, 512>(WQ, a.wp + W9_F32 + W21_F32);   // all loads in flight at once; visible after the prologue's barrier
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            w21q[t] = a.wp[W9_F32 + W21_F32 + WQ_F32 + t * 64 + lane];
-            biasq[t] = a.b9[16 + 4 * t + j];
         }
     }
     float bias9[2][4], bias21[4], w8a[2], bias8[2][4];
@@ -164,18 +106,10 @@ __global__ void __launch_bounds__(512) k19m_kernel(K19Args a)
 #pragma unroll
     for (int r = 0; r < 4; ++r) bias21[r] = j < 2 ? a.b21[4 * j + r] : 0.f;
 
-    // ---- per-lane LDS element offsets (relative to a region buffer) of the 14 B-operand reads of phase 2 ----
-    int adr[NG];
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-        int fc = 4 * g + j;
-        if (fc >= NCHUNK) fc = 0;  // zero weights there; any finite data will do
-        const int tap = fc / 6, c4 = fc - 6 * tap, ky = tap / 3, kx = tap - 3 * ky;
-        adr[g] = (2 * wave + ky) * RWS + (kx == 1 ? PS : 0) + (p + (kx >> 1)) * RS + c4 * 4;
-    }
-
-    int adr2[M16 ? NG2 : 1];   // the pair record lane group j reads in group g -- X3: 32 bytes [hi8 | lo8]; fp16 storage: 8 halves
-    if constexpr (M16) {
+    // ---- per-lane LDS element offsets (relative to a region buffer) of the B-operand reads of phase 2: the pair record lane group j
+    // reads in group g, 32 bytes [hi8 | lo8] ----
+    int adr2[NG2];
+    {
 #pragma unroll
         for (int g = 0; g < NG2; ++g) {
             int fp = 4 * g + j;
@@ -201,20 +135,16 @@ __global__ void __launch_bounds__(512) k19m_kernel(K19Args a)
             const int ry = v ? q / 33 : 0, rx = v ? q - 33 * ry : 0;
             rr[u] = v ? (ry | (rx << 8)) : 0xffff;  // 0xffff: never inside any image window
             vo[u] = (unsigned)((ry * a.W + rx) * 4 + j);
-            const int o = ry * RWS + (rx & 1) * PS + (rx >> 1) * RS + (X3 ? 0 : 4 * j);
-            if constexpr (X3) {   // chunk c = j (M-tile 0) / 4 + j (M-tile 1) -> hi4 slot of its pair record
-                wo0[u] = v ? o + 8 * (j >> 1) + 2 * (j & 1) : dummy;
-                wo1[u] = (v && j < 2) ? o + 16 + 2 * j : dummy;
-            } else {
-                wo0[u] = v ? o : dummy;
-                wo1[u] = (v && j < 2) ? o + 16 : dummy;
-            }
+            const int o = ry * RWS + (rx & 1) * PS + (rx >> 1) * RS;
+            // chunk c = j (M-tile 0) / 4 + j (M-tile 1) -> hi4 slot of its pair record
+            wo0[u] = v ? o + 8 * (j >> 1) + 2 * (j & 1) : dummy;
+            wo1[u] = (v && j < 2) ? o + 16 + 2 * j : dummy;
         }
     }
 
     const int tiles = a.tiles_y * a.tiles_x;
     const int total = a.n_frames * tiles;
-    const TT* const in = reinterpret_cast<const TT*>(a.in);
+    const x3_t* const in = reinterpret_cast<const x3_t*>(a.in);
     float xin[NU];
     struct Tile { int n, oy0, ox0; };
     auto decode = [&](int t) {
@@ -240,7 +170,7 @@ __global__ void __launch_bounds__(512) k19m_kernel(K19Args a)
         const int ylo = max(0, -iy0), yhi = min(RH, a.H - iy0), xlo = max(0, -ix0), xhi = min(33, a.W - ix0);
         return Win{ylo > 0 || yhi < RH || xlo > 0 || xhi < 33, ylo, yhi - ylo, xlo, xhi - xlo};
     };
-    auto p1_store = [&](int u, const f32x4* d, TT* buf, const Win& w) {
+    auto p1_store = [&](int u, const f32x4* d, x3_t* buf, const Win& w) {
         float o[2][4];
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt)
@@ -253,21 +183,16 @@ __global__ void __launch_bounds__(512) k19m_kernel(K19Args a)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) o[mt][r] = inimg ? o[mt][r] : 0.f;
         }
-        if constexpr (X3) {
-            // a 24-channel record is three PAIR records of 32 bytes, [hi4(chunk 2m) hi4(chunk 2m+1) | lo4(chunk 2m) lo4(chunk 2m+1)]:
-            // phase 2 reads hi8 and lo8 of a pair as two 16-byte pieces that ARE the K = 32 MFMA's B fragments.  wo0 / wo1 point at
-            // the lane's chunk (4 floats per chunk): chunk c -> pair c >> 1, half c & 1; hi4 at 8 (c >> 1) + 2 (c & 1), lo4 4 floats on
+        // a 24-channel record is three PAIR records of 32 bytes, [hi4(chunk 2m) hi4(chunk 2m+1) | lo4(chunk 2m) lo4(chunk 2m+1)]:
+        // phase 2 reads hi8 and lo8 of a pair as two 16-byte pieces that ARE the K = 32 MFMA's B fragments.  wo0 / wo1 point at
+        // the lane's chunk (4 floats per chunk): chunk c -> pair c >> 1, half c & 1; hi4 at 8 (c >> 1) + 2 (c & 1), lo4 4 floats on
 #pragma unroll
-            for (int mt = 0; mt < 2; ++mt) {
-                f16x4 hi, lo;
-                split_f16x4(o[mt][0], o[mt][1], o[mt][2], o[mt][3], hi, lo);
-                TT* dst = buf + (mt ? wo1[u] : wo0[u]);
-                *reinterpret_cast<f16x4*>(dst) = hi;
-                *reinterpret_cast<f16x4*>(dst + 4) = lo;
-            }
-        } else {
-            st4<TT>(buf + wo0[u], make_float4(o[0][0], o[0][1], o[0][2], o[0][3]));
-            st4<TT>(buf + wo1[u], make_float4(o[1][0], o[1][1], o[1][2], o[1][3]));
+        for (int mt = 0; mt < 2; ++mt) {
+            f16x4 hi, lo;
+            split_f16x4(o[mt][0], o[mt][1], o[mt][2], o[mt][3], hi, lo);
+            x3_t* dst = buf + (mt ? wo1[u] : wo0[u]);
+            *reinterpret_cast<f16x4*>(dst) = hi;
+            *reinterpret_cast<f16x4*>(dst + 4) = lo;
         }
     };
 
@@ -276,19 +201,19 @@ __global__ void __launch_bounds__(512) k19m_kernel(K19Args a)
     // ---- prologue: region of the first tile -> buffer 0; input elements of the second tile on their way ----
     {
         const Tile c = decode(t);
-        const TT* const o0 = origin(c);
+        const x3_t* const o0 = origin(c);
         const Win w0 = window(c);
 #pragma unroll
-        for (int u = 0; u < NU; ++u) xin[u] = ld1<TT>(o0 + vo[u]);
+        for (int u = 0; u < NU; ++u) xin[u] = ld1<x3_t>(o0 + vo[u]);
 #pragma unroll
         for (int u = 0; u < NU; ++u) {
             f32x4 d[2];
             p1_mfma(u, d);
             p1_store(u, d, R, w0);
         }
-        const TT* const o1 = origin(decode(t + step));
+        const x3_t* const o1 = origin(decode(t + step));
 #pragma unroll
-        for (int u = 0; u < NU; ++u) xin[u] = ld1<TT>(o1 + vo[u]);
+        for (int u = 0; u < NU; ++u) xin[u] = ld1<x3_t>(o1 + vo[u]);
         __syncthreads();
     }
 
@@ -303,156 +228,63 @@ __global__ void __launch_bounds__(512) k19m_kernel(K19Args a)
     Tile c_n = c; Win w1_n = w1; Tile tl_n = tl; long off2_n = off2;
     for (; t < total; t += step) {
         asm volatile("" : "+s"(off2));  // a plain SGPR value from here on (otherwise the origin arithmetic is re-done before every load)
-        const TT* const o2 = in + off2;
-        const TT* const Rc = R + cur;
-        TT* const Rn = R + (BUF - cur);
+        const x3_t* const o2 = in + off2;
+        const x3_t* const Rc = R + cur;
+        x3_t* const Rn = R + (BUF - cur);
 
-        // ---- phase 2 of tile t (conv1_9 on the matrix cores; acc[mt]: channels 16 mt + 4 j + r of the wave's row), with phase 1
-        // of tile t + step spread over its k groups: px-tile u's two MFMAs go out in group 2 u, their results are finished and
-        // stored in group 2 u + 1, and the element of tile t + 2 step that replaces xin[u] is requested right after.  fp32 MFMAs
-        // and VALU instructions do NOT overlap on this part (measured: the two phases' times add up exactly; the fp32 matrix
-        // rate equals the fp32 vector rate), so phase 1 is written for the fewest VALU instructions, not for overlap ----
+        // ---- phase 2 of tile t (conv1_9 on the matrix cores; acc[mt]: channels 16 mt + 4 j + r of the wave's row): 7 groups of 32
+        // k-values on v_mfma_f32_16x16x32_f16, 2 M-tiles x 3 MFMAs with split operands.  Phase 1 of tile t + step rides along: px-tile
+        // u's two fp32 MFMAs go out in group u, its split + store in group u + 1, and the element of tile t + 2 step that replaces
+        // xin[u] is requested right after ----
         f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-        f32x4 accq[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};  // Q4: channels 16 + 4 cg + i, this lane group's k-values only
         f32x4 d[2];
-        if constexpr (M16) {
-            // fp16 matrix pipe: 7 groups of 32 k-values on v_mfma_f32_16x16x32_f16 -- 2 M-tiles x 3 MFMAs with split operands (X3),
-            // 2 x 1 with fp16 storage; phase 1 of the next tile rides along: px-tile u's two fp32 MFMAs in group u, its (split +)
-            // store in group u + 1
-            f16x8 xh = *reinterpret_cast<const f16x8*>(Rc + adr2[0]), xl = xh;
-            if constexpr (X3) xl = *reinterpret_cast<const f16x8*>(Rc + adr2[0] + 4);
+        f16x8 xh = *reinterpret_cast<const f16x8*>(Rc + adr2[0]), xl = *reinterpret_cast<const f16x8*>(Rc + adr2[0] + 4);
 #pragma unroll
-            for (int g = 0; g < NG2; ++g) {
-                f16x8 xhn = xh, xln = xl;
-                if (g + 1 < NG2) {
-                    xhn = *reinterpret_cast<const f16x8*>(Rc + adr2[g + 1]);
-                    if constexpr (X3) xln = *reinterpret_cast<const f16x8*>(Rc + adr2[g + 1] + 4);
-                }
-                if (!(DBG & 1) && g >= 1 && g - 1 < NU) {
-                    p1_store(g - 1, d, Rn, w1);
-                    xin[g - 1] = ld1<TT>(o2 + vo[g - 1]);
-                }
-                if (!(DBG & 1) && g < NU) p1_mfma(g, d);
-                if constexpr (!(DBG & 2)) {
-                    if constexpr (X3) {
-#pragma unroll
-                        for (int mt = 0; mt < 2; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl8[g][mt], xh, acc[mt], 0, 0, 0);
-#pragma unroll
-                        for (int mt = 0; mt < 2; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh8[g][mt], xl, acc[mt], 0, 0, 0);
-                    }
-#pragma unroll
-                    for (int mt = 0; mt < 2; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh8[g][mt], xh, acc[mt], 0, 0, 0);
-                }
-                if (g == 3) { c_n = decode(t + step); w1_n = window(tl); }
-                if (g == 4) { tl_n = decode(t + 3 * step); }
-                if (g == 5) { off2_n = origin(tl_n) - in; }
-                __builtin_amdgcn_sched_barrier(0);
-                xh = xhn; xl = xln;
+        for (int g = 0; g < NG2; ++g) {
+            f16x8 xhn = xh, xln = xl;
+            if (g + 1 < NG2) {
+                xhn = *reinterpret_cast<const f16x8*>(Rc + adr2[g + 1]);
+                xln = *reinterpret_cast<const f16x8*>(Rc + adr2[g + 1] + 4);
             }
+            if (g >= 1 && g - 1 < NU) {
+                p1_store(g - 1, d, Rn, w1);
+                xin[g - 1] = ld1<x3_t>(o2 + vo[g - 1]);
+            }
+            if (g < NU) p1_mfma(g, d);
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl8[g][mt], xh, acc[mt], 0, 0, 0);
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh8[g][mt], xl, acc[mt], 0, 0, 0);
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh8[g][mt], xh, acc[mt], 0, 0, 0);
+            if (g == 3) { c_n = decode(t + step); w1_n = window(tl); }
+            if (g == 4) { tl_n = decode(t + 3 * step); }
+            if (g == 5) { off2_n = origin(tl_n) - in; }
+            __builtin_amdgcn_sched_barrier(0);
+            xh = xhn; xl = xln;
         }
-        using xfrag = f32x4;
-        // LDS operands of group g are requested YF_K19_PF groups ahead (1: 188-190 us; 2: A/B in DESIGN.md)
-        constexpr int PF = YF_K19_PF;
-        // The 4x4x1 weight table lies behind the two region buffers, > 64 KiB into the LDS allocation: past the 16-bit offset field of a
-        // DS instruction, so the compiler paid one v_add_u32 per read (28 per tile).  An opaque per-lane base keeps the per-group
-        // part (<= 27 KiB) in the immediate.
-        int wq_lane = (int)((size_t)2 * BUF * sizeof(TT) / sizeof(float)) + lane * 4;
+        // Leftover of the removed fp32 form (the opaque base of its 4x4x1 weight reads): it has no function here, but without it the
+        // compiler schedules this kernel differently; kept so that the code stays the one that was measured (follow-up: drop it with a
+        // measured A/B).
+        int wq_lane = (int)((size_t)2 * BUF * sizeof(x3_t) / sizeof(float)) + lane * 4;
         asm volatile("" : "+v"(wq_lane));
-        const float* const wq_base = reinterpret_cast<const float*>(k19_smem) + wq_lane;
-        xfrag xq[PF + 1];
-        f32x4 wqq[PF + 1][2];
-#pragma unroll
-        for (int d = 0; d < PF; ++d) {
-            xq[d] = *reinterpret_cast<const xfrag*>(Rc + (M16 ? 0 : adr[d < NG ? d : 0]));
-#pragma unroll
-            for (int cg = 0; cg < 2; ++cg)
-                wqq[d][cg] = Q4 ? *reinterpret_cast<const f32x4*>(wq_base + (d * 2 + cg) * 256) : f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-        xq[PF] = xq[0]; wqq[PF][0] = wqq[0][0]; wqq[PF][1] = wqq[0][1];
-        xfrag xc = xq[0];
-        f32x4 wq[2] = {wqq[0][0], wqq[0][1]};
-#pragma unroll
-        for (int g = 0; g < (M16 ? 0 : NG); ++g) {
-            if (g + PF < NG) {
-                xq[PF] = *reinterpret_cast<const xfrag*>(Rc + adr[g + PF]);
-                if constexpr (Q4) {
-#pragma unroll
-                    for (int cg = 0; cg < 2; ++cg) wqq[PF][cg] = *reinterpret_cast<const f32x4*>(wq_base + ((g + PF) * 2 + cg) * 256);
-                }
-            }
-            if (!(DBG & 1) && (g & 1) == 0 && g / 2 < NU) p1_mfma(g / 2, d);
-            if constexpr (!(DBG & 2)) {
-                if constexpr (Q4) {
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) {
-                        acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[g][s][0], xc[s], acc[0], 0, 0, 0);
-#pragma unroll
-                        for (int cg = 0; cg < 2; ++cg) accq[cg] = __builtin_amdgcn_mfma_f32_4x4x1f32(wq[cg][s], xc[s], accq[cg], 0, 0, 0);
-                    }
-                } else {
-#pragma unroll
-                    for (int s = 0; s < 4; ++s)
-#pragma unroll
-                        for (int mt = 0; mt < 2; ++mt)
-                            acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[g][s][mt], xc[s], acc[mt], 0, 0, 0);
-                }
-            }
-            if (!(DBG & 1) && (g & 1) == 1 && g / 2 < NU) {
-                p1_store(g / 2, d, Rn, w1);
-                xin[g / 2] = ld1<TT>(o2 + vo[g / 2]);
-            }
-            if (g == 10) { c_n = decode(t + step); w1_n = window(tl); }
-            if (g == 11) { tl_n = decode(t + 3 * step); }
-            if (g == 12) { off2_n = origin(tl_n) - in; }
-            __builtin_amdgcn_sched_barrier(0);  // keeps the PF-groups-ahead LDS reads where they are (hoisting all 14 costs 56 VGPRs)
-#pragma unroll
-            for (int d = 0; d < PF; ++d) { xq[d] = xq[d + 1]; wqq[d][0] = wqq[d + 1][0]; wqq[d][1] = wqq[d + 1][1]; }
-            xc = xq[0];
-            if constexpr (Q4) { wq[0] = wqq[0][0]; wq[1] = wqq[0][1]; }
-        }
-
         // ---- epilogue: bias + ReLU, conv2_1 (24 -> 8) chained in registers, store ----
         {
             f32x4 o = f32x4{0.f, 0.f, 0.f, 0.f};
-            if constexpr (Q4) {
-                // channels 16..23: add the four lane groups' partial sums (every lane group then holds all eight totals of its
-                // pixel), bias + ReLU, and hand channel 16 + 4 t + j to conv2_1's k-step t from lane group j
 #pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    float tot[4];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        float v = accq[t][i];
-                        v += __shfl_xor(v, 16);
-                        v += __shfl_xor(v, 32);
-                        tot[i] = v;
-                    }
-                    const float mine = j == 0 ? tot[0] : j == 1 ? tot[1] : j == 2 ? tot[2] : tot[3];
-                    o = __builtin_amdgcn_mfma_f32_16x16x4f32(w21q[t], fmaxf(mine + biasq[t], 0.f), o, 0, 0, 0);
-                }
-            }
-#pragma unroll
-            for (int mt = 0; mt < (Q4 ? 1 : 2); ++mt) {
+            for (int mt = 0; mt < 2; ++mt) {
                 f32x4 h;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) h[r] = fmaxf(acc[mt][r] + bias9[mt][r], 0.f);
-                if constexpr (X3) {
-                    f16x4 hh, hl;
-                    split_f16x4(h[0], h[1], h[2], h[3], hh, hl);
-                    o = __builtin_amdgcn_mfma_f32_16x16x16f16(w21l[mt], hh, o, 0, 0, 0);
-                    o = __builtin_amdgcn_mfma_f32_16x16x16f16(w21h[mt], hl, o, 0, 0, 0);
-                    o = __builtin_amdgcn_mfma_f32_16x16x16f16(w21h[mt], hh, o, 0, 0, 0);
-                } else if constexpr (H16) {
-                    const f16x4 hh = f16x4{(half_t)h[0], (half_t)h[1], (half_t)h[2], (half_t)h[3]};
-                    o = __builtin_amdgcn_mfma_f32_16x16x16f16(w21h[mt], hh, o, 0, 0, 0);
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) o = __builtin_amdgcn_mfma_f32_16x16x4f32(w21f[mt][r], h[r], o, 0, 0, 0);
-                }
+                f16x4 hh, hl;
+                split_f16x4(h[0], h[1], h[2], h[3], hh, hl);
+                o = __builtin_amdgcn_mfma_f32_16x16x16f16(w21l[mt], hh, o, 0, 0, 0);
+                o = __builtin_amdgcn_mfma_f32_16x16x16f16(w21h[mt], hl, o, 0, 0, 0);
+                o = __builtin_amdgcn_mfma_f32_16x16x16f16(w21h[mt], hh, o, 0, 0, 0);
             }
             const int oy = c.oy0 + wave, ox = c.ox0 + p;
             if (j < 2 && oy < a.Ho && ox < a.Wo)
-                st4<TT>(reinterpret_cast<TT*>(a.out) + (((long)c.n * a.Ho + oy) * a.Wo + ox) * 8 + 4 * j,
+                st4<x3_t>(reinterpret_cast<x3_t*>(a.out) + (((long)c.n * a.Ho + oy) * a.Wo + ox) * 8 + 4 * j,
                         make_float4(o[0] + bias21[0], o[1] + bias21[1], o[2] + bias21[2], o[3] + bias21[3]));
         }
         __syncthreads();  // buffer `cur` is free for the tile after next; the other one is complete
@@ -625,35 +457,19 @@ __global__ void __launch_bounds__(R_NW * 64) k19r_kernel(K19Args a)
                         for (int r = 0; r < 6; ++r) b[r] = z ? 0.f : b[r];
                     }
                 }
-#if YF_K19R_PIPE
                 if (t + 1 < 9) c8(t + 1, d, h);   // the next tap's conv1_8 goes out in front of this tap's k-steps: its result is ready when they are done
-#endif
 #pragma unroll
                 for (int s = 0; s < 4; ++s) {
-                    if (!(YF_K19R_DBG & 4)) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[s], b[s], acc, 0, 0, 0);
-                    if (!(YF_K19R_DBG & 1)) {
-                        accq0 = __builtin_amdgcn_mfma_f32_4x4x1f32(wq0[s], b[s], accq0, 0, 0, 0);
-                        accq1 = __builtin_amdgcn_mfma_f32_4x4x1f32(wq1[s], b[s], accq1, 0, 0, 0);
-                    }
+                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[s], b[s], acc, 0, 0, 0);
+                    accq0 = __builtin_amdgcn_mfma_f32_4x4x1f32(wq0[s], b[s], accq0, 0, 0, 0);
+                    accq1 = __builtin_amdgcn_mfma_f32_4x4x1f32(wq1[s], b[s], accq1, 0, 0, 0);
                 }
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
-                    if (!(YF_K19R_DBG & 4)) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wb[s], b[4 + s], acc, 0, 0, 0);
-                    if (!(YF_K19R_DBG & 1)) {
-                        accq0 = __builtin_amdgcn_mfma_f32_4x4x1f32(wq2[s], b[4 + s], accq0, 0, 0, 0);
-                        accq1 = __builtin_amdgcn_mfma_f32_4x4x1f32(wq2[2 + s], b[4 + s], accq1, 0, 0, 0);
-                    }
+                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wb[s], b[4 + s], acc, 0, 0, 0);
+                    accq0 = __builtin_amdgcn_mfma_f32_4x4x1f32(wq2[s], b[4 + s], accq0, 0, 0, 0);
+                    accq1 = __builtin_amdgcn_mfma_f32_4x4x1f32(wq2[2 + s], b[4 + s], accq1, 0, 0, 0);
                 }
-                if (YF_K19R_DBG & 5) {   // (timing builds: keep the operands alive)
-                    acc[0] += b[0] + b[1] + b[2] + b[3] + b[4] + b[5];
-                    if (YF_K19R_DBG & 1) accq0[0] += wq0[0] + wq1[1] + wq2[2];
-                }
-#if YF_K19R_PIPE == 1
-                __builtin_amdgcn_sched_barrier(0);
-#elif YF_K19R_PIPE == 2
-#else
-                if (t + 1 < 9) c8(t + 1, d, h);
-#endif
             }
         };
         if (oy == 0 || sx == 0) taps(std::true_type{});
@@ -710,19 +526,15 @@ constexpr int H_BT = 48;                                        // floats: the w
 constexpr int H_WAVE_BYTES = H_SLICE * 2 + H_BT * 4 + 64 * 16; // + conv2_1's fragment, 16 bytes per lane
 constexpr int H_W9 = 9 * 2 * 64 * 4, H_W21 = 64 * 4;            // floats (an f16x8 fragment = 4 floats per lane)
 constexpr int H_OFF = W9_F16 + W21_F16;                         // the k19h stream follows k19m's in the fp16 blob
+constexpr int X_OFF = 2 * WX3_HALF;                             // f16x3 blob: [W9 hi | W9 lo | W21 hi | W21 lo] behind k19m's stream, in
+                                                                // k19h_kernel's fragment layout (packed, read by no kernel since k19x_kernel went)
 }  // namespace
-#ifndef YF_K19H_DBG
-#define YF_K19H_DBG 0   // timing builds only: 1 = no K = 32 k-steps, 2 = no 4x4x4 MFMAs, 4 = no ReLU / conversion, 8 = no global loads in the loop
-#endif
-#ifndef YF_K19H_C8
-#define YF_K19H_C8 1   // conv1_8 on 1: v_mfma_f32_4x4x4_16B_f16 | 0: v_mfma_f32_16x16x16_f16 with K padded from 4 (A/B builds)
-#endif
 
 // WPS: waves per SIMD the register budget is set for (HIP's second launch bound): 3 -> 128 VGPRs without spills; 4 -> two weight fragments
 // are reloaded from scratch per item.  Measured at 640x512 batch 128 (tools/scratch/k19h_forms.sh): 4 waves per workgroup x 3 per SIMD
 // 69.6 us | 4 x 4 70.5 | 8 x 4 70.5 | 4 x 2 78.6 | k19m_kernel<half_t> 138 (with four + four conversions per tap: 74 | 80 | 80 | 87, and conv1_8
-// on K-padded 16x16x16 MFMAs, YF_K19H_C8=0, 80).
-// Where the time goes (timing builds, YF_K19H_DBG, at 74 us): the 18 K = 32 k-steps of an item are 288 of its ~1100 SIMD cycles; the 4x4x4 MFMAs, the
+// on K-padded 16x16x16 MFMAs, 80).
+// Where the time goes (timing builds, at 74 us): the 18 K = 32 k-steps of an item are 288 of its ~1100 SIMD cycles; the 4x4x4 MFMAs, the
 // conversions and the global loads are worth 4 / 10 / 4 us.  The fp16 matrix pipe co-issues with another wave's VALU instruction only
 // every 8 cycles while it is saturated (tools/coissue_probe.hip --f16: v_cvt_pk_f16_f32 / v_pk_max_f16 at 124 per 1000 cycles beside
 // back-to-back 16x16x32 or 4x4x4 MFMAs, against 245 alone), and a tap has 6 such instructions per 48 MFMA cycles.
@@ -756,15 +568,9 @@ __global__ void __launch_bounds__(R_NW * 64, WPS) k19h_kernel(K19Args a)
         // result row i of lane group jj: channel 4 jj + i (first instruction) / 16 + 2 jj + i, i < 2 (second: rows 2, 3 carry no channel, their
         // weights and bias are zero and their results are not even converted) -- all four lane groups hold six live channels
         auto chan = [&](int jj, int i) { return mt == 0 ? 4 * jj + i : i < 2 ? 16 + 2 * jj + i : -1; };
-#if YF_K19H_C8
         const int cout = chan(j, p & 3);               // the row this lane supplies to its 4x4 block
 #pragma unroll
         for (int k = 0; k < 4; ++k) w8A[mt][k] = cout >= 0 ? (half_t)a.w8[k * 24 + cout] : (half_t)0.f;
-#else
-        const int cout = chan(p >> 2, p & 3);          // row p of the 16-row tile; k = 4j + i: only lane group 0 holds real k-values
-#pragma unroll
-        for (int k = 0; k < 4; ++k) w8A[mt][k] = cout >= 0 && j == 0 ? (half_t)a.w8[k * 24 + cout] : (half_t)0.f;
-#endif
 #pragma unroll
         for (int r = 0; r < 4; ++r) bias8[mt][r] = chan(j, r) >= 0 ? a.b8[chan(j, r)] : 0.f;
     }
@@ -810,11 +616,9 @@ __global__ void __launch_bounds__(R_NW * 64, WPS) k19h_kernel(K19Args a)
     for (; n < a.n_frames;) {
         *reinterpret_cast<f16x4*>(SL + so0) = xin0;
         if (lane < 35) *reinterpret_cast<f16x4*>(SL + so1) = xin1;
-        if (!(YF_K19H_DBG & 8)) {
-            const half_t* o2 = origin(n2, oy2, sx2);
-            xin0 = *reinterpret_cast<const f16x4*>(o2 + vo0);
-            xin1 = *reinterpret_cast<const f16x4*>(o2 + vo1);
-        }
+        const half_t* o2 = origin(n2, oy2, sx2);
+        xin0 = *reinterpret_cast<const f16x4*>(o2 + vo0);
+        xin1 = *reinterpret_cast<const f16x4*>(o2 + vo1);
         f32x4 acc0 = f32x4{0.f, 0.f, 0.f, 0.f}, acc1 = f32x4{0.f, 0.f, 0.f, 0.f};
         auto taps = [&](auto border) {
             constexpr bool BORDER = decltype(border)::value;
@@ -823,28 +627,16 @@ __global__ void __launch_bounds__(R_NW * 64, WPS) k19h_kernel(K19Args a)
                 const int ky = t / 3, kx = t - 3 * ky;
                 const f16x4 x = *reinterpret_cast<const f16x4*>(xb + ky * H_RS + (kx == 1 ? H_PS : 0) + (kx == 2 ? 4 : 0));
                 const f32x4 c0 = bias8[0], c1 = bias8[1];
-#if YF_K19H_DBG & 2
-                d0 = c0 + __builtin_convertvector(x, f32x4); d1 = c1;
-#elif YF_K19H_C8
                 d0 = __builtin_amdgcn_mfma_f32_4x4x4f16(w8A[0], x, c0, 0, 0, 0);
                 d1 = __builtin_amdgcn_mfma_f32_4x4x4f16(w8A[1], x, c1, 0, 0, 0);
-#else
-                d0 = __builtin_amdgcn_mfma_f32_16x16x16f16(w8A[0], x, c0, 0, 0, 0);
-                d1 = __builtin_amdgcn_mfma_f32_16x16x16f16(w8A[1], x, c1, 0, 0, 0);
-#endif
             };
             f32x4 d0, d1;
             c8(0, d0, d1);
 #pragma unroll
             for (int t = 0; t < 9; ++t) {
                 const int ky = t / 3, kx = t - 3 * ky;
-#if YF_K19H_DBG & 4
-                f16x4 b0 = *reinterpret_cast<const f16x4*>(&d0);
-                f16x2 b1 = *reinterpret_cast<const f16x2*>(&d1);
-#else
                 f16x4 b0 = __builtin_elementwise_max(__builtin_convertvector(d0, f16x4), zero4);
                 f16x2 b1 = __builtin_elementwise_max(__builtin_convertvector(f32x2{d1[0], d1[1]}, f16x2), zero2);
-#endif
                 if constexpr (BORDER) {
                     if (ky == 0 || kx == 0) {   // input row -1 / column -1: conv1_9's zero padding of conv1_8's output
                         const bool z = (ky == 0 && top) || (kx == 0 && left && p == 0);
@@ -854,12 +646,8 @@ __global__ void __launch_bounds__(R_NW * 64, WPS) k19h_kernel(K19Args a)
                 }
                 if (t + 1 < 9) c8(t + 1, d0, d1);   // the next tap's conv1_8 goes out in front of this tap's k-steps
                 const f16x8 b = f16x8{b0[0], b0[1], b0[2], b0[3], b1[0], b1[1], (half_t)0.f, (half_t)0.f};
-#if YF_K19H_DBG & 1
-                acc0 += __builtin_convertvector(b0, f32x4) * wA[t][0][0]; acc1[0] += (float)b1[0] * wA[t][1][0]; acc1[1] += (float)b1[1] * wA[t][1][1];
-#else
                 acc0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(wA[t][0], b, acc0, 0, 0, 0);
                 acc1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(wA[t][1], b, acc1, 0, 0, 0);
-#endif
             }
         };
         if (oy == 0 || sx == 0) taps(std::true_type{});
@@ -880,184 +668,14 @@ __global__ void __launch_bounds__(R_NW * 64, WPS) k19h_kernel(K19Args a)
     }
 }
 
-// ------------------------------------------------------------------------------------------------
-// k19x_kernel (round 6; DT_F16X3: fp32 storage, split-operand fp16 MFMAs): the buffer-free scheme of k19r_kernel / k19h_kernel for the engine
-// that meets BASELINE configs[2]'s tolerance.  BUILT, MEASURED, A TIE with k19m_kernel<x3_t> (launch_k19m below has the numbers): not the
-// default; YF_K19X=43 selects it, tests/test_gpu_parity.py::test_f16x3_both_forms_of_the_stride2_block runs both.  Per tap and 16 output pixels
-//   * conv1_8 stays EXACT fp32 exactly as in k19r_kernel: one v_mfma_f32_16x16x4_f32 (K = 4, bias as the C operand) leaves channels
-//     4j .. 4j+3 of pixel p in lane (p, j), four packed FMAs give channels 16 + 2j, 17 + 2j -- six live channels per lane group, the k <-> channel
-//     map of k19h_kernel's K = 32 fragments;
-//   * ReLU, then ONE split of the six values into fp16 hi = rne(v) and lo = rne(v - hi) (3 + 3 conversions, 6 subtractions) -- per tap, in
-//     registers: k19m_kernel<x3_t> split once per REGION pixel but paid for it with two 55 KB region buffers, a workgroup barrier per tile and
-//     the phase-1 store traffic (203 us at 640x512 batch 128, VALU 0.44 beside matrix pipe 0.37);
-//   * conv1_9: per M-tile w_lo x_hi + w_hi x_lo + w_hi x_hi on v_mfma_f32_16x16x32_f16 (six per tap) into fp32 accumulators; the hi fragments
-//     live in registers (72 VGPRs), the lo fragments come from LDS (18 KB per workgroup, two ds_read_b128 per tap);
-//   * epilogue: bias + ReLU + split -> conv2_1 as three K = 32 MFMAs, fp32 store.
-// Items, staging, padding and the unchecked loads (guard band) are k19r_kernel's.  Weight stream (k19_pack_weights, behind k19m's at X_OFF):
-// [W9 hi | W9 lo | W21 hi | W21 lo] in k19h_kernel's fragment layout.
-// ------------------------------------------------------------------------------------------------
-namespace {
-constexpr int X_OFF = 2 * WX3_HALF;
-constexpr int X_LDSW = H_W9 + 2 * H_W21;           // floats staged in LDS: W9 lo | W21 hi | W21 lo
-constexpr int X_BT = 48;                           // floats: [j][bias9 x 6, 2 unused | bias21 x 4]
-}  // namespace
-template <int R_NW, int WPS>
-__global__ void __launch_bounds__(R_NW * 64, WPS) k19x_kernel(K19Args a)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char k19_smem[];
-    float* const WL = reinterpret_cast<float*>(k19_smem);           // [9][2][64] f16x8 lo fragments | [64] W21 hi | [64] W21 lo
-    float* const BT = WL + X_LDSW;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int p = lane & 15, j = lane >> 4;
-    float* const SL = BT + X_BT + wave * R_SLICE;
-
-    stage_to_lds<X_LDSW, R_NW * 64>(WL, a.wp + X_OFF + H_W9);
-    if (threadIdx.x < 48) {
-        const int jj = threadIdx.x / 12, e = threadIdx.x - 12 * jj;
-        BT[threadIdx.x] = e < 4 ? a.b9[4 * jj + e] : e < 6 ? a.b9[16 + 2 * jj + e - 4] : e < 8 ? 0.f : (jj < 2 ? a.b21[4 * jj + e - 8] : 0.f);
-    }
-    // ---- conv1_9's hi fragments in registers for the lifetime of the wave ----
-    f16x8 wA[9][2];
-    {
-        const f16x8* w = reinterpret_cast<const f16x8*>(a.wp + X_OFF);
-#pragma unroll
-        for (int t = 0; t < 9; ++t)
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt) wA[t][mt] = w[(t * 2 + mt) * 64 + lane];
-    }
-    float bias8[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) bias8[r] = a.b8[4 * j + r];
-    const float w8a = a.w8[j * 24 + p];                     // conv1_8's A operand, channels 0..15: row = cout p, k = cin j
-    f32x2 w8h[4], b8h;                                      // channels 16 + 2j, 17 + 2j on the VALU
-#pragma unroll
-    for (int c = 0; c < 4; ++c) w8h[c] = f32x2{a.w8[c * 24 + 16 + 2 * j], a.w8[c * 24 + 17 + 2 * j]};
-    b8h = f32x2{a.b8[16 + 2 * j], a.b8[17 + 2 * j]};
-
-    // ---- the lane's two staging records, item walk: k19r_kernel's ----
-    const int row0 = lane / 33, c0 = lane - 33 * row0;
-    const int idx1 = lane + 64 < 99 ? lane + 64 : 0, row1 = idx1 / 33, c1 = idx1 - 33 * row1;
-    const unsigned vo0 = (unsigned)((row0 * a.W + c0) * 4), vo1 = (unsigned)((row1 * a.W + c1) * 4);
-    const int so0 = row0 * R_RS + (c0 & 1) * R_PS + (c0 >> 1) * 4, so1 = row1 * R_RS + (c1 & 1) * R_PS + (c1 >> 1) * 4;
-    const int segs = (a.Wo + 15) >> 4;
-    const int nwaves = gridDim.x * R_NW;
-    const int per_frame = a.Ho * segs;
-    const int d_n = nwaves / per_frame, d_r = nwaves - d_n * per_frame, d_oy = d_r / segs, d_sx = d_r - d_oy * segs;
-    const int w0 = blockIdx.x * R_NW + wave;
-    int n = w0 / per_frame, oy = (w0 - n * per_frame) / segs, sx = w0 - n * per_frame - oy * segs;
-    auto advance = [&](int& n_, int& oy_, int& sx_) {
-        sx_ += d_sx; oy_ += d_oy; n_ += d_n;
-        if (sx_ >= segs) { sx_ -= segs; ++oy_; }
-        if (oy_ >= a.Ho) { oy_ -= a.Ho; ++n_; }
-    };
-    auto origin = [&](int n_, int oy_, int sx_) {
-        const int nn = n_ < a.n_frames ? n_ : 0;
-        return a.in + (((long)nn * a.H + (2 * oy_ - 1)) * a.W + (32 * sx_ - 1)) * 4;
-    };
-    f32x4 xin0, xin1;
-    {
-        const float* o0 = origin(n, oy, sx);
-        xin0 = *reinterpret_cast<const f32x4*>(o0 + vo0);
-        xin1 = *reinterpret_cast<const f32x4*>(o0 + vo1);
-    }
-    __syncthreads();   // the lo fragments and the bias table are staged (the only workgroup-wide step)
-    int n2 = n, oy2 = oy, sx2 = sx;
-    advance(n2, oy2, sx2);
-    const float* const xb = SL + p * 4;        // the 16-byte record of pixel p
-    const float* const xjb = SL + p * 4 + j;   // its channel j (conv1_8's B operand)
-    const f16x8* const wlo = reinterpret_cast<const f16x8*>(WL) + lane;
-    const float* const bt = BT + 12 * j;
-    const half_t hz = (half_t)0.f;
-
-    for (; n < a.n_frames;) {
-        *reinterpret_cast<f32x4*>(SL + so0) = xin0;
-        if (lane < 35) *reinterpret_cast<f32x4*>(SL + so1) = xin1;
-        {
-            const float* o2 = origin(n2, oy2, sx2);
-            xin0 = *reinterpret_cast<const f32x4*>(o2 + vo0);
-            xin1 = *reinterpret_cast<const f32x4*>(o2 + vo1);
-        }
-        f32x4 acc0 = f32x4{0.f, 0.f, 0.f, 0.f}, acc1 = f32x4{0.f, 0.f, 0.f, 0.f};
-        auto taps = [&](auto border) {
-            constexpr bool BORDER = decltype(border)::value;
-            const bool top = oy == 0, left = sx == 0;
-            auto c8 = [&](int t, f32x4& d, f32x2& h) {
-                const int ky = t / 3, kx = t - 3 * ky;
-                const int off = ky * R_RS + (kx == 1 ? R_PS : 0) + (kx == 2 ? 4 : 0);
-                const float xj = xjb[off];
-                const f32x4 x4 = *reinterpret_cast<const f32x4*>(xb + off);
-                d = __builtin_amdgcn_mfma_f32_16x16x4f32(w8a, xj, f32x4{bias8[0], bias8[1], bias8[2], bias8[3]}, 0, 0, 0);
-                h = b8h;
-                h = __builtin_elementwise_fma(f32x2{x4[0], x4[0]}, w8h[0], h);
-                h = __builtin_elementwise_fma(f32x2{x4[1], x4[1]}, w8h[1], h);
-                h = __builtin_elementwise_fma(f32x2{x4[2], x4[2]}, w8h[2], h);
-                h = __builtin_elementwise_fma(f32x2{x4[3], x4[3]}, w8h[3], h);
-            };
-            f32x4 d;
-            f32x2 h;
-            c8(0, d, h);
-#pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                const int ky = t / 3, kx = t - 3 * ky;
-                float b[6];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) b[r] = __int_as_float(max(__float_as_int(d[r]), 0));   // ReLU as one v_max_i32
-                b[4] = __int_as_float(max(__float_as_int(h[0]), 0));
-                b[5] = __int_as_float(max(__float_as_int(h[1]), 0));
-                if constexpr (BORDER) {
-                    if (ky == 0 || kx == 0) {   // input row -1 / column -1: conv1_9's zero padding of conv1_8's output
-                        const bool z = (ky == 0 && top) || (kx == 0 && left && p == 0);
-#pragma unroll
-                        for (int r = 0; r < 6; ++r) b[r] = z ? 0.f : b[r];
-                    }
-                }
-                f16x4 h4, l4;
-                f16x2 h2, l2;
-                split_f16x4(b[0], b[1], b[2], b[3], h4, l4);
-                split_f16x2(b[4], b[5], h2, l2);
-                const f16x8 bh = f16x8{h4[0], h4[1], h4[2], h4[3], h2[0], h2[1], hz, hz};
-                const f16x8 bl = f16x8{l4[0], l4[1], l4[2], l4[3], l2[0], l2[1], hz, hz};
-                const f16x8 wl0 = wlo[(t * 2 + 0) * 64], wl1 = wlo[(t * 2 + 1) * 64];
-                if (t + 1 < 9) c8(t + 1, d, h);   // the next tap's conv1_8 goes out in front of this tap's k-steps
-                acc0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl0, bh, acc0, 0, 0, 0);       // small terms first, then hi * hi
-                acc1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl1, bh, acc1, 0, 0, 0);
-                acc0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(wA[t][0], bl, acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(wA[t][1], bl, acc1, 0, 0, 0);
-                acc0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(wA[t][0], bh, acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(wA[t][1], bh, acc1, 0, 0, 0);
-            }
-        };
-        if (oy == 0 || sx == 0) taps(std::true_type{});
-        else taps(std::false_type{});
-        {   // bias + ReLU + split -> conv2_1 (24 -> 8) on three K = 32 MFMAs, fp32 store
-            const f32x4 bias9a = *reinterpret_cast<const f32x4*>(bt), bias9b = *reinterpret_cast<const f32x4*>(bt + 4), bias21 = *reinterpret_cast<const f32x4*>(bt + 8);
-            f16x4 h4, l4;
-            f16x2 h2, l2;
-            split_f16x4(fmaxf(acc0[0] + bias9a[0], 0.f), fmaxf(acc0[1] + bias9a[1], 0.f), fmaxf(acc0[2] + bias9a[2], 0.f), fmaxf(acc0[3] + bias9a[3], 0.f), h4, l4);
-            split_f16x2(fmaxf(acc1[0] + bias9b[0], 0.f), fmaxf(acc1[1] + bias9b[1], 0.f), h2, l2);
-            const f16x8 hh = f16x8{h4[0], h4[1], h4[2], h4[3], h2[0], h2[1], hz, hz};
-            const f16x8 hl = f16x8{l4[0], l4[1], l4[2], l4[3], l2[0], l2[1], hz, hz};
-            const f16x8 w21h = wlo[18 * 64], w21l = wlo[19 * 64];
-            f32x4 o = bias21;
-            o = __builtin_amdgcn_mfma_f32_16x16x32_f16(w21l, hh, o, 0, 0, 0);
-            o = __builtin_amdgcn_mfma_f32_16x16x32_f16(w21h, hl, o, 0, 0, 0);
-            o = __builtin_amdgcn_mfma_f32_16x16x32_f16(w21h, hh, o, 0, 0, 0);
-            const int ox = 16 * sx + p;
-            if (j < 2 && ox < a.Wo)
-                *reinterpret_cast<float4*>(a.out + (((long)n * a.Ho + oy) * a.Wo + ox) * 8 + 4 * j) = make_float4(o[0], o[1], o[2], o[3]);
-        }
-        n = n2; oy = oy2; sx = sx2;
-        advance(n2, oy2, sx2);
-    }
-}
-
 size_t k19_packed_floats(int wmode)
 {
     return wmode == WM_F16X3 ? (size_t)(X_OFF + 2 * (H_W9 + H_W21)) : wmode == WM_F16 ? (size_t)(H_OFF + H_W9 + H_W21) : (size_t)(R_OFF + 2 * (R_WA + R_WB) + R_WQ);
 }
 
-// w9: [tap][cin][cout] (blob layout of the dense 3x3), w21: [cin][cout]
+// w9: [tap][cin][cout] (blob layout of the dense 3x3), w21: [cin][cout].  The layouts are those of the kernels of rounds 1-6: in the fp32
+// blob the region-buffer segment in front of R_OFF, in the fp16 blob the one in front of H_OFF and in the f16x3 blob the one behind X_OFF
+// are packed but read by no kernel since the forms that read them were removed (follow-up: drop them together with the offsets).
 void k19_pack_weights(const float* w9, const float* w21, float* out, int wmode)
 {
     const bool h16 = wmode != WM_F32, x3 = wmode == WM_F16X3;
@@ -1075,7 +693,7 @@ void k19_pack_weights(const float* w9, const float* w21, float* out, int wmode)
                         if (x3) ol[((size_t)(g * 2 + mt) * 64 + l) * 8 + e] = f16_lo_bits(v);
                     }
     }
-    if (h16) {   // k19h_kernel / k19x_kernel: per tap ONE K = 32 fragment per M-tile (x3: [W9 hi | W9 lo | W21 hi | W21 lo] behind k19m's stream)
+    if (h16) {   // k19h_kernel: per tap ONE K = 32 fragment per M-tile (x3: [W9 hi | W9 lo | W21 hi | W21 lo] behind k19m's stream)
         uint16_t* o9 = reinterpret_cast<uint16_t*>(out + (x3 ? X_OFF : H_OFF));
         uint16_t* o21 = reinterpret_cast<uint16_t*>(out + (x3 ? X_OFF + 2 * H_W9 : H_OFF + H_W9));
         uint16_t* o9l = reinterpret_cast<uint16_t*>(out + X_OFF + H_W9);
@@ -1115,7 +733,7 @@ void k19_pack_weights(const float* w9, const float* w21, float* out, int wmode)
                 else out[W9_F32 + (mt * 4 + r) * 64 + l] = v;
                 if (x3) ol[(size_t)W9_F16 * 2 + ((size_t)mt * 64 + l) * 4 + r] = f16_lo_bits(v);
             }
-    if (!h16) {   // the 4x4-block form of channels 16..23 (k19m_kernel, Q4)
+    if (!h16) {   // the 4x4-block form of channels 16..23 (the removed fp32 region-buffer form)
         float* wq = out + W9_F32 + W21_F32;
         for (int g = 0; g < NG; ++g)
             for (int cg = 0; cg < 2; ++cg)
@@ -1154,7 +772,7 @@ void k19_pack_weights(const float* w9, const float* w21, float* out, int wmode)
 
 // Pixels of the 4-channel input that the two kernels' UNCHECKED 16-byte loads may touch before / after the tensor (W = its width in pixels).
 // launch_k19m() must only be handed an input with k19m_guard_elems(W) readable elements on either side (the engine's workspace guard band,
-// yf_engine.hip plan_workspace; tools/kbench.hip allocates the same): nothing else bounds these loads.
+// yf_engine.hip plan_workspace): nothing else bounds these loads.
 //   k19m_kernel: the 17x33 region of an 8x16 output tile starts one row and one column outside and ends up to 33 columns past a row end;
 //   k19r_kernel: a wave's 3x33 region starts at input (2 oy - 1, 32 sx - 1) -> W + 1 pixels before the tensor, and its last segment
 //                reaches column 32 segs - 1 + 32 <= W + 30 of the last row -> at most 31 pixels past the end.
@@ -1167,10 +785,7 @@ size_t k19m_guard_elems(int W)
     return (px * 4 + 63) & ~(size_t)63;
 }
 
-size_t k19m_lds_bytes(int dtype)
-{
-    return (size_t)2 * RH * row_stride(dtype == DT_F16) * (dtype == DT_F16 ? 2 : 4) + (dtype != DT_F32 || !YF_K19_Q4 ? 0 : (size_t)WQ_F32 * 4);
-}
+static constexpr size_t k19m_lds_bytes = (size_t)2 * RH * row_stride(false) * sizeof(x3_t);   // two region buffers
 
 template <int R_NW, bool WLDS>
 static int launch_k19r_t(const K19Args& a, long items, int n_cu, int dev, hipStream_t s)
@@ -1196,100 +811,35 @@ static int launch_k19h_t(const K19Args& a, long items, int n_cu, hipStream_t s)
     return 0;
 }
 
-template <int R_NW, int WPS>
-static int launch_k19x_t(const K19Args& a, long items, int n_cu, int dev, hipStream_t s)
-{
-    static bool attr_x[YF_MAX_DEVICES] = {};
-    constexpr size_t lds = (size_t)(X_LDSW + X_BT + R_NW * R_SLICE) * sizeof(float);
-    if (lds > 64 * 1024 && !attr_x[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k19x_kernel<R_NW, WPS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return -1;
-        attr_x[dev] = true;
-    }
-    const long wgs = (items + R_NW - 1) / R_NW, cap = (long)n_cu * (4 * WPS / R_NW > 0 ? 4 * WPS / R_NW : 1);
-    hipLaunchKernelGGL((k19x_kernel<R_NW, WPS>), dim3((unsigned)(wgs < cap ? wgs : cap)), dim3(R_NW * 64), lds, s, a);
-    return 0;
-}
-
-// fp32: k19r_kernel unless YF_K19R=0 (A/B: the region-buffer kernel of rounds 1-3)
-static bool k19r_enabled()
-{
-    static const bool on = [] { const char* v = getenv("YF_K19R"); return !(v && v[0] == '0'); }();
-    return on;
-}
-
 int launch_k19m(K19Args a, int N, hipStream_t s, int dtype)
 {
     const int dev = current_device(), n_cu = device_cu_count(dev);
     if (n_cu <= 0) return -1;
+    a.n_frames = N;
+    // the engine only plans inputs whose sides are multiples of 32, so conv1_8's input always has even sides
+    const long items = (long)N * a.Ho * ((a.Wo + 15) / 16);
+    if (dtype == DT_F32) {
+        // 16 waves, conv1_9's fragments read from LDS (156 us; 8 waves: 166, 12: 160, 12 from LDS: 162).  Small batches: the 8-wave form
+        // (fragments in registers, a third of the LDS prologue) -- 11.6 -> 8.3 us at batch 1, 12.4 -> 9.0 at 4, 20.8 -> 18.4 at 16
+        // (tools/small_batch_ops.py)
+        return items <= 64L * n_cu ? launch_k19r_t<8, false>(a, items, n_cu, dev, s) : launch_k19r_t<16, true>(a, items, n_cu, dev, s);
+    }
+    if (dtype == DT_F16) return launch_k19h_t<4, 3>(a, items, n_cu, s);   // 4 waves per workgroup, 3 per SIMD (69.6 us; see k19h_kernel)
+    // DT_F16X3: the region-buffer kernel.  The buffer-free split-operand form (k19x_kernel, removed) only tied it at 640x512 batch 128 (197-198 us
+    // against this kernel's 198-201): its per-tap operand split costs as much VALU time as the barrier it saves.
     static bool attr_done[YF_MAX_DEVICES] = {};
     if (!attr_done[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k19m_kernel<float, 0>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)k19m_lds_bytes(DT_F32)) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&k19m_kernel<half_t, 0>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)k19m_lds_bytes(DT_F16)) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&k19m_kernel<x3_t, 0>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)k19m_lds_bytes(DT_F16X3)) != hipSuccess)
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k19m_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)k19m_lds_bytes) != hipSuccess)
             return -1;
         attr_done[dev] = true;
-    }
-    a.n_frames = N;
-    if (dtype == DT_F32 && k19r_enabled() && a.H % 2 == 0 && a.W % 2 == 0) {
-        // developer switch: 16 = weights from LDS (default: 156 us); A/B: 8 (166 us) | 12 (160 us) | 1012 = 12 waves, weights from LDS (162 us);
-        // anything else is refused (it used to select the 12-wave form silently)
-        static const int nw = [] {
-            const char* v = getenv("YF_K19R_NW");
-            if (!v || !*v) return 16;
-            const int k = atoi(v);
-            if (k != 8 && k != 12 && k != 16 && k != 1012) { fprintf(stderr, "yolo_fastest_hip: YF_K19R_NW=%s is not one of 8, 12, 16, 1012\n", v); return -1; }
-            return k;
-        }();
-        if (nw < 0) return -1;
-        const long items = (long)N * a.Ho * ((a.Wo + 15) / 16);
-        // small batches: the 8-wave form (conv1_9's fragments in registers, a third of the LDS prologue) -- 11.6 -> 8.3 us at batch 1, 12.4 -> 9.0 at
-        // 4, 20.8 -> 18.4 at 16 (tools/small_batch_ops.py); unless the developer switch asks for a form
-        if (!getenv("YF_K19R_NW") && items <= 64L * n_cu) return launch_k19r_t<8, false>(a, items, n_cu, dev, s);
-        return nw == 8 ? launch_k19r_t<8, false>(a, items, n_cu, dev, s) : nw == 16 ? launch_k19r_t<16, true>(a, items, n_cu, dev, s)
-                       : nw == 1012 ? launch_k19r_t<12, true>(a, items, n_cu, dev, s) : launch_k19r_t<12, false>(a, items, n_cu, dev, s);
-    }
-    if (dtype == DT_F16 && k19r_enabled() && a.H % 2 == 0 && a.W % 2 == 0) {   // fp16 storage: k19h_kernel (YF_K19R=0: the region-buffer kernel)
-        // developer switch YF_K19H_FORM = waves per workgroup * 10 + waves per SIMD (A/B; default 43)
-        static const int form = [] { const char* v = getenv("YF_K19H_FORM"); return v && *v ? atoi(v) : 43; }();
-        const long items = (long)N * a.Ho * ((a.Wo + 15) / 16);
-        switch (form) {
-        case 43: return launch_k19h_t<4, 3>(a, items, n_cu, s);
-        case 44: return launch_k19h_t<4, 4>(a, items, n_cu, s);
-        case 42: return launch_k19h_t<4, 2>(a, items, n_cu, s);
-        case 84: return launch_k19h_t<8, 4>(a, items, n_cu, s);
-        default: fprintf(stderr, "yolo_fastest_hip: YF_K19H_FORM=%d is not one of 42, 43, 44, 84\n", form); return -1;
-        }
-    }
-    if (dtype == DT_F16X3 && k19r_enabled() && a.H % 2 == 0 && a.W % 2 == 0) {   // split operands: k19x_kernel (YF_K19X=0 / YF_K19R=0: the region-buffer kernel)
-        // Measured (tools/x3_ab.sh, 640x512 batch 128, two interleaved rounds, us): k19m_kernel<x3_t> 198-201 | k19x 4 waves x 3 per SIMD 197-198 |
-        // 12 x 3 201 (with the v_fma_mix split, yf_kernels.h YF_X3_MIX: 190-192 | 190-191 | 194) -- a TIE: per 16 output pixels k19x issues ~340 VALU
-        // instructions (six conversions + six subtractions + six ReLUs per tap: the per-tap split) + 9 fp32 and 57 fp16 MFMAs = ~2600 issue cycles,
-        // and they do not overlap (2700 measured); the region-buffer kernel splits once per region pixel and pays for its barrier instead.
-        // Default: k19m_kernel (YF_K19X unset or 0); YF_K19X=43 / 42 / 83 / 123 select a k19x form (waves per workgroup * 10 + waves per SIMD).
-        static const int form = [] { const char* v = getenv("YF_K19X"); return v && *v ? atoi(v) : 0; }();
-        const long items = (long)N * a.Ho * ((a.Wo + 15) / 16);
-        switch (form) {
-        case 0: break;
-        case 43: return launch_k19x_t<4, 3>(a, items, n_cu, dev, s);
-        case 42: return launch_k19x_t<4, 2>(a, items, n_cu, dev, s);
-        case 83: return launch_k19x_t<8, 3>(a, items, n_cu, dev, s);
-        case 123: return launch_k19x_t<12, 3>(a, items, n_cu, dev, s);
-        default: fprintf(stderr, "yolo_fastest_hip: YF_K19X=%d is not one of 0, 42, 43, 83, 123\n", form); return -1;
-        }
     }
     a.tiles_y = (a.Ho + TH - 1) / TH;
     a.tiles_x = (a.Wo + TW - 1) / TW;
     const long total = (long)N * a.tiles_y * a.tiles_x;
     // persistent: one workgroup (8 waves, two per SIMD) per CU
-    const long want = (long)n_cu;
-    const unsigned grid = (unsigned)(total < want ? total : want);
-    if (dtype == DT_F16) hipLaunchKernelGGL((k19m_kernel<half_t, 0>), dim3(grid), dim3(512), k19m_lds_bytes(DT_F16), s, a);
-    else if (dtype == DT_F16X3) hipLaunchKernelGGL((k19m_kernel<x3_t, 0>), dim3(grid), dim3(512), k19m_lds_bytes(DT_F16X3), s, a);
-    else hipLaunchKernelGGL((k19m_kernel<float, 0>), dim3(grid), dim3(512), k19m_lds_bytes(DT_F32), s, a);
+    const unsigned grid = (unsigned)(total < n_cu ? total : n_cu);
+    hipLaunchKernelGGL(k19m_kernel, dim3(grid), dim3(512), k19m_lds_bytes, s, a);
     return 0;
 }
 

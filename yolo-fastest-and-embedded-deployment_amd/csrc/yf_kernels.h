@@ -53,59 +53,19 @@ template <> __device__ __forceinline__ float ld1<x3_t>(const x3_t* p) { return p
 template <typename T> __device__ __forceinline__ void st1(T* p, float v) { *p = (T)v; }
 template <> __device__ __forceinline__ void st1<x3_t>(x3_t* p, float v) { p->v = v; }
 // split fp32 values into fp16 hi and lo halves: hi = rne(a), lo = rne(a - hi); a - hi is exact in fp32.
-// YF_X3_MIX (round 6): lo through v_fma_mixlo_f16 / v_fma_mixhi_f16 -- fma(hi as f16, -1.0, a) rounded once to f16 and written straight into a
-// half of the packed register: one instruction per value where the C form costs 2.5 (v_cvt_f32_f16, a packed subtraction per pair, a
-// v_cvt_pk_f16_f32 per pair).  The same bits: a - hi is exact, both forms round the same real number once (tools/mix_probe.hip: 2 M pairs,
-// normal and denormal results, bit-identical).  No builtin exists, so this is inline asm -- and the compiler's hazard recogniser does not see
-// inside it: an MFMA that reads the result in the next cycle got the STALE register (VALU write -> MFMA read needs wait states the compiler
-// inserts only for instructions it knows to be VALU; test_deep_stage_fusion_is_bitwise_neutral caught it as two fusion levels disagreeing).
-// Hence the trailing s_nop in the asm block: YF_X3_MIX_NOP wait states (2 = what the compiler places for its own VALU writes).
-// Measured with the s_nop in place (tools/x3_ab.sh, 640x512 batch 128 f16x3, two interleaved rounds): conv1_8+conv1_9+conv2_1 198-201 -> 190-192 us,
-// deconv5_1+conv4_1_1 46.0 -> 48.4 (its compiler-scheduled form was the tighter one), every other launch +-1 %: launch sum 1410 -> 1411-1415 us.
-// No gain for the pass: OFF.
-#ifndef YF_X3_MIX
-#define YF_X3_MIX 0
-#endif
-#ifndef YF_X3_MIX_NOP
-#define YF_X3_MIX_NOP 1    // s_nop operand: N + 1 wait states
-#endif
-#define YF_STR2(x) #x
-#define YF_STR(x) YF_STR2(x)
 __device__ __forceinline__ void split_f16x2(float a0, float a1, f16x2& hi, f16x2& lo)
 {
     typedef float f32x2v __attribute__((ext_vector_type(2)));
     const f32x2v a = {a0, a1};
     hi = __builtin_convertvector(a, f16x2);
-#if YF_X3_MIX
-    unsigned r, h = __builtin_bit_cast(unsigned, hi);
-    asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mixhi_f16 %0, %1, -1.0, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-        "s_nop " YF_STR(YF_X3_MIX_NOP)
-        : "=&v"(r) : "v"(h), "v"(a0), "v"(a1));
-    lo = __builtin_bit_cast(f16x2, r);
-#else
     lo = __builtin_convertvector(a - __builtin_convertvector(hi, f32x2v), f16x2);
-#endif
 }
 __device__ __forceinline__ void split_f16x4(float a0, float a1, float a2, float a3, f16x4& hi, f16x4& lo)
 {
     typedef float f32x4v __attribute__((ext_vector_type(4)));
     const f32x4v a = {a0, a1, a2, a3};
     hi = __builtin_convertvector(a, f16x4);
-#if YF_X3_MIX
-    typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
-    const u32x2v h = __builtin_bit_cast(u32x2v, hi);
-    unsigned r0, r1;
-    asm("v_fma_mixlo_f16 %0, %2, -1.0, %4 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mixlo_f16 %1, %3, -1.0, %6 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mixhi_f16 %0, %2, -1.0, %5 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mixhi_f16 %1, %3, -1.0, %7 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-        "s_nop " YF_STR(YF_X3_MIX_NOP)
-        : "=&v"(r0), "=&v"(r1) : "v"(h[0]), "v"(h[1]), "v"(a0), "v"(a1), "v"(a2), "v"(a3));
-    lo = __builtin_bit_cast(f16x4, u32x2v{r0, r1});
-#else
     lo = __builtin_convertvector(a - __builtin_convertvector(hi, f32x4v), f16x4);
-#endif
 }
 #endif
 
@@ -147,20 +107,12 @@ __device__ __forceinline__ void stage_to_lds(float* __restrict__ dst, const floa
 
 // Workgroups are dealt round-robin to the 8 XCDs of the chip (block i -> XCD i % 8), each with its own L2.  xcd_tile() gives XCD x the
 // CONTIGUOUS range [x * per, (x + 1) * per) of logical tiles, so that neighbouring tiles of a frame -- which share halo rows and
-// columns -- are fetched through one L2 instead of up to eight.  The ragged tail (grid % 8) keeps its index.  -DYF_XCD_SWIZZLE=0: off.
-#ifndef YF_XCD_SWIZZLE
-#define YF_XCD_SWIZZLE 1
-#endif
+// columns -- are fetched through one L2 instead of up to eight.  The ragged tail (grid % 8) keeps its index.
 #ifdef __HIPCC__
 __device__ __forceinline__ int xcd_tile(unsigned b, unsigned nb)
 {
-#if YF_XCD_SWIZZLE
     const unsigned per = nb >> 3, main = per << 3;
     return b < main ? (int)((b & 7) * per + (b >> 3)) : (int)b;
-#else
-    (void)nb;
-    return (int)b;
-#endif
 }
 #endif
 
@@ -266,7 +218,7 @@ struct FbArgs {
     const uint8_t* in_u8;         // PRE only, optional: u8 frames instead of `in` (pre-process fused into the load): gray [N,h,w], or --
                                   // C0 = 3 -- cv2's HWC BGR [N,h,w,3], channel-flipped on the fly (detect.py:119)
     int u8_down2;                 //   1: the u8 frame is exactly 2x the net input (2x2 box mean first)
-    unsigned long long* dbg;      // diagnostic builds only (-DYF_STAMP): per-phase cycle sums; null in the product
+    unsigned long long* dbg;      // unused: kept so that the kernel-argument layout stays as it is
 };
 // pre: 0 = no conv0 in front; 1 / 3 = conv0 on that many input channels evaluated on the fly
 int launch_fused_block(int cin, int cexp, int cout, int stride, bool res, bool relu_out, int pre, const FbArgs& a, int N,
@@ -343,10 +295,9 @@ struct K19Args {
     const float* wp;              // k19m: MFMA A fragments of conv1_9 and conv2_1 (k19_pack_weights)
     int n_frames;
 };
-int launch_k19(K19Args a, int N, hipStream_t s, int dtype = DT_F32);    // VALU version (kept for tools/kbench.hip)
+int launch_k19(K19Args a, int N, hipStream_t s, int dtype = DT_F32);    // VALU version: no caller left (follow-up: remove it with k19_kernel)
 int launch_k19m(K19Args a, int N, hipStream_t s, int dtype = DT_F32);   // matrix-core version (the plan's)
 size_t k19_packed_floats(int wmode = WM_F32);
-size_t k19m_lds_bytes(int dtype);
 size_t k19m_guard_elems(int W);   // the engine keeps this many elements free before and after the workspace slots
 void k19_pack_weights(const float* w9, const float* w21, float* out, int wmode = WM_F32);
 

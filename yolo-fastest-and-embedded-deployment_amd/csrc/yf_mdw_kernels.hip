@@ -18,26 +18,6 @@ namespace yf {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// Diagnostic build only (-DYF_MDW_STAMP, tools/kbench.hip mdw): per-phase shader-clock sums of wave 0 of every workgroup.
-#ifdef YF_MDW_STAMP
-__device__ unsigned long long yf_mdw_dbg[8];
-__device__ __forceinline__ unsigned long long mdw_clock()
-{
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-#define MDW_STAMP_DECL unsigned long long st_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_t_ = mdw_clock();
-#define MDW_STAMP(i) { unsigned long long n_ = mdw_clock(); st_[i] += n_ - st_t_; st_t_ = n_; }
-#define MDW_STAMP_FLUSH if (threadIdx.x == 0) { for (int i_ = 0; i_ < 8; ++i_) atomicAdd(&yf_mdw_dbg[i_], st_[i_]); }
-#else
-#define MDW_STAMP_DECL
-#define MDW_STAMP(i)
-#define MDW_STAMP_FLUSH
-#endif
-
 // h16: B fragments are f16x4 per lane (one v_mfma_f32_16x16x16_f16 per 16-channel chunk and n-tile); dw weights / biases stay fp32
 // wmode WM_F16X3 (split operands): every fp16 fragment block is followed by its lo halves (same layout)
 __host__ __device__ constexpr int mdw_chunk_floats(int n, int wmode = WM_F32)
@@ -57,22 +37,19 @@ __host__ __device__ constexpr int mdw_stream_floats(int c, int n, int headn, int
 
 typedef float mdw_f32x2 __attribute__((ext_vector_type(2)));
 
+// the small head's 1x1 convs (128 output channels) in fp32: per-chunk partial sums (see mdw_kernel, PSUM)
+__host__ __device__ constexpr bool mdw_psum(int n, int wmode) { return n == 128 && wmode == WM_F32; }
 // Pixels per 4-channel plane of E, chosen for the 25-tap window READS (ten times the fill writes): a ds_read_b128 is serviced
 // in lane groups that mix two channel quads -- lanes r in {0-3, 12-15} of quad q with r in {4-11} of quad q + 1
 // (MI355X_MICROARCH.md, LDS).  Lanes on consecutive pixels (one tile per wave) want the pitch == 0 (mod 16 records) so the two
 // quads land on complementary banks; lanes on every second pixel (ADJ: two adjacent pixels per lane) want it == 1 (mod 16) so
 // quad q + 1 takes the odd records.  (The old pitch, == 2 mod 8, was conflict-free for the fills and 2-way conflicted on every
 // window read.)
-#ifndef YF_MDW_EPL_ADD
-#define YF_MDW_EPL_ADD 0
-#endif
-// the small head's 1x1 convs (128 output channels) in fp32: per-chunk partial sums (see mdw_kernel, PSUM)
-__host__ __device__ constexpr bool mdw_psum(int n, int wmode) { return n == 128 && wmode == WM_F32; }
 __host__ __device__ constexpr int mdw_epl(int th, int tw, int nwave)
 {
     const int nrp = (th + 4) * (tw + 4), mto = th * tw / 16, mtow = (mto + nwave - 1) / nwave;
     const bool adj = mto % nwave == 0 && mtow > 1 && tw % mtow == 0;
-    return ((nrp + 15) / 16) * 16 + (adj ? 1 : 0) + YF_MDW_EPL_ADD;
+    return ((nrp + 15) / 16) * 16 + (adj ? 1 : 0);
 }
 
 // HM (head mode): 0 = no head conv; 1 = head conv of up to 32 channels (one pair of MFMA column tiles, fragments staged in LDS with the
@@ -109,13 +86,7 @@ __global__ void __launch_bounds__(NWAVE * 64) mdw_kernel(MdwArgs a)
     const int lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
     const TT* __restrict__ src = reinterpret_cast<const TT*>(a.in) + (long)n * a.H * a.W * C;
 
-    MDW_STAMP_DECL
-#ifndef YF_MDW_ROLLED_STAGING
     stage_to_lds<WFLOATS, NTHR>(WL, a.wp);
-#else   // round 2's staging loop (A/B builds only): one exposed L2 round trip per iteration
-    for (int i = threadIdx.x * 4; i < WFLOATS; i += NTHR * 4)
-        *reinterpret_cast<float4*>(&WL[i]) = *reinterpret_cast<const float4*>(a.wp + i);
-#endif
 
     // chunk-invariant addressing of this thread's NLD fill items: item id -> (region pixel, channel quad)
     int goff[NLD];  // frame-relative pixel index, -1 = outside the image (zero fill), -2 = no item
@@ -158,7 +129,6 @@ __global__ void __launch_bounds__(NWAVE * 64) mdw_kernel(MdwArgs a)
         rp0[i] = (oy + 2) * RW + ox + 2;
     }
 
-    MDW_STAMP(0)   // prologue: weight staging requests, addressing, first prefetch
 #pragma unroll 1
     for (int c = 0; c < NCH; ++c) {
         // ---- fill E with this chunk (prefetched), then request the next chunk ----
@@ -167,9 +137,7 @@ __global__ void __launch_bounds__(NWAVE * 64) mdw_kernel(MdwArgs a)
             const int id = threadIdx.x + m * NTHR;
             if (goff[m] != -2) *reinterpret_cast<float4*>(&E[((id & 3) * EPL + (id >> 2)) * 4]) = pf[m];
         }
-        MDW_STAMP(1)   // E fill (waits for the prefetched chunk)
         __syncthreads();
-        MDW_STAMP(2)   // barrier 1
         if (c + 1 < NCH) prefetch(c + 1);
         // ---- depthwise 5x5 of channels 4q..4q+3 at this lane's output pixels (taps outer: one weight read per tap) ----
         const float* wc = WL + c * CHUNK;
@@ -208,7 +176,6 @@ __global__ void __launch_bounds__(NWAVE * 64) mdw_kernel(MdwArgs a)
                 }
             __builtin_amdgcn_sched_barrier(0);
         }
-        MDW_STAMP(3)   // depthwise
         // ---- 1x1 conv: A = relu(d) (k-step j = channel 4q+j), B fragments from the staged stream ----
         if constexpr (X3) {
             f16x4 w2h[NT], w2l[NT];
@@ -286,9 +253,7 @@ __global__ void __launch_bounds__(NWAVE * 64) mdw_kernel(MdwArgs a)
                 }
             }
         }
-        MDW_STAMP(4)   // 1x1 conv MFMAs
         __syncthreads();
-        MDW_STAMP(5)   // barrier 2
     }
 
     // ---- epilogue.  The 1x1 conv ran with its weights as the MFMA's A operand and the depthwise result as B (the same
@@ -463,8 +428,6 @@ __global__ void __launch_bounds__(NWAVE * 64) mdw_kernel(MdwArgs a)
             }
         }
     }
-    MDW_STAMP(6)   // epilogue
-    MDW_STAMP_FLUSH
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -880,8 +843,7 @@ enum { MDW2_ESPLIT_MAX_FRAMES = 9 };
 size_t mdw2_esplit_scratch_floats() { return (size_t)MDW2_ESPLIT_MAX_FRAMES * (6 + 8) * 80 * 128; }
 bool mdw2_esplit_ok(int H, int W, int headn, int Nf, int dtype, const float* scratch)
 {
-    static const bool off = getenv("YF_MRES_SMALL_OFF") != nullptr || getenv("YF_MDW2_ESPLIT_OFF") != nullptr;
-    return !off && scratch && dtype == DT_F32 && H == 8 && W == 10 && headn >= 1 && headn <= 32 && Nf <= MDW2_ESPLIT_MAX_FRAMES;
+    return scratch && dtype == DT_F32 && H == 8 && W == 10 && headn >= 1 && headn <= 32 && Nf <= MDW2_ESPLIT_MAX_FRAMES;
 }
 
 int launch_mdw2(const float* in, const float* wp1, const float* wp2, float* out, int H, int W, int headn, int Nf, hipStream_t s, int dtype, float* scratch)
@@ -920,17 +882,15 @@ static int launch_mdw_t(MdwArgs a, int Nf, hipStream_t s)
     return 0;
 }
 
-#ifndef YF_MDW_LARGE_NW
-#define YF_MDW_LARGE_NW 10
-#endif
+constexpr int MDW_LARGE_NW = 10;
 //      (c, n, head mode, TH, TW, waves)      head mode: 0 none, 1 = up to 32 head channels (the shipped 24), 2 = any width
 #define YF_MDW_SHAPES(MD)                                            \
     MD(96, 128, 0, 8, 10, 5)    /* conv5_3 -> conv5_4            @ H/32 */ \
     MD(128, 128, 1, 8, 10, 5)   /* conv5_5 -> conv5_6 -> head_5  @ H/32 */ \
     MD(128, 128, 2, 8, 10, 5)                                              \
-    MD(96, 96, 0, 16, 20, YF_MDW_LARGE_NW)   /* conv4_1_2 -> conv4_1_3        @ H/16 */ \
-    MD(96, 96, 1, 16, 20, YF_MDW_LARGE_NW)   /* conv4_1_4 -> conv4_1_5 -> head_4      */ \
-    MD(96, 96, 2, 16, 20, YF_MDW_LARGE_NW)
+    MD(96, 96, 0, 16, 20, MDW_LARGE_NW)      /* conv4_1_2 -> conv4_1_3        @ H/16 */ \
+    MD(96, 96, 1, 16, 20, MDW_LARGE_NW)      /* conv4_1_4 -> conv4_1_5 -> head_4      */ \
+    MD(96, 96, 2, 16, 20, MDW_LARGE_NW)
 
 // Small batches: the stride-16 launches own a whole 16x20 frame per workgroup -- at batch 1 ONE CU works for ~30 us.
 // When those tiles would leave more than half of the CUs idle, the same kernel runs on 8x10 tiles with 5 waves (the stride-32 shapes'

@@ -189,7 +189,7 @@ __global__ void __launch_bounds__(256) pw_mfma_kernel(PwArgs a)
 // (measured: 1 workgroup per CU resident, two sequential rounds).
 __device__ __forceinline__ bool v0guard(float v) { return v != 123456.f; }  // DBG: keeps the value alive, never stores
 
-// DBG (tools/kbench.hip only): 1 = no A refill, 2 = no stores
+// DBG (timing builds of the removed tools/kbench.hip): 1 = no A refill, 2 = no stores
 // pw_ws_x3_kernel: the same weight-stationary GEMM for DT_F16X3 (fp32 in HBM, split-operand fp16 MFMAs).  A wave keeps the hi AND
 // lo f16x4 fragments of its units' weights in registers (the same register count as the fp32 fragments); every 16-byte piece of
 // the A ring is split into its fp16 halves once per row tile (ten VALU instructions that run beside the matrix pipe) and feeds
@@ -431,7 +431,7 @@ __global__ void __launch_bounds__(64 * RS * ((((N + 15) / 16) * (OMODE == 2 ? 4 
 
 //      (k1, k2, n, units per wave, row streams, relu, omode)  -- fp32 storage only.  UPW as large as the registers allow: every
 //      wave of a row stream re-reads the same A tile through the texture path (16 B per lane, 16 rows per instruction), and that
-//      path, not the matrix pipe, limits this kernel: conv4_1_1 with 1 / 2 / 3 units per wave runs 67 / 58 / 37 us (tools/kbench ws)
+//      path, not the matrix pipe, limits this kernel: conv4_1_1 with 1 / 2 / 3 units per wave runs 67 / 58 / 37 us (stand-alone benchmark)
 //      last column: workgroups that fit a CU (registers), for the persistent grid
 #define YF_WS_SHAPES(WS)                                                              \
     WS(24, 0, 136, 9, 4, true, 0, 3)    /* conv4_2: all 9 n-tiles per wave, 4 streams  (stride 16) */  \

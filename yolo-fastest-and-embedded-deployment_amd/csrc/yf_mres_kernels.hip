@@ -27,58 +27,13 @@
 
 #include "yf_kernels.h"
 
-#ifndef YF_MRES_DBG
-#define YF_MRES_DBG 0   // tools/kbench.hip only: 1 = one dw window address, 2 / 4 = one k-step in expansion / projection, 8 = one dw tap
-#endif
 
 namespace yf {
 
-// Diagnostic build only (-DYF_MRES_STAMP, tools/kbench.hip mresp): per-phase shader-clock sums of the first ([0..7]) and the last
-// ([8..15]) wave of every workgroup.
-#ifdef YF_MRES_STAMP
-__device__ unsigned long long yf_mres_dbg[16];
-__device__ __forceinline__ unsigned long long mres_clock()
-{
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-#define MRES_STAMP_DECL unsigned long long st_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_t_ = mres_clock();
-#define MRES_STAMP(i) { unsigned long long n_ = mres_clock(); st_[i] += n_ - st_t_; st_t_ = n_; }
-#define MRES_STAMP_FLUSH(NW) if ((threadIdx.x & 63) == 0 && (wave == 0 || wave == NW - 1)) { for (int i_ = 0; i_ < 8; ++i_) atomicAdd(&yf_mres_dbg[(wave ? 8 : 0) + i_], st_[i_]); }
-#else
-#define MRES_STAMP_DECL
-#define MRES_STAMP(i)
-#define MRES_STAMP_FLUSH(NW)
-#endif
 
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-#ifndef YF_RES5_CPP
-#define YF_RES5_CPP 1   // chunks per barrier phase of the stride-32 chain (A/B: 2)
-#endif
-#ifndef YF_MRES_WAVES_ATTR
-#define YF_MRES_WAVES_ATTR   // A/B builds: e.g. -DYF_MRES_WAVES_ATTR='__attribute__((amdgpu_waves_per_eu(6,6)))'
-#endif
-#ifndef YF_MRES_BATCH9_MIN
-#define YF_MRES_BATCH9_MIN 32   // blocks with more expanded channels than this issue the nine depthwise window reads of a pixel together
-#endif
-#ifndef YF_MRES_FRAME
-#define YF_MRES_FRAME 1   // frame-sized tiles of the producer/consumer kernel expand the interior pixels only (0: round 2's behaviour, for A/B builds)
-#endif
-#ifndef YF_MRES_Q4
-#define YF_MRES_Q4 0   // 1: fp32 blocks with 8 output channels project on v_mfma_f32_4x4x1_16B_f32 (no half-empty 16-wide N tile).  Built and measured in
-                       // round 5, OFF: half the matrix-pipe cycles of the projection, but every lane group keeps its own partial sums
-                       // (8 accumulator registers per tile instead of 4): 120 -> 136 VGPRs in the 8/48/8 blocks (one resident workgroup fewer) and
-                       // 78 -> 100 in the stride-2 8/32/8 triple (two instead of three): res3_1 20.3 -> 26.9 us, res3_2 19.4 -> 26.0, conv2_2 triple
-                       // 30.1 -> 37.5 (tools/ops_abn.sh, three interleaved rounds; same heads to rounding, parity tests green)
-#endif
-#ifndef YF_MRES_PK
-#define YF_MRES_PK 1   // depthwise taps as v_pk_fma_f32 (two channels per instruction; same fused multiply-add per element)
-#endif
 // ReLU of a value that is not NaN: one v_max_i32 (fmaxf() on an FMA / MFMA result costs a canonicalising v_add first)
 __device__ __forceinline__ float relu_bits(float x) { return __int_as_float(max(__float_as_int(x), 0)); }
 
@@ -86,23 +41,20 @@ __device__ __forceinline__ float relu_bits(float x) { return __int_as_float(max(
 // ({0-3, 12-15, 20-27}, ...: MI355X_MICROARCH.md, LDS): with the plane pitch a multiple of 16 records the two quads' pixels
 // (r in {0-3, 12-15} of quad q, r in {4-11} of quad q + 1) land on complementary banks.  (The old pitch, == 1 mod 8, was made
 // for 4-byte E writes; the 16-byte record writes of today are conflict-free at any pitch.)
-#ifndef YF_MRES_EPL_PAD
-#define YF_MRES_EPL_PAD 0
-#endif
 // Stride-2 blocks read every second pixel: quad q + 1 then wants the ODD records (pitch == 1 mod 16).
-__host__ __device__ constexpr int mres_epl(int mtr, int s = 1) { return mtr * 16 + (s == 2 ? 1 : 0) + YF_MRES_EPL_PAD; }
+__host__ __device__ constexpr int mres_epl(int mtr, int s = 1) { return mtr * 16 + (s == 2 ? 1 : 0); }
 __host__ __device__ constexpr int mres_ksteps(int K) { return (K / 16) * 4 + ((K % 16) ? 2 : 0); }
 // wmode WM_F16X3: the hi fragments of a matrix are followed by its lo fragments (same layout)
 __host__ __device__ constexpr int mres_chunk_floats(int cin, int cout, int wmode = WM_F32)
 {
     return wmode != WM_F32 ? (wmode == WM_F16X3 ? 2 : 1) * ((mres_ksteps(cin) + 3) / 4) * 128 + 16 + 9 * 16 + 16 +
                                  (wmode == WM_F16X3 ? 2 : 1) * ((cout + 15) / 16) * 128
-                           : mres_ksteps(cin) * 64 + 16 + 9 * 16 + 16 + ((YF_MRES_Q4 && cout == 8) ? 2 * 64 * 4 : 4 * ((cout + 15) / 16) * 64);
+                           : mres_ksteps(cin) * 64 + 16 + 9 * 16 + 16 + 4 * ((cout + 15) / 16) * 64;
 }
 
 // Stage the block's weight stream and the halo'd input tile (zeros outside the image / beyond the region) in LDS.  ALL global loads
 // are issued before the first LDS write: as rolled loops with the load under a bounds branch, every iteration exposed its own
-// L2/HBM round trip -- six to seven serial trips were 40-50 % of a workgroup's life (tools/kbench.hip mresp, -DYF_MRES_STAMP).
+// L2/HBM round trip -- six to seven serial trips were 40-50 % of a workgroup's life (measured with per-phase shader-clock stamps).
 template <int CIN, int S, int RW, int NRP, int MTR, int XP, int WFLOATS, int NTHR, typename T>
 __device__ __forceinline__ void mres_stage(const MresArgs& a, int n, int oy0, int ox0, float* X, float* WL)
 {
@@ -112,7 +64,9 @@ __device__ __forceinline__ void mres_stage(const MresArgs& a, int n, int oy0, in
 #pragma unroll
     for (int i = 0; i < NWI; ++i) {
         const int idx = threadIdx.x + i * NTHR;
-        wv[i] = (YF_MRES_DBG & 32) ? make_float4(0.01f, 0.02f, 0.03f, 0.04f) : *reinterpret_cast<const float4*>(a.wp + 4 * (idx < NW4 ? idx : NW4 - 1));
+        // the explicit copy is a leftover of a removed debug expression (`cond ? constant : load`); without it the compiler schedules the
+        // kernels differently, so it stays until an A/B measures the change (follow-up)
+        wv[i] = float4(*reinterpret_cast<const float4*>(a.wp + 4 * (idx < NW4 ? idx : NW4 - 1)));
     }
 #pragma unroll
     for (int i = 0; i < NXI; ++i) {
@@ -121,7 +75,7 @@ __device__ __forceinline__ void mres_stage(const MresArgs& a, int n, int oy0, in
         const int ry = rp / RW, rx = rp - ry * RW;
         const int iy = oy0 * S - 1 + ry, ix = ox0 * S - 1 + rx;
         const bool ok = rp < NRP && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
-        xv[i] = (YF_MRES_DBG & 16) ? make_float4(0.1f, 0.2f, 0.3f, 0.4f) : ld4<T>(src + (ok ? (iy * a.W + ix) * CIN + c4 * 4 : 0));
+        xv[i] = ld4<T>(src + (ok ? (iy * a.W + ix) * CIN + c4 * 4 : 0));
         if (!ok) xv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
 #pragma unroll
@@ -147,17 +101,14 @@ __host__ __device__ constexpr bool mres_relu_out(int cin, int cexp, int cout, in
 // the step of RW - TW = 2 records at the crossing puts two lane pairs of a ds_read_b128 lane group on the same banks.  Where the
 // E row pitch is 6 (mod 16) records (RW = 22: the 16x20 tiles) an M-tile of 2 columns x 8 rows has all 16 lanes on different
 // record slots: rows advance by 6 (mod 16), each takes two consecutive slots.
-#ifndef YF_MRES_TILE2X8
-#define YF_MRES_TILE2X8 1
-#endif
 template <int TH, int TW, int RW, int S>
 __device__ __forceinline__ void mres_out_px(int mo, int r, int& oy, int& ox)
 {
-    if constexpr (YF_MRES_TILE2X8 && S == 1 && RW % 16 == 6 && TW % 2 == 0 && TH % 8 == 0) {
+    if constexpr (S == 1 && RW % 16 == 6 && TW % 2 == 0 && TH % 8 == 0) {
         const int rb = mo / (TW / 2), cp = mo - rb * (TW / 2);
         oy = rb * 8 + (r >> 1);
         ox = cp * 2 + (r & 1);
-    } else if constexpr (YF_MRES_TILE2X8 && S == 1 && RW % 16 == 12 && TW == 10 && TH == 8) {
+    } else if constexpr (S == 1 && RW % 16 == 12 && TW == 10 && TH == 8) {
         // row pitch 12 (mod 16) records (the 8x10 tiles of stride 32): rows advance by -4, so 4-column x 4-row M-tiles are
         // conflict-free; the last two columns go as one 2 x 8 M-tile (two of its lanes share a slot)
         if (mo < 4) { oy = (mo >> 1) * 4 + (r >> 2); ox = (mo & 1) * 4 + (r & 3); }
@@ -172,7 +123,7 @@ __device__ __forceinline__ void mres_out_px(int mo, int r, int& oy, int& ox)
 // S = 2: the stride-2 triples (pw-expand -> dw3x3 stride 2 -> pw-project, no residual): a.H / a.W are the INPUT dims, the tile
 // is TH x TW OUTPUT pixels and the region (TH - 1) S + 3 rows.
 template <int CIN, int CEXP, int COUT, bool RES, int S, int TH, int TW, int NWAVE, typename T>
-__global__ void __launch_bounds__(NWAVE * 64) YF_MRES_WAVES_ATTR mres_kernel(MresArgs a)
+__global__ void __launch_bounds__(NWAVE * 64) mres_kernel(MresArgs a)
 {
     constexpr int RH = (TH - 1) * S + 3, RW = (TW - 1) * S + 3, NRP = RH * RW;
     constexpr int MTR = (NRP + 15) / 16, MTO = (TH * TW) / 16;
@@ -187,13 +138,7 @@ __global__ void __launch_bounds__(NWAVE * 64) YF_MRES_WAVES_ATTR mres_kernel(Mre
     constexpr int KS1 = mres_ksteps(CIN), NB1 = CIN / 16, NT2 = (COUT + 15) / 16, NCH = (CEXP + 15) / 16;
     constexpr int NK1 = (KS1 + 3) / 4;    // f16 MFMAs per expansion tile
     constexpr int OFF_B1 = H16 ? WM * NK1 * 128 : KS1 * 64, OFF_WD = OFF_B1 + 16, OFF_BD = OFF_WD + 144, OFF_W2 = OFF_BD + 16;
-    // Q4 (round 5): an 8-channel projection fills half of a 16x16x4 MFMA's N tile.  v_mfma_f32_4x4x1_16B_f32 multiplies, in 16 independent
-    // 4x4 blocks, the 4 output channels of lanes 4b .. 4b+3's A registers with the 4 pixels of their B registers at ONE k: with the depthwise
-    // result as B (lane (r, q): channel 4q + j of pixel r) block (q, r / 4) accumulates channels 4h .. 4h+3 of ITS four pixels over the k
-    // values lane group q holds -- two instructions (h = 0, 1) of 8 cycles per k-step instead of one of 32 -- and the four lane groups'
-    // partial sums are added once per tile in the epilogue (k19r_kernel's scheme for conv1_9's channels 16 .. 23).
-    constexpr bool Q4 = YF_MRES_Q4 && !H16 && COUT == 8;
-    constexpr int CHUNK = OFF_W2 + (H16 ? WM * NT2 * 128 : (Q4 ? 2 * 64 * 4 : 4 * NT2 * 64));
+    constexpr int CHUNK = OFF_W2 + (H16 ? WM * NT2 * 128 : 4 * NT2 * 64);
     static_assert((TH * TW) % 16 == 0 && CIN % 8 == 0 && COUT % 4 == 0, "shape");
     static_assert(!RES || (CIN == COUT && S == 1), "residual needs same shape");
     static_assert(CHUNK == mres_chunk_floats(CIN, COUT, wmode_of<T>()), "pack layout");
@@ -211,10 +156,8 @@ __global__ void __launch_bounds__(NWAVE * 64) YF_MRES_WAVES_ATTR mres_kernel(Mre
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
 
-    MRES_STAMP_DECL
     mres_stage<CIN, S, RW, NRP, MTR, XP, WFLOATS, NWAVE * 64, T>(a, n, oy0, ox0, X, WL);
     __syncthreads();
-    MRES_STAMP(0)   // staging + barrier
 
     // ---- expansion A fragments (constant over chunks) and the in-image mask of this lane's 4 C rows ----
     float a1[MTRW][KS1];
@@ -255,20 +198,17 @@ __global__ void __launch_bounds__(NWAVE * 64) YF_MRES_WAVES_ATTR mres_kernel(Mre
     }
     // ---- projection accumulators and the E offsets of this lane's output pixel (as A-fragment row r) ----
     f32x4 acc[MTOW][NT2];
-    f32x4 accq[Q4 ? MTOW : 1][2];   // Q4: channels 4h .. 4h+3 of this lane's pixel, partial over this lane group's k values
     int rp0[MTOW];
 #pragma unroll
     for (int i = 0; i < MTOW; ++i) {
 #pragma unroll
         for (int nt = 0; nt < NT2; ++nt) acc[i][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if constexpr (Q4) { accq[i][0] = f32x4{0.f, 0.f, 0.f, 0.f}; accq[i][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
         const int mo = wave + i * NWAVE;
         int oy, ox;
         mres_out_px<TH, TW, RW, S>(mo < MTO ? mo : 0, r, oy, ox);
         rp0[i] = (oy * S + 1) * RW + ox * S + 1;
     }
 
-    MRES_STAMP(1)   // fragments, offsets
 #pragma unroll 1
     for (int c = 0; c < NCH; ++c) {
         const float* wc = WL + c * CHUNK;
@@ -299,19 +239,13 @@ __global__ void __launch_bounds__(NWAVE * 64) YF_MRES_WAVES_ATTR mres_kernel(Mre
 #pragma unroll
                 for (int nt = 0; nt < NT2; ++nt) w2l[nt] = reinterpret_cast<const f16x4*>(wc + OFF_W2)[(NT2 + nt) * 64 + lane];
             }
-        } else if constexpr (!Q4) {
+        } else {
 #pragma unroll
             for (int j = 0; j < 4; ++j)
 #pragma unroll
                 for (int nt = 0; nt < NT2; ++nt) w2f[j][nt] = wc[OFF_W2 + (j * NT2 + nt) * 64 + lane];
         }
-        float4 wq[2];   // Q4: W2[4h + (r & 3)][chunk channel 4q + j], j = x y z w
-        if constexpr (Q4) {
-            wq[0] = reinterpret_cast<const float4*>(wc + OFF_W2)[lane];
-            wq[1] = reinterpret_cast<const float4*>(wc + OFF_W2)[64 + lane];
-        }
 
-        MRES_STAMP(2)   // chunk weights from LDS
         // ---- expand: E[channels 4q .. 4q+3][pixel mt*16 + r] ----
 #pragma unroll
         for (int i = 0; i < MTRW; ++i) {
@@ -335,7 +269,7 @@ __global__ void __launch_bounds__(NWAVE * 64) YF_MRES_WAVES_ATTR mres_kernel(Mre
                     }
                 } else {
 #pragma unroll
-                    for (int s = 0; s < ((YF_MRES_DBG & 2) ? 1 : KS1); ++s) cf = __builtin_amdgcn_mfma_f32_16x16x4f32(w1f[s], a1[i][s], cf, 0, 0, 0);
+                    for (int s = 0; s < KS1; ++s) cf = __builtin_amdgcn_mfma_f32_16x16x4f32(w1f[s], a1[i][s], cf, 0, 0, 0);
                 }
                 // weights as the A operand: the lane holds channels 4q .. 4q+3 of region pixel mt*16 + r = one E record
                 // ReLU and the zero outside the image in ONE instruction: median(x, 0, lim) with lim = +inf inside, 0 outside
@@ -348,9 +282,7 @@ __global__ void __launch_bounds__(NWAVE * 64) YF_MRES_WAVES_ATTR mres_kernel(Mre
                         st4<T>(reinterpret_cast<T*>(a.out_exp) + (long)n * a.H * a.W * CEXP + eoff[i] + c * 16, ev);
             }
         }
-        MRES_STAMP(3)   // expansion
         __syncthreads();
-        MRES_STAMP(4)   // barrier 1
         // ---- depthwise 3x3 of channels 4q..4q+3 at output pixel r  ==  A fragment of the projection ----
 #pragma unroll
         for (int i = 0; i < MTOW; ++i) {
@@ -361,17 +293,16 @@ __global__ void __launch_bounds__(NWAVE * 64) YF_MRES_WAVES_ATTR mres_kernel(Mre
                 // All nine window reads go out together (left to the scheduler they were split 3 + 1 + 5 with a wait each) ... except in
                 // the smallest block (8/32 stride-2 triple), where three workgroups fit a CU's LDS and the +24 VGPRs of the batch take it
                 // from 74 to 98 registers = from three resident workgroups to two (measured 35 -> 42 us).
-                constexpr bool BATCH9 = CEXP > YF_MRES_BATCH9_MIN;
+                constexpr bool BATCH9 = CEXP > 32;
                 float4 v9[9];
                 if constexpr (BATCH9) {
 #pragma unroll
-                    for (int t = 0; t < 9; ++t) v9[t] = e[((YF_MRES_DBG & 1) ? 0 : (t / 3 - 1) * RW + (t % 3 - 1))];
+                    for (int t = 0; t < 9; ++t) v9[t] = e[(t / 3 - 1) * RW + (t % 3 - 1)];
                     __builtin_amdgcn_sched_barrier(0);
                 }
-#if YF_MRES_PK
                 f32x2 dl = {d[0], d[1]}, dh2 = {d[2], d[3]};
 #pragma unroll
-                for (int t = 0; t < ((YF_MRES_DBG & 8) ? 1 : 9); ++t) {
+                for (int t = 0; t < 9; ++t) {
                     float4 v;
                     if constexpr (BATCH9) v = v9[t]; else v = e[(t / 3 - 1) * RW + (t % 3 - 1)];
                     const float4 w = wd[t];
@@ -379,18 +310,6 @@ __global__ void __launch_bounds__(NWAVE * 64) YF_MRES_WAVES_ATTR mres_kernel(Mre
                     dh2 = __builtin_elementwise_fma(f32x2{v.z, v.w}, f32x2{w.z, w.w}, dh2);
                 }
                 d[0] = dl[0]; d[1] = dl[1]; d[2] = dh2[0]; d[3] = dh2[1];
-#else
-#pragma unroll
-                for (int t = 0; t < ((YF_MRES_DBG & 8) ? 1 : 9); ++t) {
-                    float4 v;
-                    if constexpr (BATCH9) v = v9[t]; else v = e[(t / 3 - 1) * RW + (t % 3 - 1)];
-                    const float4 w = wd[t];
-                    d[0] = fmaf(v.x, w.x, d[0]);
-                    d[1] = fmaf(v.y, w.y, d[1]);
-                    d[2] = fmaf(v.z, w.z, d[2]);
-                    d[3] = fmaf(v.w, w.w, d[3]);
-                }
-#endif
                 if constexpr (X3) {
                     f16x4 dh, dl;
                     split_f16x4(relu_bits(d[0]), relu_bits(d[1]), relu_bits(d[2]), relu_bits(d[3]), dh, dl);
@@ -404,17 +323,12 @@ __global__ void __launch_bounds__(NWAVE * 64) YF_MRES_WAVES_ATTR mres_kernel(Mre
                     const f16x4 dh = f16x4{(half_t)fmaxf(d[0], 0.f), (half_t)fmaxf(d[1], 0.f), (half_t)fmaxf(d[2], 0.f), (half_t)fmaxf(d[3], 0.f)};
 #pragma unroll
                     for (int nt = 0; nt < NT2; ++nt) acc[i][nt] = __builtin_amdgcn_mfma_f32_16x16x16f16(w2h[nt], dh, acc[i][nt], 0, 0, 0);
-                } else if constexpr (Q4) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const float dj = relu_bits(d[j]);
-                        accq[i][0] = __builtin_amdgcn_mfma_f32_4x4x1f32(((const float*)&wq[0])[j], dj, accq[i][0], 0, 0, 0);
-                        accq[i][1] = __builtin_amdgcn_mfma_f32_4x4x1f32(((const float*)&wq[1])[j], dj, accq[i][1], 0, 0, 0);
-                    }
                 } else {
 #pragma unroll
-                    for (int j = 0; j < ((YF_MRES_DBG & 4) ? 1 : 4); ++j) {
-                        const float dj = relu_bits(d[j] + ((YF_MRES_DBG & 4) ? d[1] + d[2] + d[3] : 0.f));
+                    for (int j = 0; j < 4; ++j) {
+                        // + 0.f: leftover of a removed debug expression.  It is a real v_add_f32 per value (-fno-fast-math) that relu_bits
+                        // makes pointless; kept so that the generated code stays the measured one (follow-up: drop it with an A/B)
+                        const float dj = relu_bits(d[j] + 0.f);
 #pragma unroll
                         for (int nt = 0; nt < NT2; ++nt)
                             acc[i][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(w2f[j][nt], dj, acc[i][nt], 0, 0, 0);
@@ -422,9 +336,7 @@ __global__ void __launch_bounds__(NWAVE * 64) YF_MRES_WAVES_ATTR mres_kernel(Mre
                 }
             }
         }
-        MRES_STAMP(5)   // depthwise + projection
         __syncthreads();
-        MRES_STAMP(6)   // barrier 2
     }
 
     // ---- epilogue: + bias (+ residual from X), NHWC store.  The projection ran with the weights as the MFMA's A operand and the
@@ -434,18 +346,6 @@ __global__ void __launch_bounds__(NWAVE * 64) YF_MRES_WAVES_ATTR mres_kernel(Mre
 #pragma unroll
     for (int i = 0; i < MTOW; ++i) {
         const int mo = wave + i * NWAVE;
-        if constexpr (Q4) {   // add the four lane groups' partial sums (every group then holds the totals of its pixel); group q stores channels 4q .. 4q+3
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    float v = accq[i][h][k];
-                    v += __shfl_xor(v, 16);
-                    v += __shfl_xor(v, 32);
-                    accq[i][h][k] = v;
-                }
-            acc[i][0] = q == 0 ? accq[i][0] : accq[i][1];
-        }
         if (!EVEN_O && i == MTOW - 1 && mo >= MTO) continue;
         int oy, ox;
         mres_out_px<TH, TW, RW, S>(mo, r, oy, ox);
@@ -465,8 +365,6 @@ __global__ void __launch_bounds__(NWAVE * 64) YF_MRES_WAVES_ATTR mres_kernel(Mre
             st4<T>(reinterpret_cast<T*>(a.out) + (((long)n * Ho + gy) * Wo + gx) * COUT + col, v);
         }
     }
-    MRES_STAMP(7)   // epilogue
-    MRES_STAMP_FLUSH(NWAVE)
 }
 
 
@@ -764,7 +662,6 @@ __global__ void __launch_bounds__((NWP + NWC) * 64) mres_pc_kernel(MresArgs a)
 #pragma unroll
                         for (int t = 0; t < 9; ++t) v9[t] = e[(t / 3 - 1) * RW + (t % 3 - 1)];
                         __builtin_amdgcn_sched_barrier(0);
-#if YF_MRES_PK
                         f32x2 dl = {d[0], d[1]}, dh2 = {d[2], d[3]};
 #pragma unroll
                         for (int t = 0; t < 9; ++t) {
@@ -773,14 +670,6 @@ __global__ void __launch_bounds__((NWP + NWC) * 64) mres_pc_kernel(MresArgs a)
                             dh2 = __builtin_elementwise_fma(f32x2{v.z, v.w}, f32x2{w.z, w.w}, dh2);
                         }
                         d[0] = dl[0]; d[1] = dl[1]; d[2] = dh2[0]; d[3] = dh2[1];
-#else
-#pragma unroll
-                        for (int t = 0; t < 9; ++t) {
-                            const float4 v = v9[t], w = wd[t];
-                            d[0] = fmaf(v.x, w.x, d[0]); d[1] = fmaf(v.y, w.y, d[1]);
-                            d[2] = fmaf(v.z, w.z, d[2]); d[3] = fmaf(v.w, w.w, d[3]);
-                        }
-#endif
                         if constexpr (X3) {
                             f16x4 dh, dl;
                             split_f16x4(relu_bits(d[0]), relu_bits(d[1]), relu_bits(d[2]), relu_bits(d[3]), dh, dl);
@@ -864,14 +753,12 @@ __global__ void __launch_bounds__((NWP + NWC) * 64) mres_pc_kernel(MresArgs a)
 template <int CIN, int CEXP, int COUT, bool RES, int TH, int TW, int NWP, int NWC, typename T, int POSTN = 0, bool FRAME = false>
 static int launch_mres_pc_t(MresArgs a, int N, hipStream_t s)
 {
-    constexpr int CPP = (CIN == 48 && CEXP == 224) ? YF_RES5_CPP : 1;   // the stride-32 chain has the LDS for 2 x 2 E buffers
+    constexpr int CPP = 1;   // 2 (the stride-32 chain has the LDS for 2 x 2 E buffers) was measured no faster
     a.tiles_y = (a.H + TH - 1) / TH;
     a.tiles_x = (a.W + TW - 1) / TW;
-#if YF_MRES_FRAME
     if constexpr (!FRAME) {   // tile == frame: the interior-only expansion
         if (a.tiles_y == 1 && a.tiles_x == 1) return launch_mres_pc_t<CIN, CEXP, COUT, RES, TH, TW, NWP, NWC, T, POSTN, true>(a, N, s);
     }
-#endif
     constexpr int MTR = ((TH + 2) * (TW + 2) + 15) / 16;
     constexpr size_t lds = ((size_t)MTR * 16 * (CIN + 4) + 2 * CPP * 16 * mres_epl(MTR) +
                             ((((CEXP + 15) / 16) * mres_chunk_floats(CIN, COUT, wmode_of<T>()) + COUT + 3) & ~3)) * sizeof(float);
@@ -917,44 +804,23 @@ static int launch_mres_t(MresArgs a, int N, hipStream_t s)
     return 0;
 }
 
-// producer / consumer wave counts of the two chained shapes (A/B builds: -DYF_RES5_NWP=.. etc.).  Measured with the interior-only
+// producer / consumer wave counts of the two chained shapes.  Measured with the interior-only
 // expansion (tools/ops_abn.sh, us per launch at batch 256): res5 chain (8,5) 82.5 -- the three idle producers still sit in every
 // barrier --, (5,5) 71.9, (5,7) 71.3, (3,5) 69.3 [8 waves = 2 per SIMD], (5,3) / (5,4) 80, 9 or 13 waves with 3 producers > 100
 // (a third wave on one SIMD caps the registers at 168: spills); res4 chain (8,8) 76.7, (4,8) 75.7, (6,8) 79.3, (5,10) 79.7.
-#ifndef YF_RES4_NWP
-#define YF_RES4_NWP 4
-#endif
-#ifndef YF_RES4_NWC
-#define YF_RES4_NWC 8
-#endif
-#ifndef YF_RES5_NWP
-#define YF_RES5_NWP 3
-#endif
-#ifndef YF_RES5_NWC
-#define YF_RES5_NWC 5
-#endif
+constexpr int RES5_NWP = 3, RES5_NWC = 5;
 //      (cin, cexp, cout, residual, stride, TH, TW, producer waves (0 = two-barrier kernel), waves / consumer waves)
 // Producer/consumer pays where one workgroup owns the CU anyway (strides 16, 32); at stride 8 its second E buffer
-// halves the workgroups per CU and it is slower (tools/kbench.hip mrespc).
-// A/B builds (round 6): the stride-8 blocks on the producer/consumer kernel, e.g. -DYF_S8A_NWP=3 -DYF_S8A_NW=5
-#ifndef YF_S8A_NWP
-#define YF_S8A_NWP 0   // res3_1, res3_2, conv3_2 triple (8 -> 48 -> 8 / 16)
-#define YF_S8A_NW 8
-#endif
-#ifndef YF_S8B_NWP
-#define YF_S8B_NWP 0   // res3_3 .. res3_6 (16 -> 96 -> 16)
-#define YF_S8B_NW 8
-#endif
+// halves the workgroups per CU and it is slower (measured with a stand-alone kernel benchmark).
 #define YF_MRES_SHAPES(MR)                                                            \
-    MR(8, 48, 8, true, 1, 16, 20, YF_S8A_NWP, YF_S8A_NW)     /* res3_1, res3_2           @ H/8  */         \
-    MR(8, 48, 16, false, 1, 16, 20, YF_S8A_NWP, YF_S8A_NW)   /* conv3_2/3_3/3_4          @ H/8  */         \
-    MR(16, 96, 16, true, 1, 16, 20, YF_S8B_NWP, YF_S8B_NW)   /* res3_3 .. res3_6         @ H/8  */         \
+    MR(8, 48, 8, true, 1, 16, 20, 0, 8)     /* res3_1, res3_2           @ H/8  */         \
+    MR(8, 48, 16, false, 1, 16, 20, 0, 8)   /* conv3_2/3_3/3_4          @ H/8  */         \
+    MR(16, 96, 16, true, 1, 16, 20, 0, 8)   /* res3_3 .. res3_6         @ H/8  */         \
     MR(16, 96, 24, false, 2, 8, 10, 0, 8)   /* conv3_5/3_6/4_1          H/8 -> H/16 */    \
     MR(8, 32, 8, false, 2, 8, 10, 0, 8)     /* conv2_2/2_3/3_1          H/4 -> H/8  */    \
-    MR(8, 32, 8, true, 1, 16, 20, 0, 8)     /* res2_1, res2_2 @ H/4: planned for DT_F16X3 only (fp32: the VALU block is as fast) */ \
     MR(24, 136, 48, false, 2, 8, 10, 0, 8)  /* conv4_2/4_3/5_1 (+ conv4_2 written) H/16 -> H/32 */ \
-    MR(24, 136, 24, true, 1, 16, 20, YF_RES4_NWP, YF_RES4_NWC)  /* res4_1 .. res4_4         @ H/16 */         \
-    MR(48, 224, 48, true, 1, 8, 10, YF_RES5_NWP, YF_RES5_NWC)   /* res5_1 .. res5_5         @ H/32 */
+    MR(24, 136, 24, true, 1, 16, 20, 4, 8)  /* res4_1 .. res4_4         @ H/16 */         \
+    MR(48, 224, 48, true, 1, 8, 10, RES5_NWP, RES5_NWC)   /* res5_1 .. res5_5         @ H/32 */
 
 template <int CIN, int CEXP, int COUT, bool RES, int S, int TH, int TW, int NWP, int NW, typename T>
 static int launch_mres_any(const MresArgs& a, int N, hipStream_t s)
@@ -998,7 +864,7 @@ __global__ void __launch_bounds__(((TH * TW) / 16) * 64) mres_esplit_kernel(Espl
     constexpr int COUT = CIN, NPX = TH * TW, MT = NPX / 16, NWAVE = MT, RH = TH + 2, RW = TW + 2, XP = CIN + 4;
     constexpr int KS1 = mres_ksteps(CIN), NB1 = CIN / 16, NT2 = COUT / 16, NCH = (CEXP + 15) / 16;
     constexpr int OFF_B1 = KS1 * 64, OFF_WD = OFF_B1 + 16, OFF_BD = OFF_WD + 144, OFF_W2 = OFF_BD + 16, CHUNK = OFF_W2 + 4 * NT2 * 64;
-    constexpr int EPL = ((RH * RW + 15) / 16) * 16 + YF_MRES_EPL_PAD;
+    constexpr int EPL = ((RH * RW + 15) / 16) * 16;
     static_assert(NPX % 16 == 0 && CIN % 16 == 0 && CHUNK == mres_chunk_floats(CIN, COUT, WM_F32), "shape / pack layout");
     __shared__ __attribute__((aligned(16))) float X[NPX * XP];
     __shared__ __attribute__((aligned(16))) float E[4 * EPL * 4];
@@ -1111,8 +977,7 @@ enum { ESPLIT_MAX_FRAMES = 9 };   // N x 14 workgroups stay a small share of the
 size_t mres_esplit_scratch_floats() { return (size_t)ESPLIT_MAX_FRAMES * (2 + 2 * 14) * 80 * 48; }
 static bool mres_esplit_ok(const MresArgs& a, int N, int dtype)
 {
-    static const bool off = getenv("YF_MRES_SMALL_OFF") != nullptr || getenv("YF_MRES_ESPLIT_OFF") != nullptr;
-    return !off && dtype == DT_F32 && a.esplit && a.nblk > 1 && a.H == 8 && a.W == 10 && N <= ESPLIT_MAX_FRAMES;
+    return dtype == DT_F32 && a.esplit && a.nblk > 1 && a.H == 8 && a.W == 10 && N <= ESPLIT_MAX_FRAMES;
 }
 static int launch_res5_esplit(const MresArgs& a, int N, hipStream_t s)
 {
@@ -1132,10 +997,9 @@ static int launch_res5_esplit(const MresArgs& a, int N, hipStream_t s)
 // round between the blocks).  The launch count rises by nblk - 1; measured in DESIGN.md section 4 "Small batches".
 static bool mres_small_batch(int N, int H, int W, int th, int tw)
 {
-    static const bool off = getenv("YF_MRES_SMALL_OFF") != nullptr;   // developer switch (A/B)
     const int n_cu = device_cu_count(current_device());
     const long big_tiles = (long)N * ((H + th - 1) / th) * ((W + tw - 1) / tw);
-    return !off && n_cu > 0 && 2 * big_tiles <= n_cu;
+    return n_cu > 0 && 2 * big_tiles <= n_cu;
 }
 
 template <int CIN, int CEXP, int TH, int TW, int NWP, int NWC, typename T>
@@ -1161,8 +1025,7 @@ int mres_dispatches(int cin, int cexp, int cout, bool res, int stride, int nblk,
 {
     if (dtype != DT_F16 && cin == 24 && cexp == 136 && cout == 24 && res && stride == 1 && nblk > 1 && has_scratch && !has_post && mres_small_batch(N, H, W, 16, 20))
         return nblk;
-    if (esplit && cin == 48 && cexp == 224 && cout == 48 && res && stride == 1 && nblk > 1 && has_scratch && dtype == DT_F32 && H == 8 && W == 10 && N <= ESPLIT_MAX_FRAMES &&
-        !getenv("YF_MRES_SMALL_OFF") && !getenv("YF_MRES_ESPLIT_OFF"))
+    if (esplit && cin == 48 && cexp == 224 && cout == 48 && res && stride == 1 && nblk > 1 && has_scratch && dtype == DT_F32 && H == 8 && W == 10 && N <= ESPLIT_MAX_FRAMES)
         return nblk + 1;
     return 1;
 }
@@ -1186,9 +1049,9 @@ int launch_mres(int cin, int cexp, int cout, bool res, int stride, const MresArg
              : dtype == DT_F16X3 ? launch_mres_t<16, 96, 16, true, 1, 8, 10, 8, x3_t>(a, N, s) : launch_mres_t<16, 96, 16, true, 1, 8, 10, 8, float>(a, N, s);
     if (a.post_w) {
         if (!(cin == 48 && cexp == 224 && cout == 48 && res && stride == 1)) return -5;
-        return dtype == DT_F16 ? launch_mres_pc_t<48, 224, 48, true, 8, 10, YF_RES5_NWP, YF_RES5_NWC, half_t, 96>(a, N, s)
-             : dtype == DT_F16X3 ? launch_mres_pc_t<48, 224, 48, true, 8, 10, YF_RES5_NWP, YF_RES5_NWC, x3_t, 96>(a, N, s)
-                                 : launch_mres_pc_t<48, 224, 48, true, 8, 10, YF_RES5_NWP, YF_RES5_NWC, float, 96>(a, N, s);
+        return dtype == DT_F16 ? launch_mres_pc_t<48, 224, 48, true, 8, 10, RES5_NWP, RES5_NWC, half_t, 96>(a, N, s)
+             : dtype == DT_F16X3 ? launch_mres_pc_t<48, 224, 48, true, 8, 10, RES5_NWP, RES5_NWC, x3_t, 96>(a, N, s)
+                                 : launch_mres_pc_t<48, 224, 48, true, 8, 10, RES5_NWP, RES5_NWC, float, 96>(a, N, s);
     }
 #define MR(ci, ce, co, rs, st, th, tw, np, nw)                                                                    \
     if (cin == ci && cexp == ce && cout == co && res == rs && stride == st)                                       \
@@ -1212,18 +1075,9 @@ bool mres_can_chain(int cin, int cexp, int cout, int H, int W)
 
 bool mres_has_kernel(int cin, int cexp, int cout, bool res, int stride, bool relu_out, int dtype)
 {
-    // the 8/32 residual blocks at stride 4: on fp32 MFMAs this kernel only ties the VALU block kernel (61.5 vs 64 us alone, nothing end
-    // to end); with split-operand fp16 MFMAs, which run beside the depthwise VALU work, it wins
-    if (cin == 8 && cexp == 32 && cout == 8 && res && stride == 1) {
-        // The res2 pair (8 / 32 / 8 at stride 4) stays on the fp32 VALU block kernel in EVERY dtype since round 4: in an f16x3 engine the
-        // split-operand MFMA form spends as much VALU time (depthwise + operand splits + E records: 0.66 of 80 us at 640x512) as the VALU
-        // kernel needs in total (0.72 of 73 us) and is slower alone -- interleaved A/B (tools/res2_ab.sh, three rounds): 640x512 batch 128
-        // 92.1 -> 92.7 k frames/s (one batch at a time 90.5 -> 92.2 k), 320x256 batch 256 363.9 -> 366.9 k (352.8 -> 359.6 k).
-        // YF_RES2_X3=1 (developer switch) restores round 3's choice.
-        static const bool res2_x3 = getenv("YF_RES2_X3") != nullptr;
-        // (fp16 storage, single fp16 MFMAs, no operand splits: 72 us against the VALU kernel's 61 at 640x512 batch 128 -- round 5)
-        return dtype == DT_F16X3 && !relu_out && res2_x3;
-    }
+    // The res2 pair (8 / 32 / 8 at stride 4) has no row here: it runs on the fp32 VALU block kernel in every dtype.  In an f16x3 engine the
+    // split-operand MFMA form spent as much VALU time as the VALU kernel needs in total and was slower (interleaved A/B, 640x512 batch 128:
+    // 92.1 k frames/s against 92.7 k); fp16 storage on single fp16 MFMAs took 72 us against the VALU kernel's 61.
 #define MR(ci, ce, co, rs, st, th, tw, np, nw) \
     if (cin == ci && cexp == ce && cout == co && res == rs && stride == st) return relu_out == mres_relu_out(ci, ce, co, st);
     YF_MRES_SHAPES(MR)
@@ -1288,13 +1142,6 @@ void mres_pack_weights(const float* w1 /*[cin][cexp]*/, const float* b1, const f
                         const float v = w2_at(j, nt, lane);
                         o16[(nt * 64 + lane) * 4 + j] = f32_to_f16_bits(v);
                         if (x3) o16[((NT2 + nt) * 64 + lane) * 4 + j] = f16_lo_bits(v);
-                    }
-        } else if (YF_MRES_Q4 && cout == 8) {   // 4x4x1 form: [h][lane][j] = W2[chunk channel 4q + j][output channel 4h + (lane & 3)]
-            for (int h = 0; h < 2; ++h)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 4; ++j) {
-                        const int ch = 4 * (lane >> 4) + j;
-                        o[(h * 64 + lane) * 4 + j] = ch_ok(ch) ? w2[(size_t)(c * 16 + ch) * cout + 4 * h + (lane & 3)] : 0.f;
                     }
         } else {
             for (int j = 0; j < 4; ++j)

@@ -418,27 +418,24 @@ __global__ void tdw3s2_bwd_data_kernel(const float* __restrict__ dy, const float
 static inline bool tstat_room(TStatPart* st, long count, int C)
 {
     if (!st || !st->part) return false;
-    static const bool off = getenv("YF_TSTAT_OFF") != nullptr;
-    if (off || (size_t)count * C * sizeof(float2) > st->cap_bytes) return false;
+    if ((size_t)count * C * sizeof(float2) > st->cap_bytes) return false;
     st->count = count;
     return true;
 }
 static inline bool tred_room(TBnRed* red, long count, int C)
 {
     if (!red || !red->part || !red->z) return false;
-    static const bool off = getenv("YF_TRED_OFF") != nullptr;
-    if (off || (size_t)count * C * sizeof(float2) > red->cap_bytes) return false;
+    if ((size_t)count * C * sizeof(float2) > red->cap_bytes) return false;
     red->count = count;
     return true;
 }
-static const bool tdw_rows_off = getenv("YF_TDW_ROWS_OFF") != nullptr;
 template <int KS, int S, bool FLIP>
 static void launch_tdw_conv(const float* x, const float* w, float* y, int N, int C, int H, int W, int Ho, int Wo, hipStream_t s, TStatPart* st = nullptr,
                             TBnRed* red = nullptr)
 {
     if constexpr (S == 1) {
         // large maps: 4 rows per thread (see tdw_rows_kernel); the plane must still give a workgroup something to do
-        if (!tdw_rows_off && H % 4 == 0 && (H / 4) * (W / 4) >= 64) {
+        if (H % 4 == 0 && (H / 4) * (W / 4) >= 64) {
             // workgroup = 64 .. 256 threads, whichever leaves the fewest idle (a 32x40 plane is 80 threads' worth: 256 would idle 69 % of them)
             const int count = (H / 4) * (W / 4);
             int bs = 256, waste = (count + 255) / 256 * 256 - count;
@@ -453,7 +450,7 @@ static void launch_tdw_conv(const float* x, const float* w, float* y, int N, int
             hipLaunchKernelGGL((tdw_rows_kernel<KS, FLIP, 4>), dim3(N * C, ny), dim3(bs), 0, s, x, w, y, C, H, W, 0L, sp, ra);
             return;
         }
-        if (!tdw_rows_off && H % 4 == 0 && (long)N * C * (H / 4) * (W / 4) >= 16384) {      // small planes, many of them
+        if (H % 4 == 0 && (long)N * C * (H / 4) * (W / 4) >= 16384) {      // small planes, many of them
             const long total = (long)N * C * (H / 4) * (W / 4);
             hipLaunchKernelGGL((tdw_rows_kernel<KS, FLIP, 4, true>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, w, y, C, H, W, (long)N * C);
             return;

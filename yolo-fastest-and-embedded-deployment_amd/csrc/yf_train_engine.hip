@@ -468,7 +468,7 @@ static int trainer_backward_launches(yf_trainer t, const float* d_x, const float
     PassTimer tm(s);
     // the gradients of a flat parameters()-order buffer (what training.py passes): the split weight-gradient sums of all layers become one
     // launch at the end of the pass.  Pointers that are not laid out that way: every layer sums its own slabs as before.
-    bool flat = getenv("YF_TRAIN_SUM_EACH") == nullptr;
+    bool flat = true;
     for (int i = 1; i < t->n_params && flat; ++i) flat = (const float*)d_grads[i] == (const float*)d_grads[0] + t->param_off[i];
     yf::TSumDefer defer{w.slabs, w.slab_floats, 0, static_cast<float*>(d_grads[0]), 0, {}};
     yf::TSumDefer* dfr = flat ? &defer : nullptr;

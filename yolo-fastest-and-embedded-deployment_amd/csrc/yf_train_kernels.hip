@@ -39,7 +39,6 @@ static void launch_tpw_gemm(const float* x, const float* a, const float* bias, c
     const int wm = tpw_waves_m(M), wq = 4 / wm;
     const unsigned my = (unsigned)((M + 16 * wm - 1) / (16 * wm));
     const long b4 = (Q + 64L * wq - 1) / (64L * wq), b1 = (Q + 16L * wq - 1) / (16L * wq);     // workgroups along the pixels, NT = 4 / 1
-    static const bool old_only = getenv("YF_TPW_OLD") != nullptr;
     const int tiles = (M + 15) / 16;
     int mgroups = (tiles + 3) / 4, mt = (tiles + mgroups - 1) / mgroups;
     while (mt > 1 && (Q + 63) / 64 * mgroups < 512) {                  // few pixels: channel tiles on separate waves (the B re-reads hit L2)
@@ -48,9 +47,8 @@ static void launch_tpw_gemm(const float* x, const float* a, const float* bias, c
     }
     const long wg = (Q + 255) / 256 * mgroups;
     // big A operand and enough pixel blocks per workgroup to pay for staging it: the weight-stationary form
-    static const bool lds_off = getenv("YF_TPW_LDS_OFF") != nullptr;
-    const bool want_stat = st && !bias && !addend && mt <= 2 && HW % 4 == 0 && K % 4 == 0 && Q % 4 == 0 && !old_only;
-    if (!want_stat && !old_only && !lds_off && HW % 4 == 0 && K % 4 == 0 && Q % 4 == 0 && (long)M * K >= 8192 && Q >= 32768) {
+    const bool want_stat = st && !bias && !addend && mt <= 2 && HW % 4 == 0 && K % 4 == 0 && Q % 4 == 0;
+    if (!want_stat && HW % 4 == 0 && K % 4 == 0 && Q % 4 == 0 && (long)M * K >= 8192 && Q >= 32768) {
         int rc = -1;
         if (mt == 1) rc = launch_tpw4_lds<1, false>(x, a, bias, addend, y, Q, HW, M, K, sm, sk, mgroups, 0, s);
         else if (mt == 2) rc = launch_tpw4_lds<2, false>(x, a, bias, addend, y, Q, HW, M, K, sm, sk, mgroups, 0, s);
@@ -58,7 +56,7 @@ static void launch_tpw_gemm(const float* x, const float* a, const float* bias, c
         else rc = launch_tpw4_lds<4, false>(x, a, bias, addend, y, Q, HW, M, K, sm, sk, mgroups, 0, s);
         if (rc == 0) return;
     }
-    if (!old_only && HW % 4 == 0 && K % 4 == 0 && Q % 4 == 0) {
+    if (HW % 4 == 0 && K % 4 == 0 && Q % 4 == 0) {
         float2* sp = (want_stat && tstat_room(st, (Q + 255) / 256 * 4, M)) ? st->part : nullptr;
 #define YF_PW4(MT_) hipLaunchKernelGGL(tpw4_mfma_kernel<MT_>, dim3((unsigned)wg), dim3(256), 0, s, x, a, bias, addend, y, Q, HW, M, K, sm, sk, mgroups, 0, sp)
         if (mt == 1) YF_PW4(1); else if (mt == 2) YF_PW4(2); else if (mt == 3) YF_PW4(3); else YF_PW4(4);
@@ -80,8 +78,7 @@ void launch_tconv_fwd(const float* x, const float* w, const float* bias, float* 
         launch_tpw_gemm(x, w, bias, nullptr, y, (long)N * H * W, (long)H * W, Cout, Cin, (long)Cin, 1L, s, st);
         return;
     }
-    static const bool s2_off = getenv("YF_TCONV3S2_OFF") != nullptr;
-    if (!depthwise && k == 3 && stride == 2 && !s2_off && H % 2 == 0 && W % 8 == 0) {
+    if (!depthwise && k == 3 && stride == 2 && H % 2 == 0 && W % 8 == 0) {
         const long G = (long)N * Ho * (Wo / 4);
         if (Cin == 1 && Cout <= 8) {
             hipLaunchKernelGGL(tconv3s2_c1_kernel<8>, dim3(nblk(G)), dim3(256), 0, s, x, w, bias, y, N, H, W, Cout);
@@ -140,8 +137,7 @@ void launch_tconv_bwd_data(const float* dy, const float* w, float* dx, int N, in
         launch_tpw_gemm(dy, w, nullptr, addend, dx, (long)N * H * W, (long)H * W, Cin, Cout, 1L, (long)Cin, s);
         return;
     }
-    static const bool s2m_off = getenv("YF_TCONV3S2_OFF") != nullptr;
-    if (!depthwise && k == 3 && stride == 2 && H == 2 * Ho && W == 2 * Wo && !s2m_off && Cout % 4 == 0 && Wo % 4 == 0 && Cin <= 32 &&
+    if (!depthwise && k == 3 && stride == 2 && H == 2 * Ho && W == 2 * Wo && Cout % 4 == 0 && Wo % 4 == 0 && Cin <= 32 &&
         (long)N * Ho * (Wo / 4) >= 2048) {
         const dim3 grid((unsigned)(((long)N * Ho * (Wo / 4) + 63) / 64));
         if (Cin <= 16) hipLaunchKernelGGL(tconv3s2_bwd_mfma_kernel<1>, grid, dim3(256), 0, s, dy, w, dx, N, Cin, Cout, Ho, Wo);
@@ -173,8 +169,6 @@ void launch_tconv_bwd_data(const float* dy, const float* w, float* dx, int N, in
 // slice is long enough to deal out
 static inline int twgrad_waves(long workgroups, long q_per)
 {
-    static const int forced = getenv("YF_WGRAD_NW") ? atoi(getenv("YF_WGRAD_NW")) : 0;
-    if (forced == 1 || forced == 4 || forced == 8) return forced;
     if (workgroups * 8 <= 8192 && q_per >= 8 * 64) return 8;
     if (workgroups * 4 <= 8192 && q_per >= 4 * 64) return 4;
     return 1;
@@ -255,8 +249,7 @@ void launch_tconv_bwd_weight(const float* x, const float* dy, float* dw, int N, 
     const int pad = (k - 1) / 2, Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
     const long nw = (long)Cout * (depthwise ? 1 : Cin) * k * k, P = (long)N * Ho * Wo;
     const long fit = scratch ? (long)(scratch_bytes / ((size_t)nw * sizeof(float))) : 0;      // slabs that fit
-    static const bool s2_off = getenv("YF_TCONV3S2_OFF") != nullptr;
-    if (!depthwise && k == 3 && stride == 2 && !s2_off && H % 2 == 0 && W % 8 == 0 && fit >= 1) {
+    if (!depthwise && k == 3 && stride == 2 && H % 2 == 0 && W % 8 == 0 && fit >= 1) {
         const long G = (long)N * Ho * (Wo / 4);
         if (Cin == 1 && Cout <= 8 && G >= 4096) {
             long chunks = G / 2048;                                     // >= 8 groups per thread
@@ -287,8 +280,7 @@ void launch_tconv_bwd_weight(const float* x, const float* dy, float* dw, int N, 
         const int R = Cin * k * k, tiles = ((Cout + 15) / 16) * ((R + 63) / 64);
         // many pixels: 4 waves per workgroup share a slice (added through LDS) rather than 4 slices -- the same waves in flight, a
         // quarter of the slabs to write and to add up afterwards
-        static const bool forced_nw = getenv("YF_WGRAD_NW") != nullptr;
-        const long pw = (!forced_nw && P >= 65536) ? 4 : 1;
+        const long pw = P >= 65536 ? 4 : 1;
         long nsplit = (P + 128 * pw - 1) / (128 * pw);                  // >= 8 MFMA steps per wave ...
         while (nsplit * tiles * pw > 8192 && nsplit > 1) nsplit = (nsplit + 1) / 2;   // ... and a bounded grid
         if (nsplit > 1024) nsplit = 1024;
@@ -310,7 +302,7 @@ void launch_tconv_bwd_weight(const float* x, const float* dy, float* dw, int N, 
     if (depthwise && (k == 3 || k == 5)) {
         long chunks = (P + 2047) / 2048;                                // ~8 pixels per thread
         while (chunks * Cout > 4096 && chunks > 1) chunks = (chunks + 1) / 2;
-        const bool rows = !tdw_rows_off && stride == 1 && W % 4 == 0 && H % 4 == 0 && (long)N * (H / 4) * (W / 4) >= 2048;
+        const bool rows = stride == 1 && W % 4 == 0 && H % 4 == 0 && (long)N * (H / 4) * (W / 4) >= 2048;
         if (rows && (long)N * (H / 4) * (W / 4) / 512 < chunks) chunks = (long)N * (H / 4) * (W / 4) / 512;   // 16 outputs per thread and trip
         if (chunks > fit) chunks = fit < 1 ? 1 : fit;
         float* out = tsum_out(scratch, chunks, nw, dw, defer);
@@ -355,12 +347,11 @@ void launch_tconv_bwd_weight(const float* x, const float* dy, float* dw, int N, 
 bool launch_tpw_bwd_dual(const float* x, const float* dz, const float* w, float* dw, float* dx, const float* addend, int N, int Cin, int H, int W,
                          int Cout, void* scratch, size_t scratch_bytes, hipStream_t s, TSumDefer* defer)
 {
-    static const bool off = getenv("YF_TPW_DUAL_OFF") != nullptr;
     const long HW = (long)H * W, Q = (long)N * HW;
     // up to 2 M pixels per batch (batch 256: strides 4 and up; measured 18.11 -> 17.94 -> 17.80 ms for limits of 128 k / 400 k / 2 M, no
     // further gain without a limit): below that the two kernels mostly wait, and side by side they wait once
-    static const long qmax = getenv("YF_TPW_DUAL_QMAX") ? atol(getenv("YF_TPW_DUAL_QMAX")) : 2000000;
-    if (off || HW % 4 || Cout % 4 || Q > qmax || Q < 256) return false;
+    constexpr long qmax = 2000000;
+    if (HW % 4 || Cout % 4 || Q > qmax || Q < 256) return false;
     const long nw = (long)Cout * Cin;
     const long fit = scratch ? (long)(scratch_bytes / ((size_t)nw * sizeof(float))) : 0;
     // the data gradient's grid (launch_tpw_gemm's choice without the weight-stationary variant)
@@ -389,9 +380,8 @@ bool launch_tpw_bwd_dual(const float* x, const float* dz, const float* w, float*
 }
 void launch_tdeconv_fwd(const float* x, const float* w, float* y, int N, int Cin, int H, int W, int Cout, hipStream_t s)
 {
-    static const bool off = getenv("YF_TDECONV_OLD") != nullptr;
     const long Q = (long)N * H * W, HW = (long)H * W;
-    if (!off && Q >= 256 && HW % 4 == 0 && Cin % 4 == 0) {             // the GEMM form (tpw4_mfma_kernel<.., DECONV>): M = 4 Cout rows
+    if (Q >= 256 && HW % 4 == 0 && Cin % 4 == 0) {             // the GEMM form (tpw4_mfma_kernel<.., DECONV>): M = 4 Cout rows
         const int M = 4 * Cout, tiles = (M + 15) / 16;
         int mgroups = (tiles + 3) / 4, mt = (tiles + mgroups - 1) / mgroups;
         while (mt > 1 && (Q + 63) / 64 * mgroups < 512) { mt = (mt + 1) / 2; mgroups = (tiles + mt - 1) / mt; }
@@ -405,26 +395,18 @@ void launch_tdeconv_fwd(const float* x, const float* w, float* y, int N, int Cin
 }
 void launch_tdeconv_bwd_data(const float* dy, const float* w, float* dx, int N, int Cin, int H, int W, int Cout, hipStream_t s)
 {
-    static const bool off = getenv("YF_TDECONV_OLD") != nullptr;
-    if ((long)N * H * W < (off ? 8192 : 256)) {      // (the old gather GEMM at 16 x 8 x 10 pixels: 134 us against 25 us for this one)
+    if ((long)N * H * W < 256) {
         hipLaunchKernelGGL(tdeconv_bwd_data_kernel, dim3(nblk((long)N * Cin * H * W)), dim3(256), 0, s, dy, w, dx, N, Cin, H, W, Cout);
         return;
     }
-    if (!off) {
-        const long Q = (long)N * H * W;
-        const int tiles = (Cin + 15) / 16;
-        int mgroups = (tiles + 2) / 3, mt = (tiles + mgroups - 1) / mgroups;
-        while (mt > 1 && (Q + 63) / 64 * mgroups < 512) { mt = (mt + 1) / 2; mgroups = (tiles + mt - 1) / mt; }
-        const dim3 grid((unsigned)((Q + 255) / 256 * mgroups));
+    const long Q = (long)N * H * W;
+    const int tiles = (Cin + 15) / 16;
+    int mgroups = (tiles + 2) / 3, mt = (tiles + mgroups - 1) / mgroups;
+    while (mt > 1 && (Q + 63) / 64 * mgroups < 512) { mt = (mt + 1) / 2; mgroups = (tiles + mt - 1) / mt; }
+    const dim3 grid((unsigned)((Q + 255) / 256 * mgroups));
 #define YF_DB(MT_) hipLaunchKernelGGL(tdeconv_bwd_mfma_kernel<MT_>, grid, dim3(256), 0, s, dy, w, dx, Q, H, W, Cin, Cout, mgroups)
-        if (mt == 1) YF_DB(1); else if (mt == 2) YF_DB(2); else YF_DB(3);
+    if (mt == 1) YF_DB(1); else if (mt == 2) YF_DB(2); else YF_DB(3);
 #undef YF_DB
-        return;
-    }
-    // dx[ci][p] = sum over (co, a, b) of dY[co][2 iy + a][2 ix + b] w[ci][co][a][b]: a 2x2 stride-2 pad-0 convolution of dY with the weight
-    // read as [Cin][(co, a, b)] -- the im2col GEMM
-    hipLaunchKernelGGL(tconv_im2col_mfma_kernel<2>, dim3((unsigned)(((long)N * H * W + 63) / 64), (Cin + 63) / 64), dim3(256), 0, s, dy, w,
-                       (const float*)nullptr, dx, N, Cout, 2 * H, 2 * W, H, W, Cin, 2);
 }
 void launch_tdeconv_bwd_weight(const float* x, const float* dy, float* dw, int N, int Cin, int H, int W, int Cout, void* scratch, size_t scratch_bytes,
                                hipStream_t s, TSumDefer* defer)
@@ -476,8 +458,7 @@ static inline int tbn_chunks(int N, int C, long HW, int V, bool flat)
 void launch_tbn_fwd(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var, float* stats, float* y, int N,
                     int C, long HW, int relu, void* scratch, hipStream_t s, const float* residual, const TStatPart* st)
 {
-    static const bool small4_off = getenv("YF_TBN_SMALL4_OFF") != nullptr;
-    if (!small4_off && HW % 4 == 0 && (long)N * HW <= 4096 * 8) {
+    if (HW % 4 == 0 && (long)N * HW <= 4096 * 8) {
         const long P4 = (long)N * HW / 4;
 #define YF_BNF(U_) hipLaunchKernelGGL(tbn_fwd_small4_kernel<U_>, dim3(C), dim3(1024), 0, s, x, gamma, beta, y, N, C, (int)HW, relu, 1e-5f, 0.1f, stats, running_mean, running_var, residual)
         if (P4 <= 1024) YF_BNF(1); else if (P4 <= 2048) YF_BNF(2); else if (P4 <= 4096) YF_BNF(4); else YF_BNF(8);
@@ -489,8 +470,7 @@ void launch_tbn_fwd(const float* x, const float* gamma, const float* beta, float
                            running_var, residual);
         return;
     }
-    static const bool flat_off = getenv("YF_TBN_FLAT_OFF") != nullptr;
-    const bool flat = !flat_off && HW % 4 == 0 && HW % 1024 != 0;      // float4 numbered across the frames (small / ragged planes)
+    const bool flat = HW % 4 == 0 && HW % 1024 != 0;      // float4 numbered across the frames (small / ragged planes)
     const bool parts = st && st->count > 0;                             // the conv left the partial sums: no pass over z for them
     int pchunks = parts ? (int)((st->count + 1023) / 1024) : 0;        // >= 4 pairs per thread
     if (pchunks > 64) pchunks = 64;
@@ -514,8 +494,7 @@ void launch_tbn_fwd(const float* x, const float* gamma, const float* beta, float
 void launch_tbn_bwd(const float* x, const float* dy, const float* stats, const float* gamma, const float* beta, float* dgamma, float* dbeta, float* dx,
                     int N, int C, long HW, int relu, void* scratch, hipStream_t s, const TBnRed* red)
 {
-    static const bool small4_off = getenv("YF_TBN_SMALL4_OFF") != nullptr;
-    if (!small4_off && HW % 4 == 0 && (long)N * HW <= 4096 * 8) {
+    if (HW % 4 == 0 && (long)N * HW <= 4096 * 8) {
         const long P4 = (long)N * HW / 4;
 #define YF_BNB(U_) hipLaunchKernelGGL(tbn_bwd_small4_kernel<U_>, dim3(C), dim3(1024), 0, s, x, dy, stats, gamma, beta, dgamma, dbeta, dx, N, C, (int)HW, relu)
         if (P4 <= 1024) YF_BNB(1); else if (P4 <= 2048) YF_BNB(2); else if (P4 <= 4096) YF_BNB(4); else YF_BNB(8);
@@ -526,8 +505,7 @@ void launch_tbn_bwd(const float* x, const float* dy, const float* stats, const f
         hipLaunchKernelGGL(tbn_bwd_small_kernel, dim3(C), dim3(1024), 0, s, x, dy, stats, gamma, beta, dgamma, dbeta, dx, N, C, (int)HW, relu);
         return;
     }
-    static const bool flat_off = getenv("YF_TBN_FLAT_OFF") != nullptr;
-    const bool flat = !flat_off && HW % 4 == 0 && HW % 1024 != 0;
+    const bool flat = HW % 4 == 0 && HW % 1024 != 0;
     const bool parts = red && red->count > 0;                          // the data-gradient kernel above left the pairs: no reduction pass
     int pchunks = parts ? (int)((red->count + 1023) / 1024) : 0;
     if (pchunks > 64) pchunks = 64;
