@@ -317,6 +317,29 @@ int yf_augment_u8(int device, const uint8_t *d_src, int src_h, int src_w, int sr
  * d_ytab int4 [dst_h] (16 bytes each entry).  One small kernel on `stream`, no allocation or synchronisation. */
 int yf_cv_resize_tables(int device, int src_h, int src_w, int dst_h, int dst_w, void *d_xtab, void *d_ytab, void *stream);
 
+/* Baseline JPEG decoding on the device (csrc/yf_jpeg_kernels.hip): bit for bit what PIL (libjpeg-turbo, ISLOW IDCT, fancy upsampling)
+ * returns for SOF0 / SOF1 8-bit Huffman files with 1 component or 3 (luma sampling 1 or 2 each way, chroma 1 x 1), restart markers and
+ * custom tables allowed, up to 8192 x 8192.
+ * yf_jpeg_pack: host only.  Parses n files (pointer + byte count each) of ONE size and packs descriptors, tables and entropy-coded bytes
+ *   into `host_blob` (caller-owned, `blob_cap` bytes, 256-byte aligned).  host_blob == NULL: only *blob_bytes (and *h, *w) are set.  A file
+ *   outside the supported subset (progressive, lossless, arithmetic, 12-bit, 2 or >= 4 components, other sampling, DNL, several scans) or
+ *   with a broken header returns YF_E_INVALID; yf_last_error_string() names the frame index and the reason.
+ * yf_jpeg_workspace_bytes: device workspace yf_jpeg_decode_u8 needs for that blob.
+ * yf_jpeg_decode_u8: d_blob = a device copy of the blob (256-byte aligned); writes d_bgr uint8 [n, h, w, 3] (cv2.imread's BGR order,
+ *   4-byte aligned) and d_status int32 [n] (0 = decoded; otherwise flags of corrupt entropy data: 1 bad Huffman code, 2 coefficient index
+ *   past 63, 4 data exhausted, 8 restart markers missing or extra; the frame's bytes are then unspecified).  `host_blob` is read for the
+ *   launch shapes only.  One memset and three kernels on `stream`: no allocation, no synchronisation, capturable.
+ * yf_jpeg_frame_info: info[25] = ncomp, colour (0 gray, 1 YCbCr, 2 RGB), MCUs per row, MCU rows, MCUs, blocks per MCU, restart interval,
+ *   then per component (3, zeros past ncomp): h, v, blocks per row, block rows (MCU-padded), downsampled width, downsampled height.
+ * yf_jpeg_huff_lookup: the decoder's lookup of a 16-bit window (code left-aligned) in table `table` (0..3 DC, 4..7 AC) of frame `frame`:
+ *   *length 0 = no code matches. */
+int yf_jpeg_pack(int n, const void *const *files, const size_t *nbytes, void *host_blob, size_t blob_cap, size_t *blob_bytes, int *h, int *w);
+int yf_jpeg_workspace_bytes(const void *host_blob, size_t *bytes);
+int yf_jpeg_decode_u8(int device, const void *host_blob, const void *d_blob, void *d_workspace, size_t ws_bytes, uint8_t *d_bgr, int *d_status,
+                      void *stream);
+int yf_jpeg_frame_info(const void *host_blob, int frame, int *info, int n_info);
+int yf_jpeg_huff_lookup(const void *host_blob, int frame, int table, unsigned bits16, int *length, int *symbol);
+
 /* Introspection used by tests / bench. */
 /* Name ("conv1_8+conv1_9+conv2_1"), layer-granular algorithmic bytes and flops per frame of launch `op` of the
  * current plan (each conv of the op reads its input and writes its output once, + residual read: SURVEY.md 8d). */

@@ -116,6 +116,12 @@ _SIGS = {
     "yf_augment_u8": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p,
                                  _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "yf_cv_resize_tables": (_c.c_int, [_c.c_int] * 5 + [_c.c_void_p] * 3),
+    "yf_jpeg_pack": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int),
+                                _c.POINTER(_c.c_int)]),
+    "yf_jpeg_workspace_bytes": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_size_t)]),
+    "yf_jpeg_decode_u8": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "yf_jpeg_frame_info": (_c.c_int, [_c.c_void_p, _c.c_int, _c.POINTER(_c.c_int), _c.c_int]),
+    "yf_jpeg_huff_lookup": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_uint, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
     "yf_op_dispatches": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(_c.c_int)]),
     "yf_profile_head_offsets": (_c.c_int, [_c.c_void_p, _c.c_int, _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_size_t)]),
 }

@@ -6,11 +6,12 @@ reference's order: blur?, which blur, flip?) -- so `__getitem__` returns the ref
 (channels in cv2.imread's BGR order; gray for a 1-channel net) and float64 (max_boxes, 6) boxes (xc, yc, w, h, cls, 255.0), normalised
 by the CONFIGURED origin_img_shape.  The per-frame pixels -- BGR2GRAY, cv2.resize, cv2.GaussianBlur((7, 7) or (3, 3), 0), np.fliplr --
 are one kernel launch (OpenCV's 8-bit fixed-point arithmetic restated; parity with a real OpenCV build is unpinned).
-Decoding is PIL's (cv2 is not a dependency).  There is no CPU image path: labels work anywhere, images need the GPU.
+Decoding is PIL's (cv2 is not a dependency), or with `decode="device"` the device JPEG decoder's (jpeg.py: the same bytes).  There is no CPU image path: labels work anywhere, images need the GPU.
 
 Additions: `device`, `gray_bits` (OpenCV's 15- or 14-bit BGR2GRAY coefficients, as YoloFastest.gray_bits), `cache="device"` (decoded
 frames kept in GPU memory, one uint8 stack per source size, filled on first access), `class_names` (the reference reads
-config_params["io_params"]["class_names"]) and `__getitems__`, which DataLoader calls with a whole batch of indices: the same draws in
+config_params["io_params"]["class_names"]), `decode="device"` (JPEG decoding on the GPU, csrc/yf_jpeg_kernels.hip: one
+decode call per source size for a batch's frames, or for the frames a batch adds to the cache; the same bytes as PIL's) and `__getitems__`, which DataLoader calls with a whole batch of indices: the same draws in
 index order, ONE launch per source size, float32 device images [N, C, H, W] = collate_fn's `(u8 - 128.0) / 255` bit for bit.
 
 Deviation: the reference cannot return an image without objects -- `np.array([])` is 1-D, so a flip raises IndexError (`labels[:, 1]`,
@@ -57,7 +58,7 @@ class DetectBatch:
 
 class DetectDataset(torch.utils.data.Dataset):
     def __init__(self, input_shape, origin_img_shape, logger, augment=True, aug_params=None, max_boxes=64, val=False, device=None,
-                 gray_bits=15, cache=None, class_names=None):
+                 gray_bits=15, cache=None, class_names=None, decode="host"):
         if aug_params is None:
             aug_params = config_params["augment_params"]
         self.aug_params = aug_params
@@ -73,6 +74,8 @@ class DetectDataset(torch.utils.data.Dataset):
             raise ValueError("gray_bits must be 14 or 15")
         if cache not in (None, "device"):
             raise ValueError('cache must be None or "device"')
+        if decode not in ("host", "device"):
+            raise ValueError('decode must be "host" or "device"')
         self.logger = logger = logger or logging.getLogger(__name__)
         if val:
             logger.info(" Val Datasest Loading..")
@@ -86,6 +89,7 @@ class DetectDataset(torch.utils.data.Dataset):
         self.augment = augment
         self.gray_bits = gray_bits
         self.cache = cache
+        self.decode = decode
         self.classes = list(class_names if class_names is not None else config_params["io_params"]["class_names"])
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
@@ -162,11 +166,48 @@ class DetectDataset(torch.utils.data.Dataset):
         with Image.open(self.img_list[index]) as im:
             rgb = np.asarray(im.convert("RGB"))
         bgr = np.ascontiguousarray(rgb[:, :, ::-1])
-        hw = bgr.shape[:2]
+        self._check_size(index, bgr.shape[:2])
+        return bgr
+
+    def _check_size(self, index, hw):
         if list(self.input_shape[0:2]) == list(self.origin_img_shape[0:2]) and list(hw) != list(self.input_shape[0:2]):
             raise ValueError("%s is %dx%d, but origin_img_shape[:2] == input_shape[:2] = %s: the reference does not resize then and "
                              "would yield a mis-shaped image" % (self.img_list[index], hw[0], hw[1], self.input_shape[0:2]))
-        return bgr
+
+    def _decode_device(self, indices):
+        """decode="device": the frames `indices` in one decode call per source size -> [(indices of the group, uint8 device [n, h, w, 3])]."""
+        from . import jpeg
+        groups = jpeg.decode_files([self.img_list[i] for i in indices], self.device)
+        out = []
+        for g in groups:
+            members = [indices[p] for p in g.positions]
+            for i in members:
+                self._check_size(i, tuple(g.bgr.shape[1:3]))
+            out.append((members, g.bgr))
+        return out
+
+    def _fill_cache(self, indices):
+        """cache="device" with decode="device": the frames of `indices` not cached yet, decoded in one call per size into their stacks."""
+        missing = list(dict.fromkeys(i for i in indices if i not in self._slot))
+        if not missing:
+            return
+        for members, bgr in self._decode_device(missing):
+            hw = tuple(bgr.shape[1:3])
+            ent = self._stacks.get(hw)
+            if ent is None:
+                ent = self._stacks[hw] = [torch.empty((8,) + tuple(bgr.shape[1:]), dtype=torch.uint8, device=self.device), 0]
+            need = ent[1] + len(members)
+            if need > ent[0].shape[0]:
+                cap = ent[0].shape[0]
+                while cap < need:
+                    cap *= 2
+                grown = torch.empty((cap,) + tuple(bgr.shape[1:]), dtype=torch.uint8, device=self.device)
+                grown[:ent[1]].copy_(ent[0][:ent[1]])
+                ent[0] = grown
+            ent[0][ent[1]:need].copy_(bgr)
+            for k, i in enumerate(members):
+                self._slot[i] = (hw, ent[1] + k)
+            ent[1] = need
 
     def _cached(self, index):
         """cache='device': (source size, slot) of frame `index`, decoding and uploading it on first access."""
@@ -208,9 +249,20 @@ class DetectDataset(torch.utils.data.Dataset):
         packed = [int(k) | (int(bool(f)) << 8) for k, f in params]
         groups = {}
         if self.cache == "device":
+            if self.decode == "device":
+                self._fill_cache(indices)
             for pos, i in enumerate(indices):
                 hw, slot = self._cached(i)
                 groups.setdefault(hw, []).append((pos, slot))
+        elif self.decode == "device":
+            frames = {}
+            at = {}
+            for members, bgr in self._decode_device(list(dict.fromkeys(indices))):
+                frames[tuple(bgr.shape[1:3])] = bgr
+                for k, i in enumerate(members):
+                    at[i] = (tuple(bgr.shape[1:3]), k)
+            for pos, i in enumerate(indices):
+                groups.setdefault(at[i][0], []).append((pos, at[i][1]))
         else:
             frames = {}
             for pos, i in enumerate(indices):
@@ -222,6 +274,9 @@ class DetectDataset(torch.utils.data.Dataset):
             pos = [p for p, _ in members]
             if self.cache == "device":
                 stack, n_src = self._stacks[hw][0], self._stacks[hw][1]
+                index = torch.tensor([s for _, s in members], dtype=torch.int32).to(dev)
+            elif self.decode == "device":
+                stack, n_src = frames[hw], frames[hw].shape[0]
                 index = torch.tensor([s for _, s in members], dtype=torch.int32).to(dev)
             else:
                 stack = torch.from_numpy(np.stack(frames[hw])).to(dev)

@@ -5,7 +5,9 @@ Same constructor and `batch_detect(data_path, result_path)`; one log line per im
   * frames are processed `batch_size` at a time (the reference loops one image per iteration, :146);
   * the whole of `__pre_process` behind the file decode runs on the device: cvtColor(BGR2GRAY) + cv2.resize for ANY frame size
     (yf_cv_preprocess_u8: OpenCV's 8-bit arithmetic restated -- include/yolo_fastest_hip.h; exactly 2x = the 2x2 box mean) and (u8-128)/255
-    (yf_preprocess_u8); image decode uses PIL (this image has no cv2) and hands over what cv2.imread would: HWC, BGR;
+    (yf_preprocess_u8); image decode uses PIL (this image has no cv2) and hands over what cv2.imread would: HWC, BGR -- or, with
+    `decode="device"`, the device JPEG decoder (jpeg.py, the same bytes), one decode call per batch and frame size and one
+    device-to-host copy of the decoded batch for the result images;
   * model + post-process are stream-ordered launches (yf_forward, yf_decode_nms); times in the log are
     per-batch wall times divided by the batch size.
 Result writer: `result_<name>` images with the reference's boxes and labels (`plot.plot_one_box`, the
@@ -44,7 +46,10 @@ def preprocess_u8(model, u8, input_shape):
 
 
 class Detect_YOLO():
-    def __init__(self, device, model_path, config_params, logger):
+    def __init__(self, device, model_path, config_params, logger, decode="host"):
+        if decode not in ("host", "device"):
+            raise ValueError('decode must be "host" or "device"')
+        self.decode = decode
         self.model = YoloFastest(config_params["io_params"]).to(device).eval()
         net_param = torch.load(model_path, map_location=device)
         self.model.load_state_dict(net_param)
@@ -70,6 +75,23 @@ class Detect_YOLO():
             raise ValueError("image files decode to 3 channels; feed a %d-channel model through detect_u8" % self.model.input_channel)
         ori = np.asarray(Image.open(path).convert("RGB"))
         return np.ascontiguousarray(ori[:, :, ::-1]), ori
+
+    def _read_bgr_device(self, paths):
+        """decode="device": the files of one batch -> (a uint8 GPU tensor [N, h, w, 3] if all have one size, else a list of [h, w, 3] GPU
+        tensors; the RGB originals for drawing, from one device-to-host copy per frame size)."""
+        from . import jpeg
+        if self.model.input_channel not in (1, 3):
+            raise ValueError("image files decode to 3 channels; feed a %d-channel model through detect_u8" % self.model.input_channel)
+        groups = jpeg.decode_files(paths, self.device)
+        if len(groups) == 1:
+            host = groups[0].bgr.cpu().numpy()
+            return groups[0].bgr, [f[:, :, ::-1] for f in host]
+        frames, oris = [None] * len(paths), [None] * len(paths)
+        for g in groups:
+            host = g.bgr.cpu().numpy()
+            for k, p in enumerate(g.positions):
+                frames[p], oris[p] = g.bgr[k], host[k][:, :, ::-1]
+        return frames, oris
 
     def _pre_process(self, bgr):
         """detect.py:107-127 for a batch: uint8 GPU tensor [N,h,w,3] (BGR, any size) -> float32 [N,C,H,W].  The reference resizes when its
@@ -125,8 +147,17 @@ class Detect_YOLO():
                                  "total time:%.2fms" % (filename, infer_time, post_process_time, total_time))
 
         def load(names):
+            if self.decode == "device":
+                bgrs, oris = self._read_bgr_device([os.path.join(data_path, n) for n in names])
+                return bgrs, oris, torch.is_tensor(bgrs)
             bgrs, oris = zip(*[self._read_bgr(os.path.join(data_path, n)) for n in names])
             return bgrs, oris, len({b.shape for b in bgrs}) == 1
+
+        def frame(b):
+            return b[None] if torch.is_tensor(b) else torch.from_numpy(b[None]).to(self.device)
+
+        def stack(bgrs):
+            return bgrs if torch.is_tensor(bgrs) else torch.from_numpy(np.stack(bgrs)).to(self.device)
 
         if len(batches) > 1 and in_flight > 1:
             from .pipeline import BatchPipeline
@@ -147,9 +178,9 @@ class Detect_YOLO():
                 for names in batches:
                     bgrs, oris, same = load(names)
                     if same:       # cv2.imread-shaped frames of one size: cvtColor + resize + (v - 128) / 255 inside the batch's own stream
-                        x = torch.from_numpy(np.stack(bgrs)).to(self.device)
+                        x = stack(bgrs)
                     else:          # frames of different sizes: the resize brings them to one
-                        x = torch.cat([self._pre_process(torch.from_numpy(b[None]).to(self.device)) for b in bgrs])
+                        x = torch.cat([self._pre_process(frame(b)) for b in bgrs])
                     ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
                     ev[0].record()
 
@@ -169,9 +200,9 @@ class Detect_YOLO():
             for names in batches:
                 bgrs, oris, same = load(names)
                 if same:
-                    x = self._pre_process(torch.from_numpy(np.stack(bgrs)).to(self.device))
+                    x = self._pre_process(stack(bgrs))
                 else:
-                    x = torch.cat([self._pre_process(torch.from_numpy(b[None]).to(self.device)) for b in bgrs])
+                    x = torch.cat([self._pre_process(frame(b)) for b in bgrs])
                 torch.cuda.synchronize(self.device)
                 start_time = time.time()
                 with torch.no_grad():

@@ -1,0 +1,133 @@
+"""Baseline JPEG files decoded on the device (csrc/yf_jpeg_kernels.hip): the bytes `cv2.imread` would return, exactly what
+`np.asarray(PIL.Image.open(path).convert("RGB"))[:, :, ::-1]` gives (libjpeg-turbo's ISLOW IDCT, fancy upsampling and integer colour
+tables, restated bit for bit), as uint8 device tensors [n, h, w, 3] in BGR order.
+
+Supported: SOF0 / SOF1, 8-bit, Huffman coding, 1 component (gray: the value in all three bytes) or 3 (YCbCr or RGB as libjpeg guesses it;
+luma sampling 1 or 2 each way, chroma 1 x 1: 4:4:4, 4:2:2, 4:2:0, 4:4:0), restart markers, custom tables, up to 8192 x 8192.  Anything
+else is refused on the host with a ValueError naming the file (there is no fallback here: the caller picks PIL instead).  Corrupt or
+truncated entropy data raises OSError naming the file, as PIL does for truncated files.  No EXIF orientation is applied (PIL does not
+apply it either)."""
+import ctypes
+import os
+from typing import List, NamedTuple
+
+import torch
+
+from . import _lib
+
+
+class JpegGroup(NamedTuple):
+    """The frames of one size: `bgr` uint8 device [len(positions), h, w, 3]; `positions` their indices in the call's input list."""
+    positions: List[int]
+    bgr: torch.Tensor
+
+
+def _name(item, i):
+    return item if isinstance(item, (str, os.PathLike)) else "<bytes #%d>" % i
+
+
+def _bytes(item):
+    if isinstance(item, (bytes, bytearray, memoryview)):
+        return bytes(item)
+    with open(item, "rb") as f:
+        return f.read()
+
+
+def _pack_call(datas, blob_ptr, blob_cap):
+    n = len(datas)
+    ptrs = (ctypes.c_void_p * n)(*[ctypes.cast(ctypes.c_char_p(d), ctypes.c_void_p) for d in datas])
+    sizes = (ctypes.c_size_t * n)(*[len(d) for d in datas])
+    need, h, w = ctypes.c_size_t(), ctypes.c_int(), ctypes.c_int()
+    rc = _lib.lib().yf_jpeg_pack(n, ptrs, sizes, blob_ptr, blob_cap, ctypes.byref(need), ctypes.byref(h), ctypes.byref(w))
+    return rc, need.value, h.value, w.value
+
+
+def _refusal(rc, names):
+    msg = _lib.lib().yf_last_error_string().decode(errors="replace")
+    if rc == _lib.YF_E_INVALID and msg.startswith("frame "):
+        head, _, reason = msg.partition(": ")
+        i = int(head.split()[1])
+        return ValueError("%s: %s" % (names[i], reason))
+    return _lib.YFError("yolo_fastest_hip error %d: %s" % (rc, msg))
+
+
+def frame_size(data, name="<bytes>"):
+    """(h, w) of one JPEG file's bytes; ValueError if the device decoder does not support it."""
+    rc, _, h, w = _pack_call([data], None, 0)
+    if rc:
+        raise _refusal(rc, [name])
+    return h, w
+
+
+def pack(datas, names=None, pin=True):
+    """The host blob of frames of one size (yf_jpeg_pack) in a (pinned) uint8 CPU tensor -> (blob, h, w)."""
+    names = names or ["<bytes #%d>" % i for i in range(len(datas))]
+    rc, need, h, w = _pack_call(datas, None, 0)
+    if rc:
+        raise _refusal(rc, names)
+    blob = torch.empty(need, dtype=torch.uint8, pin_memory=pin)
+    rc, _, _, _ = _pack_call(datas, ctypes.c_void_p(blob.data_ptr()), need)
+    if rc:
+        raise _refusal(rc, names)
+    return blob, h, w
+
+
+def workspace_bytes(blob):
+    n = ctypes.c_size_t()
+    _lib.check(_lib.lib().yf_jpeg_workspace_bytes(ctypes.c_void_p(blob.data_ptr()), ctypes.byref(n)))
+    return n.value
+
+
+def decode_blob(blob, h, w, device, out=None, status=None, workspace=None):
+    """Stream-ordered decode of a packed blob on `device` (current stream): uploads it without blocking, launches, returns
+    (bgr uint8 [n, h, w, 3], status int32 [n]) without synchronising.  The pinned `blob` must outlive the upload."""
+    device = torch.device(device)
+    n = ctypes.cast(blob.data_ptr(), ctypes.POINTER(ctypes.c_int32))[1]
+    stream = torch.cuda.current_stream(device)
+    d_blob = torch.empty(blob.numel(), dtype=torch.uint8, device=device)
+    d_blob.copy_(blob, non_blocking=True)
+    ws_bytes = workspace_bytes(blob)
+    if workspace is None:
+        workspace = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=device)
+    if out is None:
+        out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=device)
+    if status is None:
+        status = torch.empty((n,), dtype=torch.int32, device=device)
+    _lib.check(_lib.lib().yf_jpeg_decode_u8(device.index, ctypes.c_void_p(blob.data_ptr()), ctypes.c_void_p(d_blob.data_ptr()),
+                                            ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), ctypes.c_void_p(out.data_ptr()),
+                                            ctypes.c_void_p(status.data_ptr()), ctypes.c_void_p(stream.cuda_stream)))
+    return out, status
+
+
+def decode_files(paths_or_bytes, device):
+    """Paths and / or bytes of JPEG files -> [JpegGroup(positions, bgr uint8 device [n_g, h, w, 3])], one group per frame size in order
+    of first appearance, one decode call per group.  Raises ValueError (unsupported file) before any launch and OSError (corrupt or
+    truncated data) after checking the status words."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("JPEG decoding on the device needs a cuda device")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    items = list(paths_or_bytes)
+    datas = [_bytes(x) for x in items]
+    names = [_name(x, i) for i, x in enumerate(items)]
+    order = {}
+    for i, d in enumerate(datas):
+        order.setdefault(frame_size(d, names[i]), []).append(i)
+    groups, statuses, keep = [], [], []
+    for (h, w), pos in order.items():
+        blob, _, _ = pack([datas[i] for i in pos], [names[i] for i in pos])
+        bgr, st = decode_blob(blob, h, w, device)
+        groups.append(JpegGroup(pos, bgr))
+        statuses.append(st)
+        keep.append(blob)
+    if groups:
+        st = torch.cat(statuses).cpu()            # waits for the launches (and so for the pinned blobs' uploads)
+        flat = [i for g in groups for i in g.positions]
+        bad = [(flat[k], int(st[k])) for k in range(len(flat)) if int(st[k]) != 0]
+        if bad:
+            i, s = bad[0]
+            raise OSError("%s: corrupt or truncated JPEG data (decoder status 0x%x)%s"
+                          % (names[i], s, "" if len(bad) == 1 else "; %d more such files in this call" % (len(bad) - 1)))
+    del keep
+    return groups
