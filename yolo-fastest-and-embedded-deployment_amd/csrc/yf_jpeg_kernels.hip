@@ -266,7 +266,8 @@ const char* parse_file(const uint8_t* p, size_t n, Parsed& out)
             break;
         case 0xDC: return "DNL marker is not supported";
         case 0xE0:
-            if (len >= 7 && !memcmp(p + r.i, "JFIF\0", 5)) jfif = true;
+            // libjpeg's examine_app0 needs the 14 bytes of a full JFIF header; a shorter "JFIF\0" segment does not count
+            if (len >= 16 && !memcmp(p + r.i, "JFIF\0", 5)) jfif = true;
             break;
         case 0xEE:
             if (len >= 14 && !memcmp(p + r.i, "Adobe", 5)) { adobe = true; adobe_transform = p[r.i + 11]; }
