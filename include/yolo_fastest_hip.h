@@ -332,13 +332,35 @@ int yf_cv_resize_tables(int device, int src_h, int src_w, int dst_h, int dst_w, 
  * yf_jpeg_frame_info: info[25] = ncomp, colour (0 gray, 1 YCbCr, 2 RGB), MCUs per row, MCU rows, MCUs, blocks per MCU, restart interval,
  *   then per component (3, zeros past ncomp): h, v, blocks per row, block rows (MCU-padded), downsampled width, downsampled height.
  * yf_jpeg_huff_lookup: the decoder's lookup of a 16-bit window (code left-aligned) in table `table` (0..3 DC, 4..7 AC) of frame `frame`:
- *   *length 0 = no code matches. */
+ *   *length 0 = no code matches.
+ *
+ * Progressive files (SOF2, opt-in): 8-bit, Huffman, the same component layouts, at most 256 scans, a complete progression (every
+ * coefficient of every component coded down to Al = 0: libjpeg smooths blocks otherwise and PIL's pixels are then not the IDCT of the
+ * coefficients).  A progressive frame costs more device time than its baseline twin: its scans are serial chains.
+ * yf_jpeg_pack_ex: yf_jpeg_pack with `flags`.  0: exactly yf_jpeg_pack.  YF_JPEG_PROGRESSIVE: SOF2 files are accepted too, baseline
+ *   and progressive files of one size may share a call.  Every SOS and the DHT / DQT / DRI segments between scans are parsed (each scan
+ *   keeps a snapshot of the Huffman tables it names; a component's quantisation table is the one defined when the first scan names it, as
+ *   libjpeg latches it), and the scan script is checked: a malformed or incomplete one is refused with YF_E_INVALID like any other file.
+ *   yf_jpeg_workspace_bytes and yf_jpeg_decode_u8 take either kind of blob (the blob header says which frames are progressive);
+ *   yf_jpeg_decode_u8 then launches jpeg_prog_entropy_kernel for the progressive frames (status flags as above, OR-ed over a frame's
+ *   scans; flag 2 = coefficient index past the scan's band).
+ * yf_jpeg_scan_info: info[12] for scan `scan` (file order) of frame `frame`: scans of the frame (0: a baseline frame, the rest is zero),
+ *   dependency levels, then of the scan: components, component mask (bit c = component c), Ss, Se, Ah, Al, dependency level (1 + the
+ *   highest level of an earlier scan that shares a component and overlaps its band, DC = band 0..0; 0 without one: scans of one level
+ *   are decoded at the same time), offset in the file and length of its entropy-coded bytes, restart interval.
+ * yf_jpeg_huff_lookup_ex: yf_jpeg_huff_lookup in the snapshot that scan `scan` of a progressive frame took of table `table`
+ *   (scan < 0: yf_jpeg_huff_lookup). */
+#define YF_JPEG_PROGRESSIVE 1
 int yf_jpeg_pack(int n, const void *const *files, const size_t *nbytes, void *host_blob, size_t blob_cap, size_t *blob_bytes, int *h, int *w);
 int yf_jpeg_workspace_bytes(const void *host_blob, size_t *bytes);
 int yf_jpeg_decode_u8(int device, const void *host_blob, const void *d_blob, void *d_workspace, size_t ws_bytes, uint8_t *d_bgr, int *d_status,
                       void *stream);
 int yf_jpeg_frame_info(const void *host_blob, int frame, int *info, int n_info);
 int yf_jpeg_huff_lookup(const void *host_blob, int frame, int table, unsigned bits16, int *length, int *symbol);
+int yf_jpeg_pack_ex(int n, const void *const *files, const size_t *nbytes, int flags, void *host_blob, size_t blob_cap, size_t *blob_bytes,
+                    int *h, int *w);
+int yf_jpeg_scan_info(const void *host_blob, int frame, int scan, int *info, int n_info);
+int yf_jpeg_huff_lookup_ex(const void *host_blob, int frame, int scan, int table, unsigned bits16, int *length, int *symbol);
 
 /* Introspection used by tests / bench. */
 /* Name ("conv1_8+conv1_9+conv2_1"), layer-granular algorithmic bytes and flops per frame of launch `op` of the

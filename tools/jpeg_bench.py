@@ -6,6 +6,10 @@
                                                    decode + status check) against PIL on one host thread
     python tools/jpeg_bench.py --decode --profile  the --decode run under `rocprofv3 --kernel-trace --stats` (a child process, a run of its
                                                    own): each kernel's share
+    python tools/jpeg_bench.py --progressive       the same 256 + 256 frames re-saved by Pillow as progressive files (progressive=True): device time
+                                                   of one call, batch-1 latency, end to end against PIL on one host thread on the same
+                                                   files, and the device time of the baseline twins (the same re-save without
+                                                   progressive), all in this run; with --profile each kernel's share
     python tools/jpeg_bench.py --train             train() examples/s at batch 16 (DataLoader + train_step), interleaved over --rounds:
                                                    cache=None decode="device", cache=None decode="host", cache="device\""""
 import argparse
@@ -29,6 +33,7 @@ from yolo_fastest_amd import jpeg, training, validation as val  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--decode", action="store_true")
+ap.add_argument("--progressive", action="store_true")
 ap.add_argument("--profile", action="store_true")
 ap.add_argument("--train", action="store_true")
 ap.add_argument("--reps", type=int, default=20)
@@ -56,8 +61,21 @@ def color420(n):
     return out
 
 
-def device_ms(datas):
-    blob, h, w = jpeg.pack(datas)
+def resaved(datas, quality, **kw):
+    """The files' pixels saved again by Pillow (mode kept)."""
+    from PIL import Image
+    import jpeg_gen as jg
+    out = []
+    for d in datas:
+        b = io.BytesIO()
+        with jg.big_encoder_buffer():
+            Image.open(io.BytesIO(d)).save(b, "JPEG", quality=quality, **kw)
+        out.append(b.getvalue())
+    return out
+
+
+def device_ms(datas, progressive=False):
+    blob, h, w = jpeg.pack(datas, progressive=progressive)
     d_blob = torch.empty(blob.numel(), dtype=torch.uint8, device=dev)
     d_blob.copy_(blob)
     ws = torch.empty(jpeg.workspace_bytes(blob), dtype=torch.uint8, device=dev)
@@ -85,14 +103,14 @@ def device_ms(datas):
     return e0.elapsed_time(e1) / a.reps
 
 
-def end_to_end(datas):
+def end_to_end(datas, progressive=False):
     from PIL import Image
     for _ in range(2):
-        jpeg.decode_files(datas, dev)
+        jpeg.decode_files(datas, dev, progressive=progressive)
     torch.cuda.synchronize()
     t = time.perf_counter()
     for _ in range(3):
-        jpeg.decode_files(datas, dev)
+        jpeg.decode_files(datas, dev, progressive=progressive)
     torch.cuda.synchronize()
     dev_ms = (time.perf_counter() - t) / 3 * 1e3
     t = time.perf_counter()
@@ -119,11 +137,30 @@ def decode_bench():
     return res
 
 
+def progressive_bench():
+    res = {}
+    for name, src, q in (("gray640x512", bundled(20), 90), ("yuv420_640x512_q95", color420(256), 95)):
+        prog = (resaved(src, q, progressive=True) * 13)[:256]
+        twin = (resaved(src, q) * 13)[:256]
+        assert all(b"\xff\xc2" in d[:1024] for d in prog) and not any(b"\xff\xc2" in d[:1024] for d in twin)
+        ms, one = device_ms(prog, True), device_ms(prog[:1], True)
+        tms, tone = device_ms(twin, True), device_ms(twin[:1], True)
+        dms, pms = end_to_end(prog, True)
+        res[name] = {"device_ms_256": round(ms, 4), "device_ms_1": round(one, 4), "twin_device_ms_256": round(tms, 4),
+                     "twin_device_ms_1": round(tone, 4), "end_to_end_ms_256": round(dms, 2), "pil_one_thread_ms_256": round(pms, 2),
+                     "mean_file_bytes": int(np.mean([len(d) for d in prog])), "twin_mean_file_bytes": int(np.mean([len(d) for d in twin]))}
+        print("progressive %s: 256 frames %.4f ms (%.0f frames/s), baseline twins %.4f ms (%.1fx); batch 1 %.4f ms, twin %.4f ms; "
+              "end to end %.2f ms, PIL one thread %.2f ms (%.2fx); mean file %d B, twin %d B"
+              % (name, ms, 256 / ms * 1e3, tms, ms / tms, one, tone, dms, pms, pms / dms, res[name]["mean_file_bytes"],
+                 res[name]["twin_mean_file_bytes"]))
+    return res
+
+
 def profile():
     out = a.out or tempfile.mkdtemp(prefix="jpeg_bench_")
     os.makedirs(out, exist_ok=True)
     cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", out, "-o", "jpeg", "--", sys.executable,
-           os.path.abspath(__file__), "--decode", "--reps", str(a.reps)]
+           os.path.abspath(__file__), "--progressive" if a.progressive else "--decode", "--reps", str(a.reps)]
     subprocess.check_call(cmd)
     for f in glob.glob(os.path.join(out, "**", "*kernel_stats.csv"), recursive=True):
         with open(f) as fh:
@@ -189,8 +226,10 @@ def train_bench():
 
 
 out = {}
-if a.decode and a.profile:
+if (a.decode or a.progressive) and a.profile:
     profile()
+elif a.progressive:
+    out["progressive"] = progressive_bench()
 elif a.decode:
     out["decode"] = decode_bench()
 if a.train:

@@ -10,6 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libyolo_fastest_hip.so")
 ABI_VERSION = 1
 
+YF_JPEG_PROGRESSIVE = 1                            # yf_jpeg_pack_ex flag
 YF_OK, YF_E_INVALID, YF_E_BLOB, YF_E_HIP, YF_E_WORKSPACE, YF_E_NOPROBE = 0, -1, -2, -3, -4, -5
 
 _c = ctypes
@@ -122,6 +123,11 @@ _SIGS = {
     "yf_jpeg_decode_u8": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "yf_jpeg_frame_info": (_c.c_int, [_c.c_void_p, _c.c_int, _c.POINTER(_c.c_int), _c.c_int]),
     "yf_jpeg_huff_lookup": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_uint, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
+    "yf_jpeg_pack_ex": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_size_t, _c.POINTER(_c.c_size_t),
+                                   _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
+    "yf_jpeg_scan_info": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(_c.c_int), _c.c_int]),
+    "yf_jpeg_huff_lookup_ex": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_uint, _c.POINTER(_c.c_int),
+                                          _c.POINTER(_c.c_int)]),
     "yf_op_dispatches": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(_c.c_int)]),
     "yf_profile_head_offsets": (_c.c_int, [_c.c_void_p, _c.c_int, _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_size_t)]),
 }

@@ -11,7 +11,8 @@ Decoding is PIL's (cv2 is not a dependency), or with `decode="device"` the devic
 Additions: `device`, `gray_bits` (OpenCV's 15- or 14-bit BGR2GRAY coefficients, as YoloFastest.gray_bits), `cache="device"` (decoded
 frames kept in GPU memory, one uint8 stack per source size, filled on first access), `class_names` (the reference reads
 config_params["io_params"]["class_names"]), `decode="device"` (JPEG decoding on the GPU, csrc/yf_jpeg_kernels.hip: one
-decode call per source size for a batch's frames, or for the frames a batch adds to the cache; the same bytes as PIL's) and `__getitems__`, which DataLoader calls with a whole batch of indices: the same draws in
+decode call per source size for a batch's frames, or for the frames a batch adds to the cache; the same bytes as PIL's; `progressive=True` also takes progressive files there, which are
+refused otherwise) and `__getitems__`, which DataLoader calls with a whole batch of indices: the same draws in
 index order, ONE launch per source size, float32 device images [N, C, H, W] = collate_fn's `(u8 - 128.0) / 255` bit for bit.
 
 Deviation: the reference cannot return an image without objects -- `np.array([])` is 1-D, so a flip raises IndexError (`labels[:, 1]`,
@@ -58,7 +59,7 @@ class DetectBatch:
 
 class DetectDataset(torch.utils.data.Dataset):
     def __init__(self, input_shape, origin_img_shape, logger, augment=True, aug_params=None, max_boxes=64, val=False, device=None,
-                 gray_bits=15, cache=None, class_names=None, decode="host"):
+                 gray_bits=15, cache=None, class_names=None, decode="host", progressive=False):
         if aug_params is None:
             aug_params = config_params["augment_params"]
         self.aug_params = aug_params
@@ -76,6 +77,8 @@ class DetectDataset(torch.utils.data.Dataset):
             raise ValueError('cache must be None or "device"')
         if decode not in ("host", "device"):
             raise ValueError('decode must be "host" or "device"')
+        if progressive and decode != "device":
+            raise ValueError('progressive=True needs decode="device" (PIL, the host decoder, reads progressive files anyway)')
         self.logger = logger = logger or logging.getLogger(__name__)
         if val:
             logger.info(" Val Datasest Loading..")
@@ -90,6 +93,7 @@ class DetectDataset(torch.utils.data.Dataset):
         self.gray_bits = gray_bits
         self.cache = cache
         self.decode = decode
+        self.progressive = bool(progressive)
         self.classes = list(class_names if class_names is not None else config_params["io_params"]["class_names"])
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
@@ -177,7 +181,7 @@ class DetectDataset(torch.utils.data.Dataset):
     def _decode_device(self, indices):
         """decode="device": the frames `indices` in one decode call per source size -> [(indices of the group, uint8 device [n, h, w, 3])]."""
         from . import jpeg
-        groups = jpeg.decode_files([self.img_list[i] for i in indices], self.device)
+        groups = jpeg.decode_files([self.img_list[i] for i in indices], self.device, progressive=self.progressive)
         out = []
         for g in groups:
             members = [indices[p] for p in g.positions]

@@ -6,7 +6,8 @@ Same constructor and `batch_detect(data_path, result_path)`; one log line per im
   * the whole of `__pre_process` behind the file decode runs on the device: cvtColor(BGR2GRAY) + cv2.resize for ANY frame size
     (yf_cv_preprocess_u8: OpenCV's 8-bit arithmetic restated -- include/yolo_fastest_hip.h; exactly 2x = the 2x2 box mean) and (u8-128)/255
     (yf_preprocess_u8); image decode uses PIL (this image has no cv2) and hands over what cv2.imread would: HWC, BGR -- or, with
-    `decode="device"`, the device JPEG decoder (jpeg.py, the same bytes), one decode call per batch and frame size and one
+    `decode="device"`, the device JPEG decoder (jpeg.py, the same bytes; baseline files, and with `progressive=True` progressive ones
+    too), one decode call per batch and frame size and one
     device-to-host copy of the decoded batch for the result images;
   * model + post-process are stream-ordered launches (yf_forward, yf_decode_nms); times in the log are
     per-batch wall times divided by the batch size.
@@ -46,10 +47,13 @@ def preprocess_u8(model, u8, input_shape):
 
 
 class Detect_YOLO():
-    def __init__(self, device, model_path, config_params, logger, decode="host"):
+    def __init__(self, device, model_path, config_params, logger, decode="host", progressive=False):
         if decode not in ("host", "device"):
             raise ValueError('decode must be "host" or "device"')
+        if progressive and decode != "device":
+            raise ValueError('progressive=True needs decode="device" (PIL, the host decoder, reads progressive files anyway)')
         self.decode = decode
+        self.progressive = bool(progressive)
         self.model = YoloFastest(config_params["io_params"]).to(device).eval()
         net_param = torch.load(model_path, map_location=device)
         self.model.load_state_dict(net_param)
@@ -82,7 +86,7 @@ class Detect_YOLO():
         from . import jpeg
         if self.model.input_channel not in (1, 3):
             raise ValueError("image files decode to 3 channels; feed a %d-channel model through detect_u8" % self.model.input_channel)
-        groups = jpeg.decode_files(paths, self.device)
+        groups = jpeg.decode_files(paths, self.device, progressive=self.progressive)
         if len(groups) == 1:
             host = groups[0].bgr.cpu().numpy()
             return groups[0].bgr, [f[:, :, ::-1] for f in host]

@@ -1,4 +1,4 @@
-"""Baseline JPEG files decoded on the device (csrc/yf_jpeg_kernels.hip): the bytes `cv2.imread` would return, exactly what
+"""Baseline and, opt-in, progressive JPEG files decoded on the device (csrc/yf_jpeg_kernels.hip): the bytes `cv2.imread` would return, exactly what
 `np.asarray(PIL.Image.open(path).convert("RGB"))[:, :, ::-1]` gives (libjpeg-turbo's ISLOW IDCT, fancy upsampling and integer colour
 tables, restated bit for bit), as uint8 device tensors [n, h, w, 3] in BGR order.
 
@@ -6,7 +6,12 @@ Supported: SOF0 / SOF1, 8-bit, Huffman coding, 1 component (gray: the value in a
 luma sampling 1 or 2 each way, chroma 1 x 1: 4:4:4, 4:2:2, 4:2:0, 4:4:0), restart markers, custom tables, up to 8192 x 8192.  Anything
 else is refused on the host with a ValueError naming the file (there is no fallback here: the caller picks PIL instead).  Corrupt or
 truncated entropy data raises OSError naming the file, as PIL does for truncated files.  No EXIF orientation is applied (PIL does not
-apply it either)."""
+apply it either).
+
+`progressive=True` (frame_size, pack, decode_files) also takes SOF2 files: 8-bit, Huffman, the same layouts, at most 256 scans, and a
+complete progression (every coefficient coded down to Al = 0; libjpeg smooths the blocks of an incomplete one, so such a file is
+refused).  Baseline files decode to the same bytes through the same kernels with or without the flag.  It is opt-in because a progressive
+frame costs more device time than its baseline twin: its scans are serial chains."""
 import ctypes
 import os
 from typing import List, NamedTuple
@@ -33,12 +38,16 @@ def _bytes(item):
         return f.read()
 
 
-def _pack_call(datas, blob_ptr, blob_cap):
+def _pack_call(datas, blob_ptr, blob_cap, progressive=False):
     n = len(datas)
     ptrs = (ctypes.c_void_p * n)(*[ctypes.cast(ctypes.c_char_p(d), ctypes.c_void_p) for d in datas])
     sizes = (ctypes.c_size_t * n)(*[len(d) for d in datas])
     need, h, w = ctypes.c_size_t(), ctypes.c_int(), ctypes.c_int()
-    rc = _lib.lib().yf_jpeg_pack(n, ptrs, sizes, blob_ptr, blob_cap, ctypes.byref(need), ctypes.byref(h), ctypes.byref(w))
+    if progressive:
+        rc = _lib.lib().yf_jpeg_pack_ex(n, ptrs, sizes, _lib.YF_JPEG_PROGRESSIVE, blob_ptr, blob_cap, ctypes.byref(need), ctypes.byref(h),
+                                        ctypes.byref(w))
+    else:
+        rc = _lib.lib().yf_jpeg_pack(n, ptrs, sizes, blob_ptr, blob_cap, ctypes.byref(need), ctypes.byref(h), ctypes.byref(w))
     return rc, need.value, h.value, w.value
 
 
@@ -51,22 +60,24 @@ def _refusal(rc, names):
     return _lib.YFError("yolo_fastest_hip error %d: %s" % (rc, msg))
 
 
-def frame_size(data, name="<bytes>"):
-    """(h, w) of one JPEG file's bytes; ValueError if the device decoder does not support it."""
-    rc, _, h, w = _pack_call([data], None, 0)
+def frame_size(data, name="<bytes>", progressive=False):
+    """(h, w) of one JPEG file's bytes; ValueError if the device decoder does not support it (progressive files: only with
+    `progressive=True`)."""
+    rc, _, h, w = _pack_call([data], None, 0, progressive)
     if rc:
         raise _refusal(rc, [name])
     return h, w
 
 
-def pack(datas, names=None, pin=True):
-    """The host blob of frames of one size (yf_jpeg_pack) in a (pinned) uint8 CPU tensor -> (blob, h, w)."""
+def pack(datas, names=None, pin=True, progressive=False):
+    """The host blob of frames of one size (yf_jpeg_pack, or yf_jpeg_pack_ex with YF_JPEG_PROGRESSIVE) in a (pinned) uint8 CPU tensor
+    -> (blob, h, w)."""
     names = names or ["<bytes #%d>" % i for i in range(len(datas))]
-    rc, need, h, w = _pack_call(datas, None, 0)
+    rc, need, h, w = _pack_call(datas, None, 0, progressive)
     if rc:
         raise _refusal(rc, names)
     blob = torch.empty(need, dtype=torch.uint8, pin_memory=pin)
-    rc, _, _, _ = _pack_call(datas, ctypes.c_void_p(blob.data_ptr()), need)
+    rc, _, _, _ = _pack_call(datas, ctypes.c_void_p(blob.data_ptr()), need, progressive)
     if rc:
         raise _refusal(rc, names)
     return blob, h, w
@@ -99,10 +110,19 @@ def decode_blob(blob, h, w, device, out=None, status=None, workspace=None):
     return out, status
 
 
-def decode_files(paths_or_bytes, device):
+def scan_info(blob, frame=0, scan=0):
+    """yf_jpeg_scan_info as a dict: scans and levels of the frame (scans 0: a baseline frame) and scan `scan` (file order)."""
+    a = (ctypes.c_int * 12)()
+    _lib.check(_lib.lib().yf_jpeg_scan_info(ctypes.c_void_p(blob.data_ptr()), frame, scan, a, 12))
+    keys = ("scans", "levels", "ncomp", "comp_mask", "ss", "se", "ah", "al", "level", "offset", "length", "ri")
+    return dict(zip(keys, a))
+
+
+def decode_files(paths_or_bytes, device, progressive=False):
     """Paths and / or bytes of JPEG files -> [JpegGroup(positions, bgr uint8 device [n_g, h, w, 3])], one group per frame size in order
     of first appearance, one decode call per group.  Raises ValueError (unsupported file) before any launch and OSError (corrupt or
-    truncated data) after checking the status words."""
+    truncated data) after checking the status words.  `progressive=True`: progressive files are decoded too (a size's group may mix
+    kinds); without it they are refused."""
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError("JPEG decoding on the device needs a cuda device")
@@ -113,10 +133,10 @@ def decode_files(paths_or_bytes, device):
     names = [_name(x, i) for i, x in enumerate(items)]
     order = {}
     for i, d in enumerate(datas):
-        order.setdefault(frame_size(d, names[i]), []).append(i)
+        order.setdefault(frame_size(d, names[i], progressive), []).append(i)
     groups, statuses, keep = [], [], []
     for (h, w), pos in order.items():
-        blob, _, _ = pack([datas[i] for i in pos], [names[i] for i in pos])
+        blob, _, _ = pack([datas[i] for i in pos], [names[i] for i in pos], progressive=progressive)
         bgr, st = decode_blob(blob, h, w, device)
         groups.append(JpegGroup(pos, bgr))
         statuses.append(st)
