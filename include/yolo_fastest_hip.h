@@ -362,6 +362,32 @@ int yf_jpeg_pack_ex(int n, const void *const *files, const size_t *nbytes, int f
 int yf_jpeg_scan_info(const void *host_blob, int frame, int scan, int *info, int n_info);
 int yf_jpeg_huff_lookup_ex(const void *host_blob, int frame, int scan, int table, unsigned bits16, int *length, int *symbol);
 
+/* Baseline JPEG encoding on the device (csrc/yf_jpeg_enc_kernels.hip): byte for byte the file PIL (libjpeg-turbo) writes for
+ * Image.save(f, "JPEG", quality=q, subsampling=s) without optimize / progressive: Annex K Huffman tables, no restart markers.
+ * yf_jpeg_enc_setup: host only.  The header libjpeg writes, the scaled quantisation tables and the geometry for frames of h x w
+ *   (1 .. 8192 each) with `channels` 1 (gray) or 3, `quality` 1 .. 100 and `subsampling` 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0) (PIL's numbers;
+ *   ignored for gray), written to host_blob (call with host_blob = NULL to get the size).  YF_E_INVALID for anything else and for frames
+ *   whose worst-case entropy-coded stream would exceed 2^31 bits (bit offsets are 32-bit).
+ * yf_jpeg_enc_info: info[10] = h, w, channels, luma h and v sampling, quality, header bytes, blocks per frame, blocks per MCU, blob bytes;
+ *   header (up to 640 bytes), divisors [2][64] (8 * q, natural order) and reciprocals [2][64] where the pointers are not NULL.
+ * yf_jpeg_enc_workspace_bytes: device workspace yf_jpeg_encode_u8 needs for n frames (worst-case code lengths: about 5 bytes per sample).
+ * yf_jpeg_encode_u8: d_frames uint8 [n, h, w, 3] (bgr = 1: in BGR order as the decoder writes them, 0: RGB) or [n, h, w]; writes frame
+ *   f's complete file to d_out + f * stride, its byte count to d_lengths[f] and 0 to d_status[f].  A file that does not fit `stride`
+ *   bytes: d_status[f] = 1, d_lengths[f] = the stride it needs, and no byte of its slot is written.  Stream-ordered, no allocation, no
+ *   synchronisation, capturable; the blob is read on the host during the call only (it travels as a launch argument).
+ * yf_draw_boxes_u8: plot_one_box (plot.py) for every record, in place on d_frames uint8 [n, h, w, 3].  d_rec_begin int32 [n + 1]: frame
+ *   f applies records [d_rec_begin[f], d_rec_begin[f + 1]) in order.  A record is 32 int32: five rectangles (x0, y0, x1, y1) inclusive and
+ *   clipped to the frame (x1 < x0: none), the colour and the text ink (byte k = channel k in the frames' memory order), the label mask's
+ *   x, y, width, height and offset into d_atlas (width 0: none), padding.  The mask is blended as PIL blends text:
+ *   t = d * (255 - m) + ink * m + 128, ((t >> 8) + t) >> 8. */
+int yf_jpeg_enc_setup(int h, int w, int channels, int quality, int subsampling, void *host_blob, size_t blob_cap, size_t *blob_bytes);
+int yf_jpeg_enc_info(const void *host_blob, int *info, int n_info, uint8_t *header, uint16_t *divisors, uint32_t *reciprocals);
+int yf_jpeg_enc_workspace_bytes(const void *host_blob, int n, size_t *bytes);
+int yf_jpeg_encode_u8(int device, const void *host_blob, const uint8_t *d_frames, int n, int bgr, void *d_workspace, size_t ws_bytes,
+                      uint8_t *d_out, size_t stride, int *d_lengths, int *d_status, void *stream);
+int yf_draw_boxes_u8(int device, uint8_t *d_frames, int n, int h, int w, const int *d_rec_begin, const int *d_records, const uint8_t *d_atlas,
+                     void *stream);
+
 /* Introspection used by tests / bench. */
 /* Name ("conv1_8+conv1_9+conv2_1"), layer-granular algorithmic bytes and flops per frame of launch `op` of the
  * current plan (each conv of the op reads its input and writes its output once, + residual read: SURVEY.md 8d). */

@@ -11,7 +11,13 @@
                                                    files, and the device time of the baseline twins (the same re-save without
                                                    progressive), all in this run; with --profile each kernel's share
     python tools/jpeg_bench.py --train             train() examples/s at batch 16 (DataLoader + train_step), interleaved over --rounds:
-                                                   cache=None decode="device", cache=None decode="host", cache="device\""""
+                                                   cache=None decode="device", cache=None decode="host", cache="device"
+    python tools/jpeg_bench.py --encode            the result writer on the device (csrc/yf_jpeg_enc_kernels.hip): device time of one draw and of one
+                                                   encode call for 256 frames (bundled 640x512, generated textured 640x512 and 480x640; quality 95,
+                                                   4:2:0), batch-1 latency, end to end from device frames to bytes on the host against PIL on one
+                                                   host thread on the same frames, the baseline decode time of the files PIL writes for those frames,
+                                                   and batch_detect wall time per image over 256 files for the four combinations of decode and write,
+                                                   --rounds interleaved rounds after one untimed round"""
 import argparse
 import csv
 import glob
@@ -36,6 +42,7 @@ ap.add_argument("--decode", action="store_true")
 ap.add_argument("--progressive", action="store_true")
 ap.add_argument("--profile", action="store_true")
 ap.add_argument("--train", action="store_true")
+ap.add_argument("--encode", action="store_true")
 ap.add_argument("--reps", type=int, default=20)
 ap.add_argument("--steps", type=int, default=30)
 ap.add_argument("--rounds", type=int, default=3)
@@ -225,8 +232,127 @@ def train_bench():
     return {n: float(np.median(v)) for n, v in res.items()}
 
 
+def timed(call, reps):
+    for _ in range(3):
+        call()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        call()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def encode_bench():
+    import logging
+    import shutil
+    from PIL import Image
+    import jpeg_gen as jg
+    from yolo_fastest_amd import plot
+    res = {}
+    rng = np.random.default_rng(0)
+
+    def textured(w, h):
+        out = []
+        for _ in range(256):
+            t = jg.image("smooth", w, h, rng)
+            out.append(np.clip(t.astype(int) + rng.integers(-24, 25, t.shape), 0, 255).astype(np.uint8))
+        return out
+    sets = {"bundled640x512": [np.asarray(Image.open(io.BytesIO(d)).convert("RGB")) for d in bundled(256)],
+            "textured640x512": textured(640, 512), "textured480x640": textured(480, 640)}
+    for name, rgb in sets.items():
+        h, w = rgb[0].shape[:2]
+        frames = torch.from_numpy(np.stack(rgb)).to(dev)
+        s = jpeg.enc_setup(h, w, 3, 95, "4:2:0")
+        ws = torch.empty(jpeg.enc_workspace_bytes(s, 256), dtype=torch.uint8, device=dev)
+        out_ = torch.empty((256, h * w * 3 + 1024), dtype=torch.uint8, device=dev)
+        ln, st = torch.empty(256, dtype=torch.int32, device=dev), torch.empty(256, dtype=torch.int32, device=dev)
+        enc = timed(lambda: jpeg.encode_batch(frames, order="rgb", setup=s, workspace=ws, out=out_, lengths=ln, status=st), a.reps)
+        assert not st.cpu().numpy().any()
+        one = timed(lambda: jpeg.encode_batch(frames[:1], order="rgb", setup=s, workspace=ws, out=out_[:1], lengths=ln[:1], status=st[:1]), a.reps)
+        # four boxes with labels per frame (the bundled frames carry 0..3 detections), and the dense configuration: 260 per frame
+        row = {}
+        for tag, k in (("draw_ms_256_4_boxes", 4), ("draw_ms_256_260_boxes", 260)):
+            boxes = [[[int(x), int(y), int(x) + 90, int(y) + 70] for x, y in zip(rng.integers(0, w - 90, k), rng.integers(30, h - 70, k))]
+                     for _ in range(256)]
+            labels = [["cloud %.2f" % (j % 101 / 100) for j in range(k)] for _ in range(256)]
+            colors = [[[106, 90, 205]] * k for _ in range(256)]
+            cache = {}
+            scratch = frames.clone()
+            t = time.perf_counter()
+            plot.draw_boxes_device(scratch, boxes, labels, colors, 3, "rgb", cache)
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            plot.draw_boxes_device(scratch, boxes, labels, colors, 3, "rgb", cache)
+            torch.cuda.synchronize()
+            row[tag.replace("draw_ms", "draw_call_wall_ms")] = round((time.perf_counter() - t) * 1e3, 3)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            plot.draw_boxes_device(scratch, boxes, labels, colors, 3, "rgb", cache)
+            e1.record()
+            torch.cuda.synchronize()
+            row[tag] = round(e0.elapsed_time(e1), 4)     # includes the upload of the records: one call as the driver issues it
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        for _ in range(3):
+            files = jpeg.encode_frames(frames, order="rgb")
+        e2e = (time.perf_counter() - t) / 3 * 1e3
+        t = time.perf_counter()
+        pil = []
+        for f in rgb:
+            b = io.BytesIO()
+            Image.fromarray(f).save(b, "JPEG", quality=95)
+            pil.append(b.getvalue())
+        pil_ms = (time.perf_counter() - t) * 1e3
+        assert files == pil, "device bytes differ from PIL's"
+        dec = device_ms(pil)
+        row.update(encode_ms_256=round(enc, 4), frames_per_s_256=round(256 / enc * 1e3), encode_ms_1=round(one, 4), end_to_end_ms_256=round(e2e, 2),
+                   pil_one_thread_ms_256=round(pil_ms, 2), decode_ms_256_same_files=round(dec, 4), encode_below_decode=bool(enc < dec),
+                   mean_file_bytes=int(np.mean([len(d) for d in pil])))
+        res[name] = row
+        print(name, json.dumps(row))
+        del frames, ws, out_
+    # batch_detect over 256 files of 640x512, the four combinations, interleaved
+    tmp = tempfile.mkdtemp(prefix="yf_encode_bench_")
+    data, result = os.path.join(tmp, "data"), os.path.join(tmp, "result")
+    os.makedirs(data)
+    names = sorted(os.listdir(BUNDLED))
+    for i in range(256):
+        shutil.copy(os.path.join(BUNDLED, names[i % len(names)]), os.path.join(data, "%03d_%s" % (i, names[i % len(names)])))
+    logger = logging.getLogger("jpeg-bench-encode")
+    logger.setLevel(logging.WARNING)
+    wpath = os.path.join(ROOT, "yolo-fastest-and-embedded-deployment_amd", "assets", "weights", "yolo_fastest_256x320_epoch28.pth")
+    combos = [(d, w_) for d in ("device", "host") for w_ in ("device", "host")]
+    dets = {c: yf.Detect_YOLO(dev, wpath, {"io_params": yf.io_params_for(256)}, logger, decode=c[0], write=c[1]) for c in combos}
+    times = {c: [] for c in combos}
+    for rnd in range(a.rounds + 1):
+        for c in combos:
+            shutil.rmtree(result, ignore_errors=True)
+            os.makedirs(result)
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            dets[c].batch_detect(data, result, batch_size=64, in_flight=2)
+            torch.cuda.synchronize()
+            if rnd:
+                times[c].append((time.perf_counter() - t) / 256 * 1e3)
+            assert len(os.listdir(result)) == 256
+    shutil.rmtree(tmp, ignore_errors=True)
+    bd = {"decode=%s,write=%s" % c: {"ms_per_image_rounds": [round(v, 4) for v in times[c]]} for c in combos}
+    dd, dh = times[("device", "device")], times[("device", "host")]
+    bd["claim"] = {"device_writer_slowest_ms": round(max(dd), 4), "host_writer_fastest_ms": round(min(dh), 4), "met": bool(max(dd) < min(dh)),
+                   "ratio_host_over_device_medians": round(float(np.median(dh) / np.median(dd)), 2)}
+    res["batch_detect_256_files_640x512_batch_64"] = bd
+    print(json.dumps(bd))
+    return res
+
+
 out = {}
-if (a.decode or a.progressive) and a.profile:
+if a.encode:
+    out["encode"] = encode_bench()
+elif (a.decode or a.progressive) and a.profile:
     profile()
 elif a.progressive:
     out["progressive"] = progressive_bench()

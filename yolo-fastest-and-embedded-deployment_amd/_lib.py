@@ -128,6 +128,12 @@ _SIGS = {
     "yf_jpeg_scan_info": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(_c.c_int), _c.c_int]),
     "yf_jpeg_huff_lookup_ex": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_uint, _c.POINTER(_c.c_int),
                                           _c.POINTER(_c.c_int)]),
+    "yf_jpeg_enc_setup": (_c.c_int, [_c.c_int] * 5 + [_c.c_void_p, _c.c_size_t, _c.POINTER(_c.c_size_t)]),
+    "yf_jpeg_enc_info": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_int), _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "yf_jpeg_enc_workspace_bytes": (_c.c_int, [_c.c_void_p, _c.c_int, _c.POINTER(_c.c_size_t)]),
+    "yf_jpeg_encode_u8": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_size_t,
+                                     _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "yf_draw_boxes_u8": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "yf_op_dispatches": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(_c.c_int)]),
     "yf_profile_head_offsets": (_c.c_int, [_c.c_void_p, _c.c_int, _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_size_t)]),
 }

@@ -13,6 +13,8 @@ Same constructor and `batch_detect(data_path, result_path)`; one log line per im
     per-batch wall times divided by the batch size.
 Result writer: `result_<name>` images with the reference's boxes and labels (`plot.plot_one_box`, the
 reference's general.py:56-67 without cv2) and the reference's log lines; `self.last_labels` keeps the label strings per image.
+`write="device"` (opt-in) draws and JPEG-encodes the result images on the device instead (plot.draw_boxes_device, jpeg.encode_batch): the
+same files byte for byte, the frames never leave the GPU, and a batch is encoded while the host prepares the next one.
 """
 import ctypes
 import os
@@ -47,9 +49,14 @@ def preprocess_u8(model, u8, input_shape):
 
 
 class Detect_YOLO():
-    def __init__(self, device, model_path, config_params, logger, decode="host", progressive=False):
+    def __init__(self, device, model_path, config_params, logger, decode="host", progressive=False, write="host"):
         if decode not in ("host", "device"):
             raise ValueError('decode must be "host" or "device"')
+        if write not in ("host", "device"):
+            raise ValueError('write must be "host" or "device"')
+        self.write = write
+        self._label_masks = {}                       # write="device": plot.label_mask per (label, thickness), rendered once
+        self._write_stream = None
         if progressive and decode != "device":
             raise ValueError('progressive=True needs decode="device" (PIL, the host decoder, reads progressive files anyway)')
         self.decode = decode
@@ -97,6 +104,82 @@ class Detect_YOLO():
                 frames[p], oris[p] = g.bgr[k], host[k][:, :, ::-1]
         return frames, oris
 
+    def _read_frames_device(self, paths):
+        """write="device": the files of one batch as BGR frames that stay on the device -> (a uint8 GPU tensor [N, h, w, 3] if all have one
+        size, else a list of [h, w, 3] GPU tensors; the same frames once more, per file, for the result writer).  No pixel returns to the
+        host with decode="device"; with decode="host" these are the frames that are uploaded for the model anyway."""
+        if self.decode == "device":
+            from . import jpeg
+            if self.model.input_channel not in (1, 3):
+                raise ValueError("image files decode to 3 channels; feed a %d-channel model through detect_u8" % self.model.input_channel)
+            groups = jpeg.decode_files(paths, self.device, progressive=self.progressive)
+            if len(groups) == 1:
+                bgrs = groups[0].bgr
+            else:
+                bgrs = [None] * len(paths)
+                for g in groups:
+                    for k, p in enumerate(g.positions):
+                        bgrs[p] = g.bgr[k]
+        else:
+            host = [self._read_bgr(p)[0] for p in paths]
+            if len({b.shape for b in host}) == 1:
+                bgrs = torch.from_numpy(np.stack(host)).to(self.device)
+            else:
+                bgrs = [torch.from_numpy(b).to(self.device) for b in host]
+        return bgrs, [bgrs[i] for i in range(len(paths))]
+
+    def _labels(self, boxes):
+        """detect.py:186: the label strings of one frame's detections, as `_save` formats them."""
+        return ['%s %.2f' % (self.class_names[int(b[6])], b[4] * b[5]) for b in boxes]
+
+    def _queue_write(self, paths, frames, results, labels):
+        """write="device": `_save` for one batch on a stream of its own: per frame size one copy of the frames, one draw launch
+        (plot.draw_boxes_device), one encode (jpeg.encode_batch, quality 95, 4:2:0: `_save`'s arguments) and the lengths on their way to
+        pinned memory.  Returns the pending item `_finish_write` turns into files; it keeps every tensor the queued work reads alive."""
+        from . import jpeg
+        from .plot import draw_boxes_device
+        if self._write_stream is None:
+            self._write_stream = torch.cuda.Stream(self.device)
+        ws = self._write_stream
+        ws.wait_stream(torch.cuda.current_stream(self.device))
+        sizes = {}
+        for i, f in enumerate(frames):
+            sizes.setdefault(tuple(f.shape), []).append(i)
+        parts = []
+        with torch.cuda.stream(ws):
+            for idx in sizes.values():
+                batch = torch.stack([frames[i] for i in idx])         # a copy: the drawing is in place
+                draw_boxes_device(batch, [[b[:4] for b in results[i]] for i in idx], [labels[i] for i in idx],
+                                  [[self.colors[int(b[6]) % len(self.colors)] for b in results[i]] for i in idx], line_thickness=3, order="bgr",
+                                  cache=self._label_masks)
+                out, lengths, status = jpeg.encode_batch(batch, 95, "4:2:0", order="bgr")
+                ls = torch.empty((2, len(idx)), dtype=torch.int32, pin_memory=True)
+                ls[0].copy_(lengths, non_blocking=True)
+                ls[1].copy_(status, non_blocking=True)
+                parts.append(([paths[i] for i in idx], batch, out, ls))
+            done = torch.cuda.Event()
+            done.record(ws)
+        return done, parts, frames
+
+    def _finish_write(self, item):
+        """Waits for a pending item of `_queue_write`, copies the used part of its encoded bytes to the host and writes the files."""
+        from . import jpeg
+        done, parts, _ = item
+        done.synchronize()
+        for paths, batch, out, ls in parts:
+            lengths, status = ls.tolist()
+            over = [k for k in range(len(paths)) if status[k]]
+            fit = [k for k in range(len(paths)) if not status[k]]
+            files = {}
+            if fit:
+                files.update(zip(fit, jpeg.gather_files(out[fit] if over else out, [lengths[k] for k in fit])))
+            if over:      # files larger than the first reservation: once more with the size the kernels asked for (no host fallback)
+                files.update(zip(over, jpeg.encode_frames(batch[over], 95, "4:2:0", order="bgr", stride=max(lengths[k] for k in over))))
+            for k, path in enumerate(paths):
+                if path is not None and os.path.isdir(os.path.dirname(path)):
+                    with open(path, "wb") as f:
+                        f.write(files[k])
+
     def _pre_process(self, bgr):
         """detect.py:107-127 for a batch: uint8 GPU tensor [N,h,w,3] (BGR, any size) -> float32 [N,C,H,W].  The reference resizes when its
         CONFIGURED shapes differ (:115); a frame whose actual size is not the net's is resized as well (cv2.resize there would be the only
@@ -136,10 +219,24 @@ class Detect_YOLO():
             origin = self.origin_img_shape
         batches = [img_list[b0:b0 + batch_size] for b0 in range(0, num, batch_size)]
         state = {"avg": 0.0}
+        writes = []                                    # write="device": pending items of _queue_write, oldest first
 
         def report(names, oris, results, infer_time, post_process_time):
             total_time = infer_time + post_process_time
             state["avg"] += total_time * len(names)
+            if self.write == "device":
+                # the batch's draw + encode are queued on the writer's stream; the batch before it becomes files now, so the GPU
+                # encodes this batch while the host decodes / packs the next one
+                labels = [self._labels(b) for b in results]
+                writes.append(self._queue_write([os.path.join(result_path, "result_" + n) for n in names], oris, results, labels))
+                while len(writes) > 1:
+                    self._finish_write(writes.pop(0))
+                for filename, boxes, lab in zip(names, results, labels):
+                    self.last_labels[filename] = lab
+                    self.logger.info("image_name:%s -> %s, infer time:%.2fms, post_process time:%.2fms, total time:%.2fms"
+                                     % (filename, "no targets" if len(boxes) == 0 else "detect finished", infer_time, post_process_time,
+                                        total_time))
+                return
             for filename, ori, boxes in zip(names, oris, results):
                 if len(boxes) == 0:
                     self.last_labels[filename] = self._save(os.path.join(result_path, "result_" + filename), ori, [])
@@ -151,6 +248,9 @@ class Detect_YOLO():
                                  "total time:%.2fms" % (filename, infer_time, post_process_time, total_time))
 
         def load(names):
+            if self.write == "device":
+                bgrs, oris = self._read_frames_device([os.path.join(data_path, n) for n in names])
+                return bgrs, oris, torch.is_tensor(bgrs)
             if self.decode == "device":
                 bgrs, oris = self._read_bgr_device([os.path.join(data_path, n) for n in names])
                 return bgrs, oris, torch.is_tensor(bgrs)
@@ -197,9 +297,14 @@ class Detect_YOLO():
                         finish(pending.pop(0))
                 while pending:
                     finish(pending.pop(0))
+                while writes:
+                    self._finish_write(writes.pop(0))
             finally:
                 pipe.drain()
                 self.model.lanes, self.model.branches = saved
+                if writes:                             # an exception on the way: nothing queued may outlive the tensors it reads
+                    self._write_stream.synchronize()
+                    del writes[:]
         else:
             for names in batches:
                 bgrs, oris, same = load(names)
@@ -217,6 +322,8 @@ class Detect_YOLO():
                 results = self.post_process.detect(pred, origin_shape=origin)
                 post_process_time = (time.time() - time_mark) * 1000 / len(names)
                 report(names, oris, results, infer_time, post_process_time)
+                while writes:
+                    self._finish_write(writes.pop(0))
         self.logger.info("detect avg_time: %.2fms" % (state["avg"] / max(num, 1)))
 
     def _save(self, path, ori, boxes):

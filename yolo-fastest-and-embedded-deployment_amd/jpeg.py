@@ -151,3 +151,119 @@ def decode_files(paths_or_bytes, device, progressive=False):
                           % (names[i], s, "" if len(bad) == 1 else "; %d more such files in this call" % (len(bad) - 1)))
     del keep
     return groups
+
+
+# ---- encoding (csrc/yf_jpeg_enc_kernels.hip): byte for byte the file PIL writes for Image.save(f, "JPEG", quality=q, subsampling=s) ----
+
+_SUBSAMPLING = {"4:4:4": 0, "4:2:2": 1, "4:2:0": 2}
+
+
+class EncSetup(NamedTuple):
+    """yf_jpeg_enc_setup's blob (a uint8 CPU tensor) and what it holds: the file header, the divisors 8 * q and their reciprocals per
+    table ([luma, chroma], natural order), and blocks per frame."""
+    blob: torch.Tensor
+    header: bytes
+    divisors: list
+    reciprocals: list
+    blocks: int
+
+
+def enc_setup(h, w, channels, quality=95, subsampling="4:2:0"):
+    """Host only.  ValueError for what the device encoder does not build: channels other than 1 or 3, quality outside 1..100, other
+    subsampling strings, sides above 8192, frames whose worst-case stream exceeds 2^31 bits."""
+    if subsampling not in _SUBSAMPLING:
+        raise ValueError('subsampling must be "4:4:4", "4:2:2" or "4:2:0", got %r' % (subsampling,))
+    if isinstance(quality, bool) or not isinstance(quality, int):
+        raise ValueError("quality must be an int 1..100, got %r" % (quality,))
+    lib = _lib.lib()
+    need = ctypes.c_size_t()
+    args = (int(h), int(w), int(channels), quality, _SUBSAMPLING[subsampling])
+    rc = lib.yf_jpeg_enc_setup(*args, None, 0, ctypes.byref(need))
+    if rc == _lib.YF_E_INVALID:
+        raise ValueError(lib.yf_last_error_string().decode(errors="replace"))
+    _lib.check(rc)
+    blob = torch.empty(need.value, dtype=torch.uint8)
+    _lib.check(lib.yf_jpeg_enc_setup(*args, ctypes.c_void_p(blob.data_ptr()), need.value, ctypes.byref(need)))
+    info = (ctypes.c_int * 10)()
+    header = ctypes.create_string_buffer(640)
+    div, rcp = (ctypes.c_uint16 * 128)(), (ctypes.c_uint32 * 128)()
+    _lib.check(lib.yf_jpeg_enc_info(ctypes.c_void_p(blob.data_ptr()), info, 10, header, div, rcp))
+    return EncSetup(blob, header.raw[:info[6]], [list(div[:64]), list(div[64:])], [list(rcp[:64]), list(rcp[64:])], info[7])
+
+
+def enc_workspace_bytes(setup, n):
+    """Device workspace encode_batch needs for n frames of `setup`."""
+    need = ctypes.c_size_t()
+    _lib.check(_lib.lib().yf_jpeg_enc_workspace_bytes(ctypes.c_void_p(setup.blob.data_ptr()), n, ctypes.byref(need)))
+    return need.value
+
+
+def _enc_check(frames, quality, subsampling, order, optimize, progressive):
+    if optimize or progressive:
+        raise ValueError("the device encoder writes baseline files with the Annex K tables: optimize / progressive are not built")
+    if order not in ("bgr", "rgb"):
+        raise ValueError('order must be "bgr" or "rgb"')
+    if not torch.is_tensor(frames) or not frames.is_cuda or frames.dtype != torch.uint8:
+        raise ValueError("expected a uint8 GPU tensor [n, h, w, 3] or [n, h, w]")
+    if frames.dim() not in (3, 4) or (frames.dim() == 4 and frames.shape[3] != 3) or frames.shape[0] < 1:
+        raise ValueError("expected a uint8 GPU tensor [n, h, w, 3] or [n, h, w] with n >= 1, got %s" % (tuple(frames.shape),))
+    return enc_setup(frames.shape[1], frames.shape[2], 3 if frames.dim() == 4 else 1, quality, subsampling)
+
+
+def encode_batch(frames, quality=95, subsampling="4:2:0", order="bgr", stride=None, optimize=False, progressive=False, setup=None,
+                 workspace=None, out=None, lengths=None, status=None):
+    """Stream-ordered (current stream), nothing synchronises: uint8 device frames [n, h, w, 3] (`order` "bgr" as decode_files hands them
+    out, or "rgb") or [n, h, w] (gray) -> (buffer uint8 [n, stride], lengths int32 [n], status int32 [n]) on the device.  Frame f's file is
+    buffer[f, :lengths[f]]; status[f] = 1 means it did not fit `stride` (default h * w * channels + 1024) and lengths[f] is the stride it
+    needs.  Capturable when `workspace`, `out`, `lengths` and `status` are passed in (allocated before the capture)."""
+    s = setup or _enc_check(frames, quality, subsampling, order, optimize, progressive)
+    frames = frames.contiguous()
+    n = frames.shape[0]
+    dev = frames.device
+    if stride is None:
+        stride = frames[0].numel() + 1024
+    lib = _lib.lib()
+    if workspace is None:
+        workspace = torch.empty(enc_workspace_bytes(s, n), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.empty((n, stride), dtype=torch.uint8, device=dev)
+    if lengths is None:
+        lengths = torch.empty((n,), dtype=torch.int32, device=dev)
+    if status is None:
+        status = torch.empty((n,), dtype=torch.int32, device=dev)
+    stream = torch.cuda.current_stream(dev)
+    _lib.check(lib.yf_jpeg_encode_u8(dev.index, ctypes.c_void_p(s.blob.data_ptr()), ctypes.c_void_p(frames.data_ptr()), n, int(order == "bgr"),
+                                     ctypes.c_void_p(workspace.data_ptr()), workspace.numel(), ctypes.c_void_p(out.data_ptr()), out.shape[1],
+                                     ctypes.c_void_p(lengths.data_ptr()), ctypes.c_void_p(status.data_ptr()), ctypes.c_void_p(stream.cuda_stream)))
+    return out, lengths, status
+
+
+def gather_files(out, lengths):
+    """(buffer [n, stride] on the device, lengths as a host list) -> [bytes]: one device-to-host copy of the used part of the buffer."""
+    most = max(lengths)
+    host = out[:, :most].cpu().numpy()
+    return [host[f, :lengths[f]].tobytes() for f in range(len(lengths))]
+
+
+def encode_frames(frames, quality=95, subsampling="4:2:0", order="bgr", stride=None, optimize=False, progressive=False):
+    """uint8 device frames -> [bytes], one complete JPEG file per frame: what PIL writes for `Image.fromarray(rgb_or_gray).save(f, "JPEG",
+    quality=quality, subsampling=subsampling)`.  Frames that outgrow the first reservation are encoded once more with the size they need
+    (the kernels report it); there is no host fallback."""
+    s = _enc_check(frames, quality, subsampling, order, optimize, progressive)
+    out, lengths, status = encode_batch(frames, order=order, stride=stride, setup=s)
+    ls = torch.stack([lengths, status]).cpu().tolist()
+    lengths, status = ls
+    over = [f for f in range(len(status)) if status[f]]
+    fit = [f for f in range(len(status)) if not status[f]]
+    files = [None] * len(status)
+    if fit:
+        for f, d in zip(fit, gather_files(out[fit] if over else out, [lengths[f] for f in fit])):
+            files[f] = d
+    if over:
+        out2, l2, s2 = encode_batch(frames[over], order=order, stride=max(lengths[f] for f in over), setup=s)
+        l2, s2 = torch.stack([l2, s2]).cpu().tolist()
+        if any(s2):
+            raise _lib.YFError("the device JPEG encoder overflowed the size it asked for")
+        for f, d in zip(over, gather_files(out2, l2)):
+            files[f] = d
+    return files
