@@ -27,7 +27,7 @@ import xml.etree.ElementTree as xmlET
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, jpeg
 from .config import config_params
 
 
@@ -75,10 +75,7 @@ class DetectDataset(torch.utils.data.Dataset):
             raise ValueError("gray_bits must be 14 or 15")
         if cache not in (None, "device"):
             raise ValueError('cache must be None or "device"')
-        if decode not in ("host", "device"):
-            raise ValueError('decode must be "host" or "device"')
-        if progressive and decode != "device":
-            raise ValueError('progressive=True needs decode="device" (PIL, the host decoder, reads progressive files anyway)')
+        jpeg.check_decode(decode, progressive)
         self.logger = logger = logger or logging.getLogger(__name__)
         if val:
             logger.info(" Val Datasest Loading..")
@@ -96,10 +93,8 @@ class DetectDataset(torch.utils.data.Dataset):
         self.progressive = bool(progressive)
         self.classes = list(class_names if class_names is not None else config_params["io_params"]["class_names"])
         if device is None:
-            device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+            device = "cuda" if torch.cuda.is_available() else "cpu"
+        self.device = jpeg.cuda_device(device)
 
         self.file_path_img = os.path.join(self.dataset_dir, "img")
         self.file_path_xml = os.path.join(self.dataset_dir, "xml")
@@ -180,7 +175,6 @@ class DetectDataset(torch.utils.data.Dataset):
 
     def _decode_device(self, indices):
         """decode="device": the frames `indices` in one decode call per source size -> [(indices of the group, uint8 device [n, h, w, 3])]."""
-        from . import jpeg
         groups = jpeg.decode_files([self.img_list[i] for i in indices], self.device, progressive=self.progressive)
         out = []
         for g in groups:
@@ -190,46 +184,61 @@ class DetectDataset(torch.utils.data.Dataset):
             out.append((members, g.bgr))
         return out
 
-    def _fill_cache(self, indices):
-        """cache="device" with decode="device": the frames of `indices` not cached yet, decoded in one call per size into their stacks."""
-        missing = list(dict.fromkeys(i for i in indices if i not in self._slot))
-        if not missing:
-            return
-        for members, bgr in self._decode_device(missing):
-            hw = tuple(bgr.shape[1:3])
-            ent = self._stacks.get(hw)
-            if ent is None:
-                ent = self._stacks[hw] = [torch.empty((8,) + tuple(bgr.shape[1:]), dtype=torch.uint8, device=self.device), 0]
-            need = ent[1] + len(members)
-            if need > ent[0].shape[0]:
-                cap = ent[0].shape[0]
-                while cap < need:
-                    cap *= 2
-                grown = torch.empty((cap,) + tuple(bgr.shape[1:]), dtype=torch.uint8, device=self.device)
-                grown[:ent[1]].copy_(ent[0][:ent[1]])
-                ent[0] = grown
-            ent[0][ent[1]:need].copy_(bgr)
-            for k, i in enumerate(members):
-                self._slot[i] = (hw, ent[1] + k)
-            ent[1] = need
-
-    def _cached(self, index):
-        """cache='device': (source size, slot) of frame `index`, decoding and uploading it on first access."""
-        if index in self._slot:
-            return self._slot[index]
-        bgr = self._decode(index)
-        hw = bgr.shape[:2]
+    def _append(self, indices, frames):
+        """cache="device": the frames `indices`, uint8 [k, h, w, 3] of one size (a host array or a device tensor), to the end of that size's
+        stack (8 slots at first, doubled while too small); records their slots."""
+        hw = tuple(frames.shape[1:3])
         ent = self._stacks.get(hw)
         if ent is None:
-            ent = self._stacks[hw] = [torch.empty((8,) + bgr.shape, dtype=torch.uint8, device=self.device), 0]
-        if ent[1] == ent[0].shape[0]:
-            grown = torch.empty((2 * ent[1],) + bgr.shape, dtype=torch.uint8, device=self.device)
-            grown[:ent[1]].copy_(ent[0])
+            ent = self._stacks[hw] = [torch.empty((8,) + tuple(frames.shape[1:]), dtype=torch.uint8, device=self.device), 0]
+        need = ent[1] + len(indices)
+        if need > ent[0].shape[0]:
+            cap = ent[0].shape[0]
+            while cap < need:
+                cap *= 2
+            grown = torch.empty((cap,) + tuple(frames.shape[1:]), dtype=torch.uint8, device=self.device)
+            grown[:ent[1]].copy_(ent[0][:ent[1]])
             ent[0] = grown
-        ent[0][ent[1]].copy_(torch.from_numpy(bgr))
-        self._slot[index] = (hw, ent[1])
-        ent[1] += 1
-        return self._slot[index]
+        ent[0][ent[1]:need].copy_(torch.as_tensor(frames))
+        for k, i in enumerate(indices):
+            self._slot[i] = (hw, ent[1] + k)
+        ent[1] = need
+
+    # Where the frames of a batch are: per source size (uint8 device stack [n_src, h, w, 3], slot in it per member -- None: the stack is
+    # the members in order --, position in the batch per member).
+    def _from_cache(self, indices):
+        """cache="device": the stacks of the cache; frames not in it yet are decoded (decode="device": in one call per size) and appended."""
+        if self.decode == "device":
+            for members, bgr in self._decode_device(list(dict.fromkeys(i for i in indices if i not in self._slot))):
+                self._append(members, bgr)
+        groups = {}
+        for pos, i in enumerate(indices):
+            if i not in self._slot:
+                self._append([i], self._decode(i)[None])
+            hw, slot = self._slot[i]
+            slots, at = groups.setdefault(hw, ([], []))
+            slots.append(slot)
+            at.append(pos)
+        return [(self._stacks[hw][0][:self._stacks[hw][1]], slots, at) for hw, (slots, at) in groups.items()]
+
+    def _from_device_decode(self, indices):
+        """decode="device": each distinct frame decoded once, one call per size."""
+        out = []
+        for members, bgr in self._decode_device(list(dict.fromkeys(indices))):
+            slot = {i: k for k, i in enumerate(members)}
+            at = [pos for pos, i in enumerate(indices) if i in slot]
+            out.append((bgr, [slot[indices[pos]] for pos in at], at))
+        return out
+
+    def _from_host_decode(self, indices):
+        """decode="host": every member decoded by PIL, one upload per size."""
+        frames = {}
+        for pos, i in enumerate(indices):
+            bgr = self._decode(i)
+            stack, at = frames.setdefault(bgr.shape[:2], ([], []))
+            stack.append(bgr)
+            at.append(pos)
+        return [(torch.from_numpy(np.stack(stack)).to(self.device), None, at) for stack, at in frames.values()]
 
     def _resize_tables(self, hw, stream):
         H, W = self.input_shape[0], self.input_shape[1]
@@ -251,46 +260,22 @@ class DetectDataset(torch.utils.data.Dataset):
         stream = torch.cuda.current_stream(dev).cuda_stream
         out = torch.empty((N, H, W, C) if out_u8 else (N, C, H, W), dtype=torch.uint8 if out_u8 else torch.float32, device=dev)
         packed = [int(k) | (int(bool(f)) << 8) for k, f in params]
-        groups = {}
         if self.cache == "device":
-            if self.decode == "device":
-                self._fill_cache(indices)
-            for pos, i in enumerate(indices):
-                hw, slot = self._cached(i)
-                groups.setdefault(hw, []).append((pos, slot))
+            groups = self._from_cache(indices)
         elif self.decode == "device":
-            frames = {}
-            at = {}
-            for members, bgr in self._decode_device(list(dict.fromkeys(indices))):
-                frames[tuple(bgr.shape[1:3])] = bgr
-                for k, i in enumerate(members):
-                    at[i] = (tuple(bgr.shape[1:3]), k)
-            for pos, i in enumerate(indices):
-                groups.setdefault(at[i][0], []).append((pos, at[i][1]))
+            groups = self._from_device_decode(indices)
         else:
-            frames = {}
-            for pos, i in enumerate(indices):
-                bgr = self._decode(i)
-                frames.setdefault(bgr.shape[:2], []).append(bgr)
-                groups.setdefault(bgr.shape[:2], []).append((pos, len(frames[bgr.shape[:2]]) - 1))
+            groups = self._from_host_decode(indices)
         lib = _lib.lib()
-        for hw, members in groups.items():
-            pos = [p for p, _ in members]
-            if self.cache == "device":
-                stack, n_src = self._stacks[hw][0], self._stacks[hw][1]
-                index = torch.tensor([s for _, s in members], dtype=torch.int32).to(dev)
-            elif self.decode == "device":
-                stack, n_src = frames[hw], frames[hw].shape[0]
-                index = torch.tensor([s for _, s in members], dtype=torch.int32).to(dev)
-            else:
-                stack = torch.from_numpy(np.stack(frames[hw])).to(dev)
-                n_src, index = stack.shape[0], None
+        for stack, slots, pos in groups:
+            hw = tuple(stack.shape[1:3])
+            index = None if slots is None else torch.tensor(slots, dtype=torch.int32).to(dev)
             prm = torch.tensor([packed[p] for p in pos], dtype=torch.int32).to(dev)
             whole = len(groups) == 1
             dst = out if whole else torch.empty((len(pos),) + tuple(out.shape[1:]), dtype=out.dtype, device=dev)
             xt, yt = self._resize_tables(hw, stream)
-            _lib.check(lib.yf_augment_u8(dev.index, stack.data_ptr(), hw[0], hw[1], 3, None if index is None else index.data_ptr(), n_src,
-                                         len(pos), xt, yt, H, W, C, self.gray_bits, prm.data_ptr(),
+            _lib.check(lib.yf_augment_u8(dev.index, stack.data_ptr(), hw[0], hw[1], 3, None if index is None else index.data_ptr(),
+                                         stack.shape[0], len(pos), xt, yt, H, W, C, self.gray_bits, prm.data_ptr(),
                                          dst.data_ptr() if out_u8 else None, None if out_u8 else dst.data_ptr(), ctypes.c_void_p(stream)))
             if not whole:
                 out.index_copy_(0, torch.tensor(pos, device=dev), dst)

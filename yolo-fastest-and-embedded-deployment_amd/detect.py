@@ -23,9 +23,9 @@ import time
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, jpeg
 from .model import YoloFastest
-from .plot import plot_one_box
+from .plot import draw_boxes_device, plot_one_box
 from .post_process import YOLO_post_process
 
 
@@ -50,22 +50,19 @@ def preprocess_u8(model, u8, input_shape):
 
 class Detect_YOLO():
     def __init__(self, device, model_path, config_params, logger, decode="host", progressive=False, write="host"):
-        if decode not in ("host", "device"):
-            raise ValueError('decode must be "host" or "device"')
+        jpeg.check_decode(decode, progressive)
         if write not in ("host", "device"):
             raise ValueError('write must be "host" or "device"')
         self.write = write
         self._label_masks = {}                       # write="device": plot.label_mask per (label, thickness), rendered once
         self._write_stream = None
-        if progressive and decode != "device":
-            raise ValueError('progressive=True needs decode="device" (PIL, the host decoder, reads progressive files anyway)')
         self.decode = decode
         self.progressive = bool(progressive)
         self.model = YoloFastest(config_params["io_params"]).to(device).eval()
         net_param = torch.load(model_path, map_location=device)
         self.model.load_state_dict(net_param)
         self.logger = logger
-        self.device = torch.device(device)
+        self.device = jpeg.cuda_device(device)
         io = config_params["io_params"]
         self.class_names = io["class_names"]
         self.num_cls = io["num_cls"]
@@ -78,55 +75,40 @@ class Detect_YOLO():
                                               input_shape=self.input_shape, num_class=self.num_cls).bind(self.model)
         self.colors = [[106, 90, 205], [199, 97, 20], [112, 128, 105]]
 
+    def _check_channels(self):
+        if self.model.input_channel not in (1, 3):   # cv2.imread as detect.py:108-113 calls it yields 3 channels: nothing to mirror
+            raise ValueError("image files decode to 3 channels; feed a %d-channel model through detect_u8" % self.model.input_channel)
+
     def _read_bgr(self, path):
         """-> (what cv2.imread(path) returns: uint8 [h,w,3] in BGR order, detect.py:108; the RGB original for drawing).  BGR2GRAY for a
         1-channel net (:110-111) and the resize (:115-116) happen on the device (`_pre_process`)."""
         from PIL import Image
-        if self.model.input_channel not in (1, 3):   # cv2.imread as detect.py:108-113 calls it yields 3 channels: nothing to mirror
-            raise ValueError("image files decode to 3 channels; feed a %d-channel model through detect_u8" % self.model.input_channel)
+        self._check_channels()
         ori = np.asarray(Image.open(path).convert("RGB"))
         return np.ascontiguousarray(ori[:, :, ::-1]), ori
 
-    def _read_bgr_device(self, paths):
-        """decode="device": the files of one batch -> (a uint8 GPU tensor [N, h, w, 3] if all have one size, else a list of [h, w, 3] GPU
-        tensors; the RGB originals for drawing, from one device-to-host copy per frame size)."""
-        from . import jpeg
-        if self.model.input_channel not in (1, 3):
-            raise ValueError("image files decode to 3 channels; feed a %d-channel model through detect_u8" % self.model.input_channel)
-        groups = jpeg.decode_files(paths, self.device, progressive=self.progressive)
-        if len(groups) == 1:
-            host = groups[0].bgr.cpu().numpy()
-            return groups[0].bgr, [f[:, :, ::-1] for f in host]
-        frames, oris = [None] * len(paths), [None] * len(paths)
-        for g in groups:
-            host = g.bgr.cpu().numpy()
-            for k, p in enumerate(g.positions):
-                frames[p], oris[p] = g.bgr[k], host[k][:, :, ::-1]
-        return frames, oris
-
-    def _read_frames_device(self, paths):
-        """write="device": the files of one batch as BGR frames that stay on the device -> (a uint8 GPU tensor [N, h, w, 3] if all have one
-        size, else a list of [h, w, 3] GPU tensors; the same frames once more, per file, for the result writer).  No pixel returns to the
-        host with decode="device"; with decode="host" these are the frames that are uploaded for the model anyway."""
+    def _load(self, paths):
+        """The files of one batch -> (their BGR frames on the device: a uint8 tensor [N, h, w, 3] if all have one size, else a list of
+        [h, w, 3] tensors; with write="host" the RGB originals on the host for `_save`, else None).  `decode` says where the pixels come
+        from: PIL and one upload per batch (per frame when sizes differ), or the device decoder and, for the originals, one device-to-host
+        copy per frame size."""
+        oris = None
         if self.decode == "device":
-            from . import jpeg
-            if self.model.input_channel not in (1, 3):
-                raise ValueError("image files decode to 3 channels; feed a %d-channel model through detect_u8" % self.model.input_channel)
+            self._check_channels()
             groups = jpeg.decode_files(paths, self.device, progressive=self.progressive)
-            if len(groups) == 1:
-                bgrs = groups[0].bgr
-            else:
-                bgrs = [None] * len(paths)
-                for g in groups:
-                    for k, p in enumerate(g.positions):
-                        bgrs[p] = g.bgr[k]
+            bgrs = jpeg.frames_in_order(groups)
+            if self.write == "host":
+                oris = [f[:, :, ::-1] for f in jpeg.frames_in_order(groups, [g.bgr.cpu().numpy() for g in groups])]
         else:
-            host = [self._read_bgr(p)[0] for p in paths]
+            if self.write == "host":
+                host, oris = zip(*[self._read_bgr(p) for p in paths])
+            else:      # each original is dropped as it is read: held for the batch they cost 0.4 ms per 640 x 512 frame (fresh host pages)
+                host = [self._read_bgr(p)[0] for p in paths]
             if len({b.shape for b in host}) == 1:
                 bgrs = torch.from_numpy(np.stack(host)).to(self.device)
             else:
                 bgrs = [torch.from_numpy(b).to(self.device) for b in host]
-        return bgrs, [bgrs[i] for i in range(len(paths))]
+        return bgrs, oris
 
     def _labels(self, boxes):
         """detect.py:186: the label strings of one frame's detections, as `_save` formats them."""
@@ -136,8 +118,6 @@ class Detect_YOLO():
         """write="device": `_save` for one batch on a stream of its own: per frame size one copy of the frames, one draw launch
         (plot.draw_boxes_device), one encode (jpeg.encode_batch, quality 95, 4:2:0: `_save`'s arguments) and the lengths on their way to
         pinned memory.  Returns the pending item `_finish_write` turns into files; it keeps every tensor the queued work reads alive."""
-        from . import jpeg
-        from .plot import draw_boxes_device
         if self._write_stream is None:
             self._write_stream = torch.cuda.Stream(self.device)
         ws = self._write_stream
@@ -163,22 +143,24 @@ class Detect_YOLO():
 
     def _finish_write(self, item):
         """Waits for a pending item of `_queue_write`, copies the used part of its encoded bytes to the host and writes the files."""
-        from . import jpeg
         done, parts, _ = item
         done.synchronize()
         for paths, batch, out, ls in parts:
             lengths, status = ls.tolist()
-            over = [k for k in range(len(paths)) if status[k]]
-            fit = [k for k in range(len(paths)) if not status[k]]
-            files = {}
-            if fit:
-                files.update(zip(fit, jpeg.gather_files(out[fit] if over else out, [lengths[k] for k in fit])))
-            if over:      # files larger than the first reservation: once more with the size the kernels asked for (no host fallback)
-                files.update(zip(over, jpeg.encode_frames(batch[over], 95, "4:2:0", order="bgr", stride=max(lengths[k] for k in over))))
-            for k, path in enumerate(paths):
+            for path, data in zip(paths, jpeg.gather_encoded(batch, out, lengths, status, 95, "4:2:0", "bgr")):
                 if path is not None and os.path.isdir(os.path.dirname(path)):
                     with open(path, "wb") as f:
-                        f.write(files[k])
+                        f.write(data)
+
+    def _drain_writes(self, writes, keep=0):
+        """Turns the oldest pending items of `_queue_write` into files until `keep` are left."""
+        while len(writes) > keep:
+            self._finish_write(writes.pop(0))
+
+    @property
+    def _origin(self):
+        """The post-process' `origin_shape`: the configured original shape where it differs from the net's (__adjust_coord, :131-139)."""
+        return self.origin_img_shape if list(self.input_shape[0:2]) != list(self.origin_img_shape[0:2]) else None
 
     def _pre_process(self, bgr):
         """detect.py:107-127 for a batch: uint8 GPU tensor [N,h,w,3] (BGR, any size) -> float32 [N,C,H,W].  The reference resizes when its
@@ -191,19 +173,13 @@ class Detect_YOLO():
         """bgr: uint8 GPU tensor [N,h,w,3] as cv2.imread returns frames, any size.  The whole of detect.py:108-182 on the device; per-frame
         lists in the coordinates of `origin_img_shape` (after __adjust_coord, :131-139)."""
         pred = self.model.forward_bgr_u8(bgr, self.input_shape, gray_bits=gray_bits)
-        origin = None
-        if list(self.input_shape[0:2]) != list(self.origin_img_shape[0:2]):
-            origin = self.origin_img_shape
-        return self.post_process.detect(pred, kmax=kmax, origin_shape=origin)
+        return self.post_process.detect(pred, kmax=kmax, origin_shape=self._origin)
 
     def detect_u8(self, u8, kmax=64):
         """u8: uint8 GPU tensor [N,h,w] in the ORIGINAL image geometry (any size: cv2.resize's arithmetic brings it to the net's). Returns
         per-frame lists in original coordinates (after __adjust_coord, detect.py:181-182)."""
         pred = self.model.forward_u8(u8, self.input_shape)  # pre-process in front of / fused into the first kernel's loads
-        origin = None
-        if list(self.input_shape[0:2]) != list(self.origin_img_shape[0:2]):
-            origin = self.origin_img_shape
-        return self.post_process.detect(pred, kmax=kmax, origin_shape=origin)
+        return self.post_process.detect(pred, kmax=kmax, origin_shape=self._origin)
 
     def batch_detect(self, data_path, result_path, batch_size=256, in_flight=2):
         """detect.py:141-192 over a directory, `batch_size` images per pass.  More than one batch: the batches go through `BatchPipeline`
@@ -214,77 +190,57 @@ class Detect_YOLO():
         img_list = sorted(os.listdir(data_path))   # the reference iterates os.listdir order; its logs show it sorted
         num = len(img_list)
         self.last_labels = {}
-        origin = None
-        if list(self.input_shape[0:2]) != list(self.origin_img_shape[0:2]):
-            origin = self.origin_img_shape
+        origin = self._origin
         batches = [img_list[b0:b0 + batch_size] for b0 in range(0, num, batch_size)]
+        pipelined = len(batches) > 1 and in_flight > 1
         state = {"avg": 0.0}
         writes = []                                    # write="device": pending items of _queue_write, oldest first
 
-        def report(names, oris, results, infer_time, post_process_time):
+        def report(names, bgrs, oris, results, infer_time, post_process_time):
             total_time = infer_time + post_process_time
             state["avg"] += total_time * len(names)
+            paths = [os.path.join(result_path, "result_" + n) for n in names]
+            labels = [self._labels(b) for b in results]
             if self.write == "device":
-                # the batch's draw + encode are queued on the writer's stream; the batch before it becomes files now, so the GPU
-                # encodes this batch while the host decodes / packs the next one
-                labels = [self._labels(b) for b in results]
-                writes.append(self._queue_write([os.path.join(result_path, "result_" + n) for n in names], oris, results, labels))
-                while len(writes) > 1:
-                    self._finish_write(writes.pop(0))
-                for filename, boxes, lab in zip(names, results, labels):
-                    self.last_labels[filename] = lab
-                    self.logger.info("image_name:%s -> %s, infer time:%.2fms, post_process time:%.2fms, total time:%.2fms"
-                                     % (filename, "no targets" if len(boxes) == 0 else "detect finished", infer_time, post_process_time,
-                                        total_time))
-                return
-            for filename, ori, boxes in zip(names, oris, results):
-                if len(boxes) == 0:
-                    self.last_labels[filename] = self._save(os.path.join(result_path, "result_" + filename), ori, [])
-                    self.logger.info("image_name:%s -> no targets, infer time:%.2fms, post_process time:%.2fms, "
-                                     "total time:%.2fms" % (filename, infer_time, post_process_time, total_time))
-                    continue
-                self.last_labels[filename] = self._save(os.path.join(result_path, "result_" + filename), ori, boxes)
-                self.logger.info("image_name:%s -> detect finished, infer time:%.2fms, post_process time:%.2fms, "
-                                 "total time:%.2fms" % (filename, infer_time, post_process_time, total_time))
+                # the batch's draw + encode are queued on the writer's stream; with batches in flight the batch before it becomes files
+                # now, so the GPU encodes this batch while the host decodes / packs the next one
+                writes.append(self._queue_write(paths, bgrs, results, labels))
+                self._drain_writes(writes, keep=int(pipelined))
+            for k, (filename, boxes) in enumerate(zip(names, results)):
+                if self.write == "host":
+                    self._save(paths[k], oris[k], boxes)
+                self.last_labels[filename] = labels[k]
+                self.logger.info("image_name:%s -> %s, infer time:%.2fms, post_process time:%.2fms, total time:%.2fms"
+                                 % (filename, "no targets" if len(boxes) == 0 else "detect finished", infer_time, post_process_time,
+                                    total_time))
 
         def load(names):
-            if self.write == "device":
-                bgrs, oris = self._read_frames_device([os.path.join(data_path, n) for n in names])
-                return bgrs, oris, torch.is_tensor(bgrs)
-            if self.decode == "device":
-                bgrs, oris = self._read_bgr_device([os.path.join(data_path, n) for n in names])
-                return bgrs, oris, torch.is_tensor(bgrs)
-            bgrs, oris = zip(*[self._read_bgr(os.path.join(data_path, n)) for n in names])
-            return bgrs, oris, len({b.shape for b in bgrs}) == 1
+            """-> (the batch's frames and originals as `_load` returns them, the net's input)."""
+            bgrs, oris = self._load([os.path.join(data_path, n) for n in names])
+            if not torch.is_tensor(bgrs):      # frames of different sizes: the resize brings them to one
+                x = torch.cat([self._pre_process(b[None]) for b in bgrs])
+            else:      # cv2.imread-shaped frames of one size; in flight, cvtColor + resize + (v - 128) / 255 run inside the batch's own stream
+                x = bgrs if pipelined else self._pre_process(bgrs)
+            return bgrs, oris, x
 
-        def frame(b):
-            return b[None] if torch.is_tensor(b) else torch.from_numpy(b[None]).to(self.device)
-
-        def stack(bgrs):
-            return bgrs if torch.is_tensor(bgrs) else torch.from_numpy(np.stack(bgrs)).to(self.device)
-
-        if len(batches) > 1 and in_flight > 1:
+        if pipelined:
             from .pipeline import BatchPipeline
             saved = (self.model.lanes, self.model.branches)
             pipe = BatchPipeline(self.model, self.post_process, depth=in_flight, kmax=64, origin_shape=origin, lanes=1, branches=0)
             pending = []
 
             def finish(item):
-                names, oris, ticket, ev = item
+                names, bgrs, oris, ticket, ev = item
                 raw = ticket.synchronize()
                 most = int(raw["counts"].max().item()) if raw["counts"].numel() else 0
                 if most > raw["boxes"].shape[1]:      # more survivors than the first attempt reserved: once more with room for all (post.detect does the same)
                     raw = self.post_process.detect_raw((raw["head_large"], raw["head_small"]), kmax=most, origin_shape=origin)
                 results = self.post_process.to_lists(raw)
-                report(names, oris, results, ev[0].elapsed_time(ev[1]) / len(names), ev[1].elapsed_time(ev[2]) / len(names))
+                report(names, bgrs, oris, results, ev[0].elapsed_time(ev[1]) / len(names), ev[1].elapsed_time(ev[2]) / len(names))
 
             try:
                 for names in batches:
-                    bgrs, oris, same = load(names)
-                    if same:       # cv2.imread-shaped frames of one size: cvtColor + resize + (v - 128) / 255 inside the batch's own stream
-                        x = stack(bgrs)
-                    else:          # frames of different sizes: the resize brings them to one
-                        x = torch.cat([self._pre_process(frame(b)) for b in bgrs])
+                    bgrs, oris, x = load(names)
                     ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
                     ev[0].record()
 
@@ -292,13 +248,12 @@ class Detect_YOLO():
                         ev[1].record()
                         return pred
                     ticket = pipe.submit(x, mid=mid, then=lambda out, ev=ev: ev[2].record())
-                    pending.append((names, oris, ticket, ev))
+                    pending.append((names, bgrs, oris, ticket, ev))
                     if len(pending) >= in_flight:
                         finish(pending.pop(0))
                 while pending:
                     finish(pending.pop(0))
-                while writes:
-                    self._finish_write(writes.pop(0))
+                self._drain_writes(writes)
             finally:
                 pipe.drain()
                 self.model.lanes, self.model.branches = saved
@@ -307,11 +262,7 @@ class Detect_YOLO():
                     del writes[:]
         else:
             for names in batches:
-                bgrs, oris, same = load(names)
-                if same:
-                    x = self._pre_process(stack(bgrs))
-                else:
-                    x = torch.cat([self._pre_process(frame(b)) for b in bgrs])
+                bgrs, oris, x = load(names)
                 torch.cuda.synchronize(self.device)
                 start_time = time.time()
                 with torch.no_grad():
@@ -321,21 +272,17 @@ class Detect_YOLO():
                 infer_time = (time_mark - start_time) * 1000 / len(names)
                 results = self.post_process.detect(pred, origin_shape=origin)
                 post_process_time = (time.time() - time_mark) * 1000 / len(names)
-                report(names, oris, results, infer_time, post_process_time)
-                while writes:
-                    self._finish_write(writes.pop(0))
+                report(names, bgrs, oris, results, infer_time, post_process_time)
         self.logger.info("detect avg_time: %.2fms" % (state["avg"] / max(num, 1)))
 
     def _save(self, path, ori, boxes):
         """detect.py:184-190: one box + label per detection (plot.plot_one_box), then the image file.  Returns the label
         strings it drew ('%s %.2f' % (class name, conf * cls_score), :186)."""
         img = np.ascontiguousarray(ori).copy()
-        labels = []
-        for *xyxy, conf, cls_score, cls_pred in boxes:
-            label = '%s %.2f' % (self.class_names[int(cls_pred)], conf * cls_score)
+        labels = self._labels(boxes)
+        for (*xyxy, _, _, cls_pred), label in zip(boxes, labels):
             # (the reference has three colours, :105, and would raise IndexError from the fourth class on: they repeat here)
             plot_one_box(xyxy, img, label=label, color=self.colors[int(cls_pred) % len(self.colors)], line_thickness=3)
-            labels.append(label)
         if path is not None and os.path.isdir(os.path.dirname(path)):
             from PIL import Image
             Image.fromarray(img).save(path, quality=95)   # cv2.imwrite's default JPEG quality

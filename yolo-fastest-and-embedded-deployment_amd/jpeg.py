@@ -27,6 +27,22 @@ class JpegGroup(NamedTuple):
     bgr: torch.Tensor
 
 
+def check_decode(decode, progressive):
+    """The `decode` / `progressive` keywords of the drivers that start from image files (DetectDataset, Detect_YOLO)."""
+    if decode not in ("host", "device"):
+        raise ValueError('decode must be "host" or "device"')
+    if progressive and decode != "device":
+        raise ValueError('progressive=True needs decode="device" (PIL, the host decoder, reads progressive files anyway)')
+
+
+def cuda_device(device):
+    """torch.device(device); "cuda" without an index means the current device."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return device
+
+
 def _name(item, i):
     return item if isinstance(item, (str, os.PathLike)) else "<bytes #%d>" % i
 
@@ -43,11 +59,8 @@ def _pack_call(datas, blob_ptr, blob_cap, progressive=False):
     ptrs = (ctypes.c_void_p * n)(*[ctypes.cast(ctypes.c_char_p(d), ctypes.c_void_p) for d in datas])
     sizes = (ctypes.c_size_t * n)(*[len(d) for d in datas])
     need, h, w = ctypes.c_size_t(), ctypes.c_int(), ctypes.c_int()
-    if progressive:
-        rc = _lib.lib().yf_jpeg_pack_ex(n, ptrs, sizes, _lib.YF_JPEG_PROGRESSIVE, blob_ptr, blob_cap, ctypes.byref(need), ctypes.byref(h),
-                                        ctypes.byref(w))
-    else:
-        rc = _lib.lib().yf_jpeg_pack(n, ptrs, sizes, blob_ptr, blob_cap, ctypes.byref(need), ctypes.byref(h), ctypes.byref(w))
+    rc = _lib.lib().yf_jpeg_pack_ex(n, ptrs, sizes, _lib.YF_JPEG_PROGRESSIVE if progressive else 0, blob_ptr, blob_cap, ctypes.byref(need),
+                                    ctypes.byref(h), ctypes.byref(w))
     return rc, need.value, h.value, w.value
 
 
@@ -70,7 +83,7 @@ def frame_size(data, name="<bytes>", progressive=False):
 
 
 def pack(datas, names=None, pin=True, progressive=False):
-    """The host blob of frames of one size (yf_jpeg_pack, or yf_jpeg_pack_ex with YF_JPEG_PROGRESSIVE) in a (pinned) uint8 CPU tensor
+    """The host blob of frames of one size (yf_jpeg_pack_ex, flags 0 or YF_JPEG_PROGRESSIVE) in a (pinned) uint8 CPU tensor
     -> (blob, h, w)."""
     names = names or ["<bytes #%d>" % i for i in range(len(datas))]
     rc, need, h, w = _pack_call(datas, None, 0, progressive)
@@ -123,11 +136,9 @@ def decode_files(paths_or_bytes, device, progressive=False):
     of first appearance, one decode call per group.  Raises ValueError (unsupported file) before any launch and OSError (corrupt or
     truncated data) after checking the status words.  `progressive=True`: progressive files are decoded too (a size's group may mix
     kinds); without it they are refused."""
-    device = torch.device(device)
+    device = cuda_device(device)
     if device.type != "cuda":
         raise RuntimeError("JPEG decoding on the device needs a cuda device")
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
     items = list(paths_or_bytes)
     datas = [_bytes(x) for x in items]
     names = [_name(x, i) for i, x in enumerate(items)]
@@ -151,6 +162,19 @@ def decode_files(paths_or_bytes, device, progressive=False):
                           % (names[i], s, "" if len(bad) == 1 else "; %d more such files in this call" % (len(bad) - 1)))
     del keep
     return groups
+
+
+def frames_in_order(groups, stacks=None):
+    """decode_files' groups back in the order of its input: the [n, h, w, 3] stack itself when there is one group, else a list of
+    [h, w, 3] views.  `stacks`: one [n_g, h, w, 3] array per group to take the frames from in place of `bgr` (the groups' host copies)."""
+    stacks = [g.bgr for g in groups] if stacks is None else stacks
+    if len(groups) == 1:
+        return stacks[0]
+    frames = [None] * sum(len(g.positions) for g in groups)
+    for g, stack in zip(groups, stacks):
+        for k, p in enumerate(g.positions):
+            frames[p] = stack[k]
+    return frames
 
 
 # ---- encoding (csrc/yf_jpeg_enc_kernels.hip): byte for byte the file PIL writes for Image.save(f, "JPEG", quality=q, subsampling=s) ----
@@ -245,14 +269,9 @@ def gather_files(out, lengths):
     return [host[f, :lengths[f]].tobytes() for f in range(len(lengths))]
 
 
-def encode_frames(frames, quality=95, subsampling="4:2:0", order="bgr", stride=None, optimize=False, progressive=False):
-    """uint8 device frames -> [bytes], one complete JPEG file per frame: what PIL writes for `Image.fromarray(rgb_or_gray).save(f, "JPEG",
-    quality=quality, subsampling=subsampling)`.  Frames that outgrow the first reservation are encoded once more with the size they need
-    (the kernels report it); there is no host fallback."""
-    s = _enc_check(frames, quality, subsampling, order, optimize, progressive)
-    out, lengths, status = encode_batch(frames, order=order, stride=stride, setup=s)
-    ls = torch.stack([lengths, status]).cpu().tolist()
-    lengths, status = ls
+def gather_encoded(frames, out, lengths, status, quality=95, subsampling="4:2:0", order="bgr"):
+    """encode_batch's `out` for `frames`, with its `lengths` and `status` as host lists -> [bytes], one complete file per frame.  Frames
+    that outgrew `out`'s stride are encoded once more with the size they need (the kernels report it); there is no host fallback."""
     over = [f for f in range(len(status)) if status[f]]
     fit = [f for f in range(len(status)) if not status[f]]
     files = [None] * len(status)
@@ -260,10 +279,18 @@ def encode_frames(frames, quality=95, subsampling="4:2:0", order="bgr", stride=N
         for f, d in zip(fit, gather_files(out[fit] if over else out, [lengths[f] for f in fit])):
             files[f] = d
     if over:
-        out2, l2, s2 = encode_batch(frames[over], order=order, stride=max(lengths[f] for f in over), setup=s)
+        out2, l2, s2 = encode_batch(frames[over], quality, subsampling, order, stride=max(lengths[f] for f in over))
         l2, s2 = torch.stack([l2, s2]).cpu().tolist()
         if any(s2):
             raise _lib.YFError("the device JPEG encoder overflowed the size it asked for")
         for f, d in zip(over, gather_files(out2, l2)):
             files[f] = d
     return files
+
+
+def encode_frames(frames, quality=95, subsampling="4:2:0", order="bgr", stride=None, optimize=False, progressive=False):
+    """uint8 device frames -> [bytes], one complete JPEG file per frame: what PIL writes for `Image.fromarray(rgb_or_gray).save(f, "JPEG",
+    quality=quality, subsampling=subsampling)` (gather_encoded after one encode_batch)."""
+    out, lengths, status = encode_batch(frames, quality, subsampling, order, stride, optimize, progressive)
+    lengths, status = torch.stack([lengths, status]).cpu().tolist()
+    return gather_encoded(frames, out, lengths, status, quality, subsampling, order)
