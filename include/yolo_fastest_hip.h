@@ -313,6 +313,23 @@ int yf_forward_bgr_u8(yf_handle h, const uint8_t *d_bgr, int N, int src_h, int s
  * No allocation or synchronisation; stream-ordered. */
 int yf_augment_u8(int device, const uint8_t *d_src, int src_h, int src_w, int src_c, const int *d_index, int n_src, int N, const void *d_xtab,
                   const void *d_ytab, int dst_h, int dst_w, int dst_c, int gray_bits, const int *d_params, uint8_t *d_u8, float *d_x, void *stream);
+/* yf_augment_u8 with yolov5's geometric augmentation (random_perspective) between the resize and the blur, and a vertical flip at the end:
+ *     x = flipud?(fliplr?(GaussianBlur_k(warp?(resize(cvtColor_BGR2GRAY?(frame))))))
+ *   warp      Pillow's Image.transform(size, AFFINE | PERSPECTIVE, coefficients, resample=BILINEAR, fillcolor=114), bit for bit: per
+ *             destination pixel (x, y), in IEEE double with one rounding per operation (no FMA contraction, correctly rounded division):
+ *             xin = x + 0.5, yin = y + 0.5; sx = (a0 xin + a1 yin) + a2, sy = (a3 xin + a4 yin) + a5, PERSPECTIVE: each divided by
+ *             (a6 xin + a7 yin) + 1.0; 114 on every channel if sx < 0, sx >= dst_w, sy < 0 or sy >= dst_h; otherwise the bilinear sample of
+ *             the resized frame at (sx - 0.5, sy - 0.5) with columns and rows clamped, truncated to uint8.
+ *             Pinned to Pillow; OpenCV parity not claimed (cv2.warpAffine / warpPerspective interpolate through fixed-point tables).
+ *   d_params  int32 [N]: yf_augment_u8's k | fliplr << 8, and bit 9 flipud, bit 10 warp present, bit 11 perspective (a6, a7 are read);
+ *             a frame without bit 10 and bit 9 gets yf_augment_u8's bytes
+ *   d_warp    float64 [N, 8]: a0 .. a7 of the output -> input map per frame (read for frames with bit 10)
+ *   d_scratch caller-owned u8 [N, dst_h, dst_w, dst_c] (may not overlap an output): the resized frames between the two launches
+ * Two launches on `stream` (the resize into the scratch, then warp + blur + flips out of it); the blur's reflect-101 border is taken on
+ * the warped image.  No allocation or synchronisation; stream-ordered; capturable. */
+int yf_augment_warp_u8(int device, const uint8_t *d_src, int src_h, int src_w, int src_c, const int *d_index, int n_src, int N, const void *d_xtab,
+                       const void *d_ytab, int dst_h, int dst_w, int dst_c, int gray_bits, const int *d_params, const double *d_warp,
+                       uint8_t *d_scratch, uint8_t *d_u8, float *d_x, void *stream);
 /* cv::resize's INTER_LINEAR tables for one (source, destination) size pair into caller-owned device memory: d_xtab int4 [dst_w],
  * d_ytab int4 [dst_h] (16 bytes each entry).  One small kernel on `stream`, no allocation or synchronisation. */
 int yf_cv_resize_tables(int device, int src_h, int src_w, int dst_h, int dst_w, void *d_xtab, void *d_ytab, void *stream);

@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
 """DetectDataset throughput (dataset.py, csrc/yf_aug_kernels.hip).  GPU box:
     python tools/dataset_bench.py --kernel            augment launch (640x512 BGR -> 256x320 gray, blur / flip drawn like the reference)
-                                                      at batch 16 and 512: event-timed ms and required bytes/s (source + float32 output)
+                                                      at batch 16 and 512: event-timed ms and required bytes/s (source + float32 output);
+                                                      then the same frames with the geometric keys active (yf_augment_warp_u8: every
+                                                      frame warped with a perspective draw, half of them flipped upside down)
     python tools/dataset_bench.py --kernel --profile  the same under `rocprofv3 --kernel-trace --stats` (a child process, a run of its own):
                                                       the kernel's own average duration from the stats file
     python tools/dataset_bench.py --train             train() iterations (DataLoader + train_step) at batch 16, examples/s, interleaved:
-                                                      DetectDataset cache="device", cache=None, and tools/train_bench.py's no-data loop"""
+                                                      DetectDataset cache="device", decode="device", cache=None (decode="host"), the first
+                                                      two again with the geometric keys active, and tools/train_bench.py's no-data loop"""
 import argparse
 import csv
 import glob
@@ -35,6 +38,7 @@ ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--out", default=None, help="directory for the rocprofv3 output (default: a new temporary directory)")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
+GEOMETRIC = dict(degrees=10.0, translate=0.1, scale=1.5, shear=2.0, perspective=0.0005, flipud=0.5)   # yolov5-sized ranges
 
 
 def kernel_bench():
@@ -69,6 +73,33 @@ def kernel_bench():
                   "blurred_frames": sum(1 for p in prm if p & 15)}
         print("augment batch %d: %.4f ms, %.1f MB required, %.3f TB/s (%d of %d frames blurred)"
               % (N, ms, need / 1e6, need / ms / 1e9, res[N]["blurred_frames"], N))
+        if not hasattr(lib, "yf_augment_warp_u8"):
+            continue
+        from yolo_fastest_amd.dataset import DetectDataset
+        draw = DetectDataset.__new__(DetectDataset)                    # the draws alone: no files behind it
+        draw.input_shape = [256, 320, 1]
+        for key in ("degrees", "translate", "scale", "shear", "perspective"):
+            setattr(draw, key, GEOMETRIC[key])
+        random.seed(0)
+        coeffs = [draw._draw_warp()[2] for _ in range(N)]
+        d_warp = torch.tensor(np.stack(coeffs), dtype=torch.float64).to(dev)
+        d_prm2 = torch.tensor([p | (int(rng.random() < GEOMETRIC["flipud"]) << 9) | (3 << 10) for p in prm], dtype=torch.int32, device=dev)
+        scratch = torch.empty((N, 256, 320, 1), dtype=torch.uint8, device=dev)
+
+        def launch_warp():
+            _lib.check(lib.yf_augment_warp_u8(dev.index, src.data_ptr(), 512, 640, 3, None, N, N, None, None, 256, 320, 1, 15, d_prm2.data_ptr(),
+                                              d_warp.data_ptr(), scratch.data_ptr(), None, x.data_ptr(), stream))
+        for _ in range(5):
+            launch_warp()
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(a.reps):
+            launch_warp()
+        e1.record()
+        torch.cuda.synchronize()
+        ms2 = e0.elapsed_time(e1) / a.reps
+        res[N].update(geometric_ms=round(ms2, 4), geometric_over_plain=round(ms2 / ms, 3))
+        print("augment batch %d, geometric keys active (two launches): %.4f ms = %.2f x the plain launch" % (N, ms2, ms2 / ms))
     return res
 
 
@@ -114,10 +145,13 @@ def train_bench():
     d = voc_tree_copies(tmp)
     aug = dict(yf.config_params["augment_params"], train_dataset_dir=d, val_dataset_dir=d)
     loaders = {}
-    for cache in ("device", None):
-        ds = DetectDataset(io["input_shape"], io["origin_img_shape"], None, aug_params=aug, device=dev, cache=cache)
-        loaders["cache=%s" % cache] = DataLoader(ds, batch_size=B, num_workers=0, drop_last=True, pin_memory=True, shuffle=True,
-                                                  collate_fn=val.collate_fn)
+    configs = [("cache=device", aug, dict(cache="device")), ("decode=device", aug, dict(decode="device")), ("cache=None", aug, {})]
+    if hasattr(DetectDataset, "draw_ex"):
+        active = dict(aug, **GEOMETRIC)
+        configs += [("geometric cache=device", active, dict(cache="device")), ("geometric decode=device", active, dict(decode="device"))]
+    for name, params, kw in configs:
+        ds = DetectDataset(io["input_shape"], io["origin_img_shape"], None, aug_params=params, device=dev, **kw)
+        loaders[name] = DataLoader(ds, batch_size=B, num_workers=0, drop_last=True, pin_memory=True, shuffle=True, collate_fn=val.collate_fn)
     x0 = torch.rand(B, 1, 256, 320, device=dev) - 0.5
     t0 = torch.zeros(B, 64, 6, device=dev)
     t0[:, 0] = torch.tensor([0.5, 0.5, 0.1, 0.1, 1.0, 255.0])
@@ -129,7 +163,7 @@ def train_bench():
             else:
                 for imgs, targets in loaders[name]:
                     yield imgs.to(dev).float(), targets.to(dev).float()
-    gens = {n: batches(n) for n in ("cache=device", "cache=None", "no-data")}
+    gens = {n: batches(n) for n in list(loaders) + ["no-data"]}
     for n, g in gens.items():                                        # warm-up: the device cache fills, engines and graphs are built
         for _ in range(20):
             imgs, targets = next(g)
@@ -148,7 +182,11 @@ def train_bench():
     for n, v in res.items():
         print("train batch %d, %s: %.0f examples/s (median of %d rounds: %s)" % (B, n, float(np.median(v)), len(v), ["%.0f" % x for x in v]))
     print("cache=device / no-data = %.3f" % (np.median(res["cache=device"]) / np.median(res["no-data"])))
-    return {n: float(np.median(v)) for n, v in res.items()}
+    for n in ("cache=device", "decode=device"):
+        if "geometric " + n in res:
+            print("geometric %s / %s = %.3f, / cache=None (decode=host) = %.3f" % (
+                n, n, np.median(res["geometric " + n]) / np.median(res[n]), np.median(res["geometric " + n]) / np.median(res["cache=None"])))
+    return {n: {"median": float(np.median(v)), "rounds": [round(float(x), 1) for x in v]} for n, v in res.items()}
 
 
 out = {}

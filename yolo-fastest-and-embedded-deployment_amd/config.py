@@ -29,7 +29,7 @@ config_params = {
     "augment_params": {
         "train_dataset_dir": "./data/train_data/",   # Pascal-VOC trees: <dir>/xml/*.xml, <dir>/img/<stem>.jpg
         "val_dataset_dir": "./data/val_data/",
-        "degrees": 0.0,                     # the reference does not implement these six (detect_dataset.py:131): kept for its config's shape
+        "degrees": 0.0,                     # the reference does not implement these six (detect_dataset.py:131); DetectDataset does (dataset.py): neutral here
         "translate": 0.0,
         "scale": 1.0,
         "shear": 0.0,

@@ -59,7 +59,7 @@ struct AugArgs {
     int mode, gray;               // as CvArgs
     const int4* xtab;             // mode 2
     const int4* ytab;
-    const int* params;            // [n] k (0, 3, 5, 7) | flip << 8
+    const int* params;            // [n] k (0, 3, 5, 7) | flip << 8, or null (no blur, no flip: launch 1 of yf_augment_warp_u8)
     uint8_t* u8;                  // [n, dh, dw, dc] or null
     float* x;                     // [n, dc, dh, dw] or null
     int tr, pitch;                // destination rows per workgroup; LDS row pitch of the u8 tile (bytes, multiple of 16)
@@ -85,6 +85,92 @@ __device__ __forceinline__ int src_px(const uint8_t* __restrict__ row, int x, in
     }
 }
 
+// The row pass (blurred frames only): sum_x k_x * tile, exact in uint16 (at most 255 * 256); tile [T][pitch] -> hb [T][dw * C].
+template <int C>
+__device__ __forceinline__ void blur_rows(const uint8_t* tile, uint16_t* hb, const int* taps, int k, int T, int dw, int pitch)
+{
+    const int re = dw * C;
+    if (k) {
+#pragma unroll 1
+        for (int e = threadIdx.x; e < T * dw; e += 256) {
+            const int r = e / dw, x = e - r * dw;
+            const uint8_t* const tr = tile + r * pitch;
+            int acc[C];
+#pragma unroll
+            for (int c = 0; c < C; ++c) acc[c] = 0;
+#pragma unroll
+            for (int i = 0; i < 7; ++i) {
+                const int xs = reflect101(x + i - AUG_R, dw);
+#pragma unroll
+                for (int c = 0; c < C; ++c) acc[c] += taps[i] * tr[xs * C + c];
+            }
+#pragma unroll
+            for (int c = 0; c < C; ++c) hb[r * re + x * C + c] = (uint16_t)acc[c];
+        }
+        __syncthreads();
+    }
+}
+
+// The column pass + flips + stores of `rows` destination rows from dy0 on, 4 destination pixels per task.  fliplr mirrors the columns
+// read, flipud the row written (dh - 1 - dy): both commute with the blur (symmetric taps, reflect-101).
+template <int C>
+__device__ __forceinline__ void blur_cols_store(const uint8_t* tile, const uint16_t* hb, const int* taps, int k, int n, int dy0, int rows,
+                                                int dh, int dw, int pitch, bool flip, bool flipud, uint8_t* u8, float* xo)
+{
+    const int re = dw * C;
+    const int quads = (dw + 3) >> 2;
+#pragma unroll 1
+    for (int t = threadIdx.x; t < rows * quads; t += 256) {
+        const int r = t / quads, dx0 = (t - r * quads) * 4, dy = flipud ? dh - 1 - (dy0 + r) : dy0 + r;
+        uint32_t packed[C];
+        float fv[C][4];
+#pragma unroll
+        for (int w = 0; w < C; ++w) packed[w] = 0u;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int dx = dx0 + i;
+            if (dx >= dw) break;
+            const int sx = flip ? dw - 1 - dx : dx;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                int v;
+                if (k) {
+                    int acc = 0;
+#pragma unroll
+                    for (int j = 0; j < 7; ++j) acc += taps[j] * (int)hb[(r + j) * re + sx * C + c];
+                    v = (acc + (1 << 15)) >> 16;
+                } else {
+                    v = tile[r * pitch + sx * C + c];
+                }
+                const int kk = i * C + c;
+                packed[kk >> 2] |= (uint32_t)v << (8 * (kk & 3));
+                fv[c][i] = ((float)v - 128.0f) / 255.0f;
+            }
+        }
+        const int nb = dw - dx0 < 4 ? dw - dx0 : 4;
+        if (u8) {
+            uint8_t* o = u8 + (((long)n * dh + dy) * dw + dx0) * C;
+            if (nb == 4 && ((reinterpret_cast<uintptr_t>(o) & 3) == 0)) {
+#pragma unroll
+                for (int w = 0; w < C; ++w) reinterpret_cast<uint32_t*>(o)[w] = packed[w];
+            } else {
+                for (int kk = 0; kk < nb * C; ++kk) o[kk] = (uint8_t)(packed[kk >> 2] >> (8 * (kk & 3)));
+            }
+        }
+        if (xo) {
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                float* o = xo + (((long)n * C + c) * dh + dy) * dw + dx0;
+                if (nb == 4 && ((reinterpret_cast<uintptr_t>(o) & 15) == 0)) {
+                    *reinterpret_cast<float4*>(o) = make_float4(fv[c][0], fv[c][1], fv[c][2], fv[c][3]);
+                } else {
+                    for (int i = 0; i < nb; ++i) o[i] = fv[c][i];
+                }
+            }
+        }
+    }
+}
+
 template <int GRAY, int MODE, int C>
 __global__ void __launch_bounds__(256) aug_kernel(AugArgs a)
 {
@@ -93,7 +179,7 @@ __global__ void __launch_bounds__(256) aug_kernel(AugArgs a)
     const int n = blockIdx.x / groups, dy0 = (blockIdx.x - n * groups) * a.tr;
     const int f = a.index ? a.index[n] : n;
     if (f < 0 || f >= a.n_src) return;                       // an index outside the stack leaves its output frame untouched
-    const int p = a.params[n];
+    const int p = a.params ? a.params[n] : 0;                // no parameters: the resized frame as it is
     const int k = ((p & 15) == 3 || (p & 15) == 5 || (p & 15) == 7) ? (p & 15) : 0;
     const bool flip = (p >> 8) & 1;
     const int* const taps = k ? aug_taps[(k - 3) >> 1] : aug_taps[0];
@@ -105,7 +191,6 @@ __global__ void __launch_bounds__(256) aug_kernel(AugArgs a)
     const int quads = (a.dw + 3) >> 2;
     uint8_t* const tile = aug_smem;                                                              // [T][pitch]
     uint16_t* const hb = reinterpret_cast<uint16_t*>(aug_smem + (size_t)(a.tr + 2 * AUG_R) * a.pitch);   // [T][dw * C]
-    const int re = a.dw * C;
 
     // ---- stage: cvtColor + resize of the tile's rows, 4 destination pixels (all channels) per task, one 4-byte LDS store per channel ----
 #pragma unroll 1
@@ -150,78 +235,124 @@ __global__ void __launch_bounds__(256) aug_kernel(AugArgs a)
     }
     __syncthreads();
 
-    // ---- row pass (blurred frames only): sum_x k_x * tile, exact in uint16 (at most 255 * 256) ----
-    if (k) {
-#pragma unroll 1
-        for (int e = threadIdx.x; e < T * a.dw; e += 256) {
-            const int r = e / a.dw, x = e - r * a.dw;
-            const uint8_t* const tr = tile + r * a.pitch;
-            int acc[C];
+    blur_rows<C>(tile, hb, taps, k, T, a.dw, a.pitch);
+    blur_cols_store<C>(tile, hb, taps, k, n, dy0, rows, a.dh, a.dw, a.pitch, flip, false, a.u8, a.x);
+}
+
+// ---- the geometric warp (yf_augment_warp_u8): launch 2, over the resized (gray) frames launch 1 left in the scratch ----
+struct WarpArgs {
+    const uint8_t* img;           // [n, dh, dw, C] the resized frames (aug_kernel without parameters)
+    const int* index;             // as AugArgs: a frame whose index is outside the stack was not resized and is left untouched here too
+    int n_src, n, dh, dw;
+    const int* params;            // [n] k | fliplr << 8 | flipud << 9 | warp << 10 | perspective << 11
+    const double* warp;           // [n, 8] output -> input coefficients (read for frames with bit 10)
+    uint8_t* u8;
+    float* x;
+    int tr, pitch;
+};
+constexpr int WARP_FILL = 114;    // yolov5's border value, every channel
+
+// One bilinear sample, Pillow's arithmetic (src/libImaging/Geometry.c: affine_transform / perspective_transform + bilinear_filter8) in
+// IEEE double, one rounding per operation: no contraction into FMAs, and the correctly rounded division (no fast-math).  -> false: fill.
+template <int C>
+__device__ __forceinline__ bool warp_sample(const uint8_t* __restrict__ img, int dh, int dw, const double (&m)[8], bool persp, int x, int y,
+                                            int (&v)[C])
+{
+#pragma clang fp contract(off)
+    const double xin = x + 0.5, yin = y + 0.5;
+    double sx = (m[0] * xin + m[1] * yin) + m[2];
+    double sy = (m[3] * xin + m[4] * yin) + m[5];
+    if (persp) {
+        const double den = (m[6] * xin + m[7] * yin) + 1.0;
+        sx = sx / den;
+        sy = sy / den;
+    }
+    if (!(sx >= 0.0 && sx < dw && sy >= 0.0 && sy < dh)) return false;    // a NaN fills as well
+    sx -= 0.5;
+    sy -= 0.5;
+    const double fx = floor(sx), fy = floor(sy);
+    const double ddx = sx - fx, ddy = sy - fy;
+    const int x0 = (int)fx, y0 = (int)fy;                                 // -1 .. dw - 1, -1 .. dh - 1
+    const int xa = max(x0, 0), xb = min(x0 + 1, dw - 1);
+    const uint8_t* const r0 = img + ((long)max(y0, 0) * dw) * C;
+    const bool below = y0 + 1 < dh;                                       // y0 + 1 >= 0 always
+    const uint8_t* const r1 = img + ((long)(below ? y0 + 1 : 0) * dw) * C;
 #pragma unroll
-            for (int c = 0; c < C; ++c) acc[c] = 0;
-#pragma unroll
-            for (int i = 0; i < 7; ++i) {
-                const int xs = reflect101(x + i - AUG_R, a.dw);
-#pragma unroll
-                for (int c = 0; c < C; ++c) acc[c] += taps[i] * tr[xs * C + c];
-            }
-#pragma unroll
-            for (int c = 0; c < C; ++c) hb[r * re + x * C + c] = (uint16_t)acc[c];
+    for (int c = 0; c < C; ++c) {
+        const int a0 = r0[xa * C + c], b0 = r0[xb * C + c];
+        const double v1 = (double)a0 + (double)(b0 - a0) * ddx;
+        double v2 = v1;
+        if (below) {
+            const int a1 = r1[xa * C + c], b1 = r1[xb * C + c];
+            v2 = (double)a1 + (double)(b1 - a1) * ddx;
         }
-        __syncthreads();
+        v[c] = (int)(v1 + (v2 - v1) * ddy);                               // (uint8)v: a truncation; 0 <= v <= 255
+    }
+    return true;
+}
+
+// Built like aug_kernel: one workgroup owns `tr` destination rows of one frame and stages them plus the blur halo (reflect-101 on the
+// WARPED image) in LDS, each staged pixel a bilinear sample of the resized frame (or that frame's own pixel without bit 10: then the
+// bytes are yf_augment_u8's); the blur passes are aug_kernel's; both flips at the store.
+template <int C>
+__global__ void __launch_bounds__(256) warp_kernel(WarpArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t aug_smem[];
+    const int groups = (a.dh + a.tr - 1) / a.tr;
+    const int n = blockIdx.x / groups, dy0 = (blockIdx.x - n * groups) * a.tr;
+    const int f = a.index ? a.index[n] : n;
+    if (f < 0 || f >= a.n_src) return;
+    const int p = a.params[n];
+    const int k = ((p & 15) == 3 || (p & 15) == 5 || (p & 15) == 7) ? (p & 15) : 0;
+    const bool fliplr = (p >> 8) & 1, flipud = (p >> 9) & 1, warped = (p >> 10) & 1, persp = (p >> 11) & 1;
+    const int* const taps = k ? aug_taps[(k - 3) >> 1] : aug_taps[0];
+    const int rows = min(a.tr, a.dh - dy0);
+    const int halo = k ? AUG_R : 0;
+    const int T = rows + 2 * halo;
+    const uint8_t* const img = a.img + (long)n * a.dh * a.dw * C;
+    const int quads = (a.dw + 3) >> 2;
+    uint8_t* const tile = aug_smem;                                                              // [T][pitch]
+    uint16_t* const hb = reinterpret_cast<uint16_t*>(aug_smem + (size_t)(a.tr + 2 * AUG_R) * a.pitch);   // [T][dw * C]
+    double m[8] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0};
+    if (warped) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) m[i] = a.warp[(long)n * 8 + i];
     }
 
-    // ---- column pass + flip + stores: 4 destination pixels per task ----
+    // ---- stage: 4 destination pixels (all channels) per task, one 4-byte LDS store per channel ----
 #pragma unroll 1
-    for (int t = threadIdx.x; t < rows * quads; t += 256) {
-        const int r = t / quads, dx0 = (t - r * quads) * 4, dy = dy0 + r;
+    for (int t = threadIdx.x; t < T * quads; t += 256) {
+        const int r = t / quads, dx0 = (t - r * quads) * 4;
+        const int y = reflect101(dy0 - halo + r, a.dh);
         uint32_t packed[C];
-        float fv[C][4];
 #pragma unroll
         for (int w = 0; w < C; ++w) packed[w] = 0u;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int dx = dx0 + i;
             if (dx >= a.dw) break;
-            const int sx = flip ? a.dw - 1 - dx : dx;
+            int v[C];
+            if (!warped) {
+#pragma unroll
+                for (int c = 0; c < C; ++c) v[c] = img[((long)y * a.dw + dx) * C + c];
+            } else if (!warp_sample<C>(img, a.dh, a.dw, m, persp, dx, y, v)) {
+#pragma unroll
+                for (int c = 0; c < C; ++c) v[c] = WARP_FILL;
+            }
 #pragma unroll
             for (int c = 0; c < C; ++c) {
-                int v;
-                if (k) {
-                    int acc = 0;
-#pragma unroll
-                    for (int j = 0; j < 7; ++j) acc += taps[j] * (int)hb[(r + j) * re + sx * C + c];
-                    v = (acc + (1 << 15)) >> 16;
-                } else {
-                    v = tile[r * a.pitch + sx * C + c];
-                }
                 const int kk = i * C + c;
-                packed[kk >> 2] |= (uint32_t)v << (8 * (kk & 3));
-                fv[c][i] = ((float)v - 128.0f) / 255.0f;
+                packed[kk >> 2] |= (uint32_t)(v[c] & 255) << (8 * (kk & 3));
             }
         }
-        const int nb = a.dw - dx0 < 4 ? a.dw - dx0 : 4;
-        if (a.u8) {
-            uint8_t* o = a.u8 + (((long)n * a.dh + dy) * a.dw + dx0) * C;
-            if (nb == 4 && ((reinterpret_cast<uintptr_t>(o) & 3) == 0)) {
+        uint32_t* const o = reinterpret_cast<uint32_t*>(tile + r * a.pitch + dx0 * C);
 #pragma unroll
-                for (int w = 0; w < C; ++w) reinterpret_cast<uint32_t*>(o)[w] = packed[w];
-            } else {
-                for (int kk = 0; kk < nb * C; ++kk) o[kk] = (uint8_t)(packed[kk >> 2] >> (8 * (kk & 3)));
-            }
-        }
-        if (a.x) {
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                float* o = a.x + (((long)n * C + c) * a.dh + dy) * a.dw + dx0;
-                if (nb == 4 && ((reinterpret_cast<uintptr_t>(o) & 15) == 0)) {
-                    *reinterpret_cast<float4*>(o) = make_float4(fv[c][0], fv[c][1], fv[c][2], fv[c][3]);
-                } else {
-                    for (int i = 0; i < nb; ++i) o[i] = fv[c][i];
-                }
-            }
-        }
+        for (int w = 0; w < C; ++w) o[w] = packed[w];
     }
+    __syncthreads();
+
+    blur_rows<C>(tile, hb, taps, k, T, a.dw, a.pitch);
+    blur_cols_store<C>(tile, hb, taps, k, n, dy0, rows, a.dh, a.dw, a.pitch, fliplr, flipud, a.u8, a.x);
 }
 
 template <int GRAY, int C>
@@ -231,6 +362,50 @@ void launch_aug_mode(const AugArgs& a, size_t lds, hipStream_t s)
     if (a.mode == 0) hipLaunchKernelGGL((aug_kernel<GRAY, 0, C>), dim3(grid), dim3(256), lds, s, a);
     else if (a.mode == 1) hipLaunchKernelGGL((aug_kernel<GRAY, 1, C>), dim3(grid), dim3(256), lds, s, a);
     else hipLaunchKernelGGL((aug_kernel<GRAY, 2, C>), dim3(grid), dim3(256), lds, s, a);
+}
+
+// The arguments yf_augment_u8 and yf_augment_warp_u8 share, checked, into AugArgs (parameters left to the caller) + the LDS bytes of a
+// workgroup; `who` names the entry in the messages.
+int aug_setup(const char* who, const uint8_t* d_src, int src_h, int src_w, int src_c, const int* d_index, int n_src, int N, const void* d_xtab,
+              const void* d_ytab, int dst_h, int dst_w, int dst_c, int gray_bits, uint8_t* d_u8, float* d_x, AugArgs& a, size_t& lds)
+{
+    if (!d_src || (!d_u8 && !d_x) || N <= 0 || n_src <= 0 || (!d_index && n_src < N))
+        return fail(YF_E_INVALID, "%s: null pointer, no output, N <= 0 or fewer source frames than N without an index table", who);
+    if (src_h <= 0 || src_w <= 0 || src_h > 16384 || src_w > 16384 || dst_h <= 0 || dst_w <= 0 || dst_h > 16384 || dst_w > 16384)
+        return fail(YF_E_INVALID, "%s: source %dx%d / destination %dx%d", who, src_h, src_w, dst_h, dst_w);
+    a.src = d_src; a.index = d_index; a.n_src = n_src; a.n = N; a.sh = src_h; a.sw = src_w; a.sc = src_c; a.dh = dst_h; a.dw = dst_w; a.dc = dst_c;
+    a.u8 = d_u8; a.x = d_x;
+    if (src_c == 3 && dst_c == 1) {
+        if (gray_bits != 0 && gray_bits != 14 && gray_bits != 15) return fail(YF_E_INVALID, "gray_bits must be 14, 15 or 0 (= 15)");
+        a.gray = gray_bits == 14 ? 14 : 15;
+    } else if (src_c == dst_c && (src_c == 1 || src_c == 3)) {
+        a.gray = 0;
+    } else {
+        return fail(YF_E_INVALID, "%s: %d-channel frames from %d-channel sources (gray from BGR, or 1 / 3 channels as they are)", who, dst_c, src_c);
+    }
+    a.mode = (src_h == dst_h && src_w == dst_w) ? 0 : (src_h == 2 * dst_h && src_w == 2 * dst_w) ? 1 : 2;
+    if (a.mode == 2) {
+        if (!d_xtab || !d_ytab) return fail(YF_E_INVALID, "%s: a %dx%d -> %dx%d resize needs the tables of yf_cv_resize_tables", who, src_h, src_w, dst_h, dst_w);
+        a.xtab = static_cast<const int4*>(d_xtab); a.ytab = static_cast<const int4*>(d_ytab);
+    }
+    const int quads = (dst_w + 3) >> 2;
+    a.pitch = (quads * 4 * dst_c + 15) & ~15;
+    const long per_row = (long)a.pitch + 2L * dst_w * dst_c;   // u8 tile row + uint16 row-pass row
+    const long tr = AUG_LDS / per_row - 2 * AUG_R;
+    if (tr < 1) return fail(YF_E_INVALID, "%s: rows of %d x %d bytes do not fit the LDS tile", who, dst_w, dst_c);
+    a.tr = tr < AUG_MAX_TR ? (int)tr : AUG_MAX_TR;
+    lds = (size_t)(a.tr + 2 * AUG_R) * per_row;
+    const long groups = (long)N * ((dst_h + a.tr - 1) / a.tr);
+    if (groups > 0x7fffffffL) return fail(YF_E_INVALID, "%s: batch too large for one launch", who);
+    return YF_OK;
+}
+
+void launch_aug(const AugArgs& a, size_t lds, hipStream_t s)
+{
+    if (a.gray == 14) launch_aug_mode<14, 1>(a, lds, s);
+    else if (a.gray == 15) launch_aug_mode<15, 1>(a, lds, s);
+    else if (a.dc == 1) launch_aug_mode<0, 1>(a, lds, s);
+    else launch_aug_mode<0, 3>(a, lds, s);
 }
 
 }  // namespace
@@ -250,41 +425,40 @@ int yf_cv_resize_tables(int device, int src_h, int src_w, int dst_h, int dst_w, 
 int yf_augment_u8(int device, const uint8_t* d_src, int src_h, int src_w, int src_c, const int* d_index, int n_src, int N, const void* d_xtab,
                   const void* d_ytab, int dst_h, int dst_w, int dst_c, int gray_bits, const int* d_params, uint8_t* d_u8, float* d_x, void* stream)
 {
-    if (!d_src || !d_params || (!d_u8 && !d_x) || N <= 0 || n_src <= 0 || (!d_index && n_src < N))
-        return fail(YF_E_INVALID, "yf_augment_u8: null pointer, no output, N <= 0 or fewer source frames than N without an index table");
-    if (src_h <= 0 || src_w <= 0 || src_h > 16384 || src_w > 16384 || dst_h <= 0 || dst_w <= 0 || dst_h > 16384 || dst_w > 16384)
-        return fail(YF_E_INVALID, "yf_augment_u8: source %dx%d / destination %dx%d", src_h, src_w, dst_h, dst_w);
     AugArgs a{};
-    a.src = d_src; a.index = d_index; a.n_src = n_src; a.n = N; a.sh = src_h; a.sw = src_w; a.sc = src_c; a.dh = dst_h; a.dw = dst_w; a.dc = dst_c;
-    a.params = d_params; a.u8 = d_u8; a.x = d_x;
-    if (src_c == 3 && dst_c == 1) {
-        if (gray_bits != 0 && gray_bits != 14 && gray_bits != 15) return fail(YF_E_INVALID, "gray_bits must be 14, 15 or 0 (= 15)");
-        a.gray = gray_bits == 14 ? 14 : 15;
-    } else if (src_c == dst_c && (src_c == 1 || src_c == 3)) {
-        a.gray = 0;
-    } else {
-        return fail(YF_E_INVALID, "yf_augment_u8: %d-channel frames from %d-channel sources (gray from BGR, or 1 / 3 channels as they are)", dst_c, src_c);
-    }
-    a.mode = (src_h == dst_h && src_w == dst_w) ? 0 : (src_h == 2 * dst_h && src_w == 2 * dst_w) ? 1 : 2;
-    if (a.mode == 2) {
-        if (!d_xtab || !d_ytab) return fail(YF_E_INVALID, "yf_augment_u8: a %dx%d -> %dx%d resize needs the tables of yf_cv_resize_tables", src_h, src_w, dst_h, dst_w);
-        a.xtab = static_cast<const int4*>(d_xtab); a.ytab = static_cast<const int4*>(d_ytab);
-    }
-    const int quads = (dst_w + 3) >> 2;
-    a.pitch = (quads * 4 * dst_c + 15) & ~15;
-    const long per_row = (long)a.pitch + 2L * dst_w * dst_c;   // u8 tile row + uint16 row-pass row
-    const long tr = AUG_LDS / per_row - 2 * AUG_R;
-    if (tr < 1) return fail(YF_E_INVALID, "yf_augment_u8: rows of %d x %d bytes do not fit the LDS tile", dst_w, dst_c);
-    a.tr = tr < AUG_MAX_TR ? (int)tr : AUG_MAX_TR;
-    const size_t lds = (size_t)(a.tr + 2 * AUG_R) * per_row;
-    const long groups = (long)N * ((dst_h + a.tr - 1) / a.tr);
-    if (groups > 0x7fffffffL) return fail(YF_E_INVALID, "yf_augment_u8: batch too large for one launch");
+    size_t lds;
+    if (!d_params) return fail(YF_E_INVALID, "yf_augment_u8: null d_params");
+    const int rc = aug_setup("yf_augment_u8", d_src, src_h, src_w, src_c, d_index, n_src, N, d_xtab, d_ytab, dst_h, dst_w, dst_c, gray_bits, d_u8, d_x,
+                             a, lds);
+    if (rc != YF_OK) return rc;
+    a.params = d_params;
+    HIP_OK(hipSetDevice(device));
+    launch_aug(a, lds, (hipStream_t)stream);
+    HIP_OK(hipGetLastError());
+    return YF_OK;
+}
+
+int yf_augment_warp_u8(int device, const uint8_t* d_src, int src_h, int src_w, int src_c, const int* d_index, int n_src, int N, const void* d_xtab,
+                       const void* d_ytab, int dst_h, int dst_w, int dst_c, int gray_bits, const int* d_params, const double* d_warp,
+                       uint8_t* d_scratch, uint8_t* d_u8, float* d_x, void* stream)
+{
+    AugArgs a{};
+    size_t lds;
+    if (!d_params || !d_warp || !d_scratch) return fail(YF_E_INVALID, "yf_augment_warp_u8: null d_params, d_warp or d_scratch");
+    const int rc = aug_setup("yf_augment_warp_u8", d_src, src_h, src_w, src_c, d_index, n_src, N, d_xtab, d_ytab, dst_h, dst_w, dst_c, gray_bits,
+                             d_u8, d_x, a, lds);
+    if (rc != YF_OK) return rc;
+    WarpArgs w{};
+    w.img = d_scratch; w.index = d_index; w.n_src = n_src; w.n = N; w.dh = dst_h; w.dw = dst_w; w.params = d_params; w.warp = d_warp;
+    w.u8 = d_u8; w.x = d_x; w.tr = a.tr; w.pitch = a.pitch;
+    a.params = nullptr; a.u8 = d_scratch; a.x = nullptr;      // launch 1: gray + resize alone, into the scratch
     HIP_OK(hipSetDevice(device));
     const hipStream_t s = (hipStream_t)stream;
-    if (a.gray == 14) launch_aug_mode<14, 1>(a, lds, s);
-    else if (a.gray == 15) launch_aug_mode<15, 1>(a, lds, s);
-    else if (dst_c == 1) launch_aug_mode<0, 1>(a, lds, s);
-    else launch_aug_mode<0, 3>(a, lds, s);
+    launch_aug(a, lds, s);
+    HIP_OK(hipGetLastError());
+    const unsigned grid = (unsigned)((long)N * ((dst_h + a.tr - 1) / a.tr));
+    if (dst_c == 1) hipLaunchKernelGGL((warp_kernel<1>), dim3(grid), dim3(256), lds, s, w);
+    else hipLaunchKernelGGL((warp_kernel<3>), dim3(grid), dim3(256), lds, s, w);
     HIP_OK(hipGetLastError());
     return YF_OK;
 }

@@ -15,11 +15,18 @@ decode call per source size for a batch's frames, or for the frames a batch adds
 refused otherwise) and `__getitems__`, which DataLoader calls with a whole batch of indices: the same draws in
 index order, ONE launch per source size, float32 device images [N, C, H, W] = collate_fn's `(u8 - 128.0) / 255` bit for bit.
 
+Beyond the reference: the geometric keys of `augment_params` -- `degrees`, `translate`, `scale`, `shear`, `perspective`, `flipud` --, which
+the reference reads nowhere, are honoured as yolov5's random_perspective (draw_ex, _draw_warp, _warp_labels): the warp runs on the device
+between the resize and the blur (`yf_augment_warp_u8`; pixels pinned to Pillow's Image.transform with BILINEAR and fill 114; OpenCV parity
+not claimed), the vertical flip after the horizontal one.  At their neutral values (the reference's _config.py: 0, 0, 1.0, 0, 0, 0) or
+absent, draws, labels, launch and bytes are the reference's.  `mixup` stays ignored.
+
 Deviation: the reference cannot return an image without objects -- `np.array([])` is 1-D, so a flip raises IndexError (`labels[:, 1]`,
 :143) and otherwise the box copy raises ValueError (:159); here such an image is blurred / flipped as drawn and gets all-zero boxes (the
 draws stay in the reference's order, so the items after it are the reference's)."""
 import ctypes
 import logging
+import math
 import os
 import random
 import xml.etree.ElementTree as xmlET
@@ -85,6 +92,22 @@ class DetectDataset(torch.utils.data.Dataset):
             self.dataset_dir = aug_params["train_dataset_dir"]
         self.fliplr = aug_params["fliplr"]
         self.gussian_filter = aug_params["gussian_filter"]
+        # yolov5's geometric keys (absent = the reference's _config.py value = neutral); `mixup` stays ignored
+        self.degrees = float(aug_params.get("degrees", 0.0))
+        self.translate = float(aug_params.get("translate", 0.0))
+        self.scale = float(aug_params.get("scale", 1.0))
+        self.shear = float(aug_params.get("shear", 0.0))
+        self.perspective = float(aug_params.get("perspective", 0.0))
+        self.flipud = aug_params.get("flipud", 0.0)
+        if not 0.0 < self.scale < 2.0:
+            raise ValueError("augment_params['scale'] must lie inside (0, 2): the gain is drawn from 1 -+ |scale - 1|")
+        for key in ("degrees", "shear", "perspective"):
+            if not getattr(self, key) >= 0.0:
+                raise ValueError("augment_params[%r] must not be negative: it is the far end of a range around 0" % key)
+        if not 0.0 <= self.translate < 1.0:
+            raise ValueError("augment_params['translate'] must lie inside [0, 1)")
+        self.geometric = bool(augment) and (self.degrees != 0.0 or self.translate != 0.0 or self.scale != 1.0 or self.shear != 0.0
+                                            or self.perspective != 0.0)
         self.max_boxes = max_boxes
         self.augment = augment
         self.gray_bits = gray_bits
@@ -127,14 +150,82 @@ class DetectDataset(torch.utils.data.Dataset):
     # ---- labels and draws (host; no GPU needed) ----
     def draw(self, index):
         """The host half of __getitem__ (:126-160): the label arithmetic and the random draws of one item, in the reference's order.
-        -> (blur kernel size: 0, 3 or 7; flip; float64 boxes [max_boxes, 6])."""
+        -> (blur kernel size: 0, 3 or 7; flip; float64 boxes [max_boxes, 6]).  draw_ex returns the geometric draws as well."""
+        return self.draw_ex(index)[:3]
+
+    def _draw_warp(self):
+        """yolov5's random_perspective matrix for one item, in continuous pixel coordinates of the net-input image (pixel centres at
+        half-integers, as Pillow places them and as the normalised labels mean): M = T S R P C in float64, from eight random.uniform draws
+        (perspective x, y, angle, gain, shear x, y, translate x, y; all made even where a range is zero).
+        -> (M, gain, the eight coefficients of the output -> input map: inv(M) / inv(M)[2, 2]).
+        A draw whose denominator a6 x + a7 y + 1 is not positive at all four corners of the output (the image would fold over) is
+        REDRAWN, all eight values; after 100 such draws in a row the configured `perspective` is refused with a ValueError."""
+        H, W = self.input_shape[0], self.input_shape[1]
+        g = abs(self.scale - 1.0)
+        for _ in range(100):
+            C = np.eye(3)
+            C[0, 2], C[1, 2] = -W / 2, -H / 2
+            P = np.eye(3)
+            P[2, 0] = random.uniform(-self.perspective, self.perspective)
+            P[2, 1] = random.uniform(-self.perspective, self.perspective)
+            a = math.radians(random.uniform(-self.degrees, self.degrees))
+            gain = random.uniform(1 - g, 1 + g)
+            R = np.eye(3)
+            R[0, 0], R[0, 1], R[1, 0], R[1, 1] = gain * math.cos(a), gain * math.sin(a), -gain * math.sin(a), gain * math.cos(a)
+            S = np.eye(3)
+            S[0, 1] = math.tan(math.radians(random.uniform(-self.shear, self.shear)))
+            S[1, 0] = math.tan(math.radians(random.uniform(-self.shear, self.shear)))
+            T = np.eye(3)
+            T[0, 2] = random.uniform(0.5 - self.translate, 0.5 + self.translate) * W
+            T[1, 2] = random.uniform(0.5 - self.translate, 0.5 + self.translate) * H
+            M = T @ S @ R @ P @ C
+            inv = np.linalg.inv(M)
+            coeffs = (inv / inv[2, 2]).reshape(9)[:8].copy()
+            if self.perspective == 0:
+                coeffs[6:] = 0.0                    # an affine frame: exactly, whatever the inverse's rounding left there
+            if all(coeffs[6] * x + coeffs[7] * y + 1 > 0 for x in (0, W) for y in (0, H)):
+                return M, gain, coeffs
+        raise ValueError("augment_params['perspective'] = %r folds the %dx%d image over in 100 draws out of 100" % (self.perspective, W, H))
+
+    def _warp_labels(self, labels, M, gain):
+        """yolov5's label half of random_perspective on normalised (cls, xc, yc, w, h) rows: the four corners of each box through M (with
+        the perspective divide), min / max as the new box, clipped to the image; box_candidates keeps a box whose width and height are
+        both above 2 pixels, whose area is above 0.1 of the old one times gain^2 and whose aspect ratio is below 20.  float64."""
+        H, W = self.input_shape[0], self.input_shape[1]
+        x1, x2 = (labels[:, 1] - labels[:, 3] / 2) * W, (labels[:, 1] + labels[:, 3] / 2) * W
+        y1, y2 = (labels[:, 2] - labels[:, 4] / 2) * H, (labels[:, 2] + labels[:, 4] / 2) * H
+        n = len(labels)
+        xy = np.ones((n * 4, 3))
+        xy[:, 0] = np.stack([x1, x2, x1, x2], 1).reshape(-1)
+        xy[:, 1] = np.stack([y1, y2, y2, y1], 1).reshape(-1)
+        xy = xy @ M.T
+        xy = (xy[:, :2] / xy[:, 2:3]).reshape(n, 4, 2)
+        nx1, nx2 = xy[:, :, 0].min(1).clip(0, W), xy[:, :, 0].max(1).clip(0, W)
+        ny1, ny2 = xy[:, :, 1].min(1).clip(0, H), xy[:, :, 1].max(1).clip(0, H)
+        w1, h1 = (x2 - x1) * gain, (y2 - y1) * gain
+        w2, h2 = nx2 - nx1, ny2 - ny1
+        ar = np.maximum(w2 / (h2 + 1e-16), h2 / (w2 + 1e-16))
+        keep = (w2 > 2) & (h2 > 2) & (w2 * h2 / (w1 * h1 + 1e-16) > 0.1) & (ar < 20)
+        out = labels.copy()
+        out[:, 1], out[:, 2], out[:, 3], out[:, 4] = (nx1 + nx2) / 2 / W, (ny1 + ny2) / 2 / H, w2 / W, h2 / H
+        return out[keep]
+
+    def draw_ex(self, index):
+        """draw() with the geometric part: -> (k, flip, boxes, flipud, coeffs), coeffs the eight float64 output -> input coefficients of
+        the item's warp, or None while the geometric keys are neutral.  Draws: [eight for the warp, when any of degrees / translate /
+        scale / shear / perspective is set], blur?, which blur, fliplr?, [flipud?, when flipud > 0].  Labels: the reference's
+        normalisation, the warp (boxes it drops are compacted out before the max_boxes fill), x = 1 - x for fliplr, y = 1 - y for flipud."""
         labels = np.array(self.dataset_dict[self.img_list[index]])
         if len(labels):
             labels[:, 1:5] = xyxy2xywh(labels[:, 1:5])
             labels[:, [2, 4]] /= self.origin_img_shape[0]
             labels[:, [1, 3]] /= self.origin_img_shape[1]
-        k, flip = 0, False
+        k, flip, flipud, coeffs = 0, False, False, None
         if self.augment:
+            if self.geometric:
+                M, gain, coeffs = self._draw_warp()
+                if len(labels):
+                    labels = self._warp_labels(labels, M, gain)
             if random.random() < self.gussian_filter:
                 _ret = random.random()
                 k = 7 if _ret < 0.4 else 3          # the reference's `elif _ret < 0.2` (5 x 5) cannot be reached
@@ -142,6 +233,10 @@ class DetectDataset(torch.utils.data.Dataset):
                 flip = True
                 if len(labels):                     # deviation: no IndexError for an image without objects (nor ValueError below)
                     labels[:, 1] = 1 - labels[:, 1]
+            if self.flipud > 0 and random.random() < self.flipud:
+                flipud = True
+                if len(labels):
+                    labels[:, 2] = 1 - labels[:, 2]
         nL = len(labels)
         if nL:
             cls_id = labels[:, 0].copy()
@@ -152,7 +247,7 @@ class DetectDataset(torch.utils.data.Dataset):
         if m:                                       # deviation: the reference's copy raises ValueError for no objects
             out[:m, 0:5] = labels[:m]
             out[:m, 5] = 255.0
-        return k, flip, out
+        return k, flip, out, flipud, coeffs
 
     # ---- images (GPU) ----
     def _need_gpu(self):
@@ -251,7 +346,8 @@ class DetectDataset(torch.utils.data.Dataset):
         return t.data_ptr(), t.data_ptr() + W * 16
 
     def augment_images(self, indices, params, out_u8=False):
-        """The frames `indices` with per-frame (k, flip) `params` through yf_augment_u8, one launch per source size.
+        """The frames `indices` with per-frame `params` -- (k, flip) or (k, flip, flipud, coeffs), draw_ex's values -- through
+        yf_augment_u8, one launch per source size; a size group with a warped or flipud frame goes through yf_augment_warp_u8 (two).
         -> float32 device [N, C, H, W] ((v - 128) / 255), or uint8 device [N, H, W, C] with out_u8."""
         self._need_gpu()
         H, W, C = self.input_shape
@@ -259,7 +355,12 @@ class DetectDataset(torch.utils.data.Dataset):
         dev = self.device
         stream = torch.cuda.current_stream(dev).cuda_stream
         out = torch.empty((N, H, W, C) if out_u8 else (N, C, H, W), dtype=torch.uint8 if out_u8 else torch.float32, device=dev)
-        packed = [int(k) | (int(bool(f)) << 8) for k, f in params]
+        packed, warps = [], []
+        for k, f, *rest in params:
+            ud, coeffs = rest if rest else (False, None)
+            warps.append(coeffs)
+            packed.append(int(k) | (int(bool(f)) << 8) | (int(bool(ud)) << 9) |
+                          (0 if coeffs is None else (1 << 10) | (int(coeffs[6] != 0 or coeffs[7] != 0) << 11)))
         if self.cache == "device":
             groups = self._from_cache(indices)
         elif self.decode == "device":
@@ -274,9 +375,16 @@ class DetectDataset(torch.utils.data.Dataset):
             whole = len(groups) == 1
             dst = out if whole else torch.empty((len(pos),) + tuple(out.shape[1:]), dtype=out.dtype, device=dev)
             xt, yt = self._resize_tables(hw, stream)
-            _lib.check(lib.yf_augment_u8(dev.index, stack.data_ptr(), hw[0], hw[1], 3, None if index is None else index.data_ptr(),
-                                         stack.shape[0], len(pos), xt, yt, H, W, C, self.gray_bits, prm.data_ptr(),
-                                         dst.data_ptr() if out_u8 else None, None if out_u8 else dst.data_ptr(), ctypes.c_void_p(stream)))
+            head = (dev.index, stack.data_ptr(), hw[0], hw[1], 3, None if index is None else index.data_ptr(), stack.shape[0], len(pos), xt, yt,
+                    H, W, C, self.gray_bits, prm.data_ptr())
+            tail = (dst.data_ptr() if out_u8 else None, None if out_u8 else dst.data_ptr(), ctypes.c_void_p(stream))
+            if any(packed[p] >> 9 for p in pos):
+                neutral = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0)
+                warp = torch.tensor([neutral if warps[p] is None else [float(v) for v in warps[p]] for p in pos], dtype=torch.float64).to(dev)
+                scratch = torch.empty((len(pos), H, W, C), dtype=torch.uint8, device=dev)
+                _lib.check(lib.yf_augment_warp_u8(*head, warp.data_ptr(), scratch.data_ptr(), *tail))
+            else:
+                _lib.check(lib.yf_augment_u8(*head, *tail))
             if not whole:
                 out.index_copy_(0, torch.tensor(pos, device=dev), dst)
         return out
@@ -284,8 +392,8 @@ class DetectDataset(torch.utils.data.Dataset):
     def __getitem__(self, index):
         """The reference's item: (float64 [H, W, C] image u8 - 128.0, float64 [max_boxes, 6] boxes)."""
         self._need_gpu()
-        k, flip, boxes = self.draw(index)
-        u8 = self.augment_images([index], [(k, flip)], out_u8=True)[0].cpu().numpy()
+        k, flip, boxes, flipud, coeffs = self.draw_ex(index)
+        u8 = self.augment_images([index], [(k, flip, flipud, coeffs)], out_u8=True)[0].cpu().numpy()
         img = u8 - 128.0
         return np.ascontiguousarray(img), boxes
 
@@ -294,9 +402,9 @@ class DetectDataset(torch.utils.data.Dataset):
         -> DetectBatch(float32 device [N, C, H, W], float64 host [N, max_boxes, 6]); collate_fn passes it through."""
         self._need_gpu()
         indices = [int(i) for i in indices]
-        draws = [self.draw(i) for i in indices]
-        imgs = self.augment_images(indices, [(k, f) for k, f, _ in draws])
-        targets = torch.from_numpy(np.stack([b for _, _, b in draws])) if draws else torch.zeros((0, self.max_boxes, 6), dtype=torch.float64)
+        draws = [self.draw_ex(i) for i in indices]
+        imgs = self.augment_images(indices, [(k, f, ud, coeffs) for k, f, _, ud, coeffs in draws])
+        targets = torch.from_numpy(np.stack([d[2] for d in draws])) if draws else torch.zeros((0, self.max_boxes, 6), dtype=torch.float64)
         return DetectBatch(imgs, targets)
 
     @staticmethod
