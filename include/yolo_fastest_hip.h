@@ -136,7 +136,8 @@ int yf_nms_sorted(yf_handle h, const int32_t *d_boxes, int n, double nms_thres, 
  *       d_pred float32 [N,M,5+C] (yf_val_nms: C = the engine's num_cls; yf_val_nms_ex: C = num_classes, the reference's argument);
  *       conf >= conf_thres, per-class greedy NMS, IoU with the +1 convention, keep iou < nms_thres;
  *       d_det float32 [N,K_max,7] = (x1,y1,x2,y2,obj_conf,class_conf,class_pred), class-ascending then conf-descending;
- *       d_counts int32 [N] = true number of detections (0 <=> the reference's None). */
+ *       d_counts int32 [N] = true number of detections (0 <=> the reference's None);
+ *       M <= 8191 and num_classes < 2^18 (the fields of the 64-bit sort key), else YF_E_INVALID; equal confidences keep row order. */
 int yf_val_decode_head(yf_handle h, const float *d_head, int N, int fh, int fw, const double *anchors, int M_total, int m_off,
                        float *d_out, void *stream);
 int yf_val_nms(yf_handle h, const float *d_pred, int N, int M, double conf_thres, double nms_thres, int K_max, float *d_det,

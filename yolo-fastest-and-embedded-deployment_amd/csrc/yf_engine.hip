@@ -1285,6 +1285,7 @@ int yf_val_nms_ex(yf_handle h, const float* d_pred, int N, int M, int num_classe
     HIP_OK(hipSetDevice(h->device));
     int rc = yf::launch_val_nms(d_pred, N, M, num_classes, (float)conf_thres, (float)nms_thres, K_max, d_det, d_counts, (hipStream_t)stream);
     if (rc == -1) return fail(YF_E_INVALID, "yf_val_nms: at most 8191 boxes per image");
+    if (rc == -3) return fail(YF_E_INVALID, "yf_val_nms: at most 262143 classes");
     if (rc) return fail(YF_E_HIP, "hipFuncSetAttribute(val_nms_kernel) failed");
     HIP_OK(hipGetLastError());
     return YF_OK;

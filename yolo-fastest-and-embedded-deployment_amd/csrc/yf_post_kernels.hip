@@ -647,7 +647,8 @@ __global__ void __launch_bounds__(POST_THREADS) val_nms_kernel(const float* __re
 static int pow2_at_least(int n);
 int launch_val_nms(const float* pred, int N, int M, int nc, float conf_thres, float nms_thres, int kmax, float* det, int32_t* counts, hipStream_t s)
 {
-    if (M > 8191 || nc < 1) return -1;
+    if (M > 8191 || nc < 1) return -1;   // 13-bit row field of the sort key
+    if (nc >= (1 << 18)) return -3;      // the class sits above bit 45 of the sort key, as in launch_post
     int mp = pow2_at_least(M);
     size_t lds = (size_t)mp * 8 + (size_t)M * 3 + 16;
     static size_t attr_set[YF_MAX_DEVICES] = {};
