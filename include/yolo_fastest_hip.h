@@ -145,6 +145,23 @@ int yf_val_nms(yf_handle h, const float *d_pred, int N, int M, double conf_thres
 int yf_val_nms_ex(yf_handle h, const float *d_pred, int N, int M, int num_classes, double conf_thres, double nms_thres, int K_max,
                   float *d_det, int32_t *d_counts, void *stream);
 
+/* Validation's matching of detections to ground truth for a whole batch: Validation.get_mAP's per-image loop
+ *                                                                      src/model_training/validate.py:46-74 (+ bbox_iou, utils/general.py:29-52)
+ *   d_det, d_counts: yf_val_nms_ex's output as it is (K_max the same); an image contributes min(max(count, 0), K_max) detections.
+ *   d_targets float32 [N,T,6] = (x1, y1, x2, y2, class, marker) in net-input pixels (validate.py:112-122's recovered corners); only rows
+ *       with marker > 1 exist (validate.py:47).  T = 0: every detection is a false positive.  T <= 65536.
+ *   Per image, detections in slot order (class-ascending, then confidence-descending = validate.py:50's unique() loop over :56's): a
+ *       detection is a true positive if a target not yet matched has class == class_pred (compared as floats) and IoU (fp32, +1
+ *       convention, clamp(min=0) on both extents, / (a1 + a2 - inter + 1e-16f)) > (float)iou_thres; the one with the lowest index is taken
+ *       and removed.  NaN behaves as in torch (max / min / clamp return it): a NaN IoU is not above the threshold.
+ *   d_records int32 [cap,3]: one record per detection = (obj_conf as float32 bits, (int)class_pred, hit 0 / 1), appended in image, slot
+ *       order from record *d_base on; a record whose index is >= cap is not written.  *d_next = *d_base + the number of this call's
+ *       detections, written or not: pass it as the next call's d_base (two int64 slots used in turn; d_next == d_base is refused).
+ *   `device` = HIP device index; stream-ordered, no allocation, no synchronisation, plain vector stores only.
+ *   YF_E_INVALID before any launch: a null pointer, N < 1, K_max < 1, T < 0 or > 65536, cap < 0. */
+int yf_val_match(int device, const float *d_det, const int32_t *d_counts, int N, int K_max, const float *d_targets, int T, double iou_thres,
+                 const int64_t *d_base, int64_t *d_next, int32_t *d_records, int64_t cap, void *stream);
+
 /* The loss end of the reference's training step (first slice; the layers' backward is not part of it):
  *   yf_train_loss = YOLOLossV3.forward(input, targets) for ONE head   src/model_training/loss/yolo_loss.py:48-97 (+ get_target :144-196)
  *                   and, if d_grad_head is not NULL, d(total loss)/d(input): what loss.backward() (train.py:131) leaves in input.grad.

@@ -1291,6 +1291,20 @@ int yf_val_nms_ex(yf_handle h, const float* d_pred, int N, int M, int num_classe
     return YF_OK;
 }
 
+// validate.py:46-74 on yf_val_nms_ex's output, one launch per batch.  No engine: nothing here depends on the network.
+int yf_val_match(int device, const float* d_det, const int32_t* d_counts, int N, int K_max, const float* d_targets, int T, double iou_thres,
+                 const int64_t* d_base, int64_t* d_next, int32_t* d_records, int64_t cap, void* stream)
+{
+    if (!d_det || !d_counts || !d_targets || !d_base || !d_next || !d_records) return fail(YF_E_INVALID, "yf_val_match: null pointer");
+    if (N < 1 || K_max < 1 || T < 0 || cap < 0) return fail(YF_E_INVALID, "yf_val_match: N >= 1, K_max >= 1, T >= 0, cap >= 0");
+    if (T > yf::VAL_MATCH_MAX_T) return fail(YF_E_INVALID, "yf_val_match: at most %d targets per image", (int)yf::VAL_MATCH_MAX_T);
+    if (d_base == d_next) return fail(YF_E_INVALID, "yf_val_match: d_next must not be d_base (every image's wave reads the base)");
+    HIP_OK(hipSetDevice(device));
+    yf::launch_val_match(d_det, d_counts, N, K_max, d_targets, T, (float)iou_thres, d_base, d_next, d_records, cap, (hipStream_t)stream);
+    HIP_OK(hipGetLastError());
+    return YF_OK;
+}
+
 // Training-time loss of ONE head (first slice).  anchors: HOST double[3][2] of this head, net-input pixels.
 int yf_train_loss_workspace_bytes(yf_handle h, int N, int fh, int fw, size_t* out)
 {

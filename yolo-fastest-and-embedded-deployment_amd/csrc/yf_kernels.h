@@ -333,6 +333,11 @@ size_t post_lds_bytes(int ncell);
 void launch_val_decode(const float* in, float* out, int N, int h, int w, int M_total, int m_off, const float* anc, int na, int nc, float stride_w,
                        float stride_h, hipStream_t s);
 int launch_val_nms(const float* pred, int N, int M, int nc, float conf_thres, float nms_thres, int kmax, float* det, int32_t* counts, hipStream_t s);
+// detections of launch_val_nms against targets [N,T,6] = (x1,y1,x2,y2,cls,marker): records int32 [cap,3] = (conf bits, class, hit), appended at
+// *base; *next = *base + sum of min(counts, kmax).  T <= VAL_MATCH_MAX_T (the alive bits of one image sit in LDS: one bit per target, sized per launch)
+enum { VAL_MATCH_MAX_T = 65536 };
+void launch_val_match(const float* det, const int32_t* counts, int N, int kmax, const float* targets, int T, float thres, const int64_t* base,
+                      int64_t* next, int32_t* records, int64_t cap, hipStream_t s);
 // training-time loss of one head and its gradient with respect to the head tensor (yf_loss_kernels.hip)
 size_t train_loss_workspace_bytes(int N, int fh, int fw, int na = 3, int nc = 3);
 void launch_train_loss(const float* head, int N, int fh, int fw, const float* anc, int na, int nc, const float* targets, int T, float ignore_thres,

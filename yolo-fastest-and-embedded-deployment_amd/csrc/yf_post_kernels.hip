@@ -663,6 +663,81 @@ int launch_val_nms(const float* pred, int N, int M, int nc, float conf_thres, fl
     return 0;
 }
 
+// validate.py:46-74 for a whole batch: every detection of val_nms_kernel's output against the image's targets, TP / FP per detection.
+// One wave per image; lanes are targets, 64 at a time.  The detections of an image are visited in slot order (class-ascending, then
+// confidence-descending: the reference's unique() loop over its per-class loop); a detection takes the lowest-index target of its class
+// that is still unmatched and whose IoU (general.py:29-52, +1 convention) is above the threshold, and that target is gone for the rest.
+// torch.max / torch.min / clamp(min=0) return NaN where fmaxf / fminf would drop it, hence the helpers: a NaN IoU is not above anything.
+// Every loop bound is a clamped argument (n = min(max(counts, 0), kmax), T): garbage counts cannot run the kernel away.
+__device__ __forceinline__ float torch_max(float a, float b) { return (a != a || b != b) ? a + b : (a > b ? a : b); }
+__device__ __forceinline__ float torch_min(float a, float b) { return (a != a || b != b) ? a + b : (a < b ? a : b); }
+__device__ __forceinline__ float torch_clamp0(float x) { return x != x ? x : (x < 0.f ? 0.f : x); }
+
+__global__ void __launch_bounds__(64) val_match_kernel(const float* __restrict__ det, const int32_t* __restrict__ counts, int N, int kmax,
+                                                       const float* __restrict__ targets, int T, float thres, const long long* __restrict__ base,
+                                                       long long* __restrict__ next, int32_t* __restrict__ rec, long long cap)
+{
+    extern __shared__ unsigned long long s_alive[];                // (T + 63) / 64 words; bit l of word c: target 64 c + l exists and is unmatched
+    const int img = blockIdx.x, lane = threadIdx.x;
+    long long before = 0;                                          // records of the images in front of this one
+    for (int j = lane; j < img; j += 64) before += min(max(counts[j], 0), kmax);
+    for (int d = 32; d > 0; d >>= 1) before += __shfl_xor(before, d);
+    const int n = min(max(counts[img], 0), kmax);
+    const long long at = base[0] + before;
+    if (img == N - 1 && lane == 0) next[0] = at + n;
+    const int nchunk = (T + 63) >> 6;
+    const float* tg = targets + (long)img * T * 6;
+    for (int c = 0; c < nchunk; ++c) {
+        const int t = c * 64 + lane;
+        const unsigned long long m = __ballot(t < T && tg[(long)t * 6 + 5] > 1.f);   // validate.py:47: marker > 1
+        if (lane == 0) s_alive[c] = m;
+    }
+    float r0 = 0.f, r1 = 0.f, r2 = 0.f, r3 = 0.f, rc = 0.f;       // chunk 0 (all of the reference's 64 boxes per image) stays in registers
+    if (lane < T) { r0 = tg[lane * 6]; r1 = tg[lane * 6 + 1]; r2 = tg[lane * 6 + 2]; r3 = tg[lane * 6 + 3]; rc = tg[lane * 6 + 4]; }
+    __syncthreads();
+    for (int k = 0; k < n; ++k) {
+        const float* q = det + ((long)img * kmax + k) * 7;
+        const float b0 = q[0], b1 = q[1], b2 = q[2], b3 = q[3], conf = q[4], cls = q[6];
+        const float a1 = (b2 - b0 + 1.f) * (b3 - b1 + 1.f);
+        int hit = 0;
+        for (int c = 0; c < nchunk; ++c) {
+            const unsigned long long alive = s_alive[c];          // one address for the wave: every branch on it is uniform
+            if (!alive) continue;
+            const int t = c * 64 + lane;
+            bool over = false;
+            if ((alive >> lane) & 1ull) {
+                float t0 = r0, t1 = r1, t2 = r2, t3 = r3, tc = rc;
+                if (c) { const float* p = tg + (long)t * 6; t0 = p[0]; t1 = p[1]; t2 = p[2]; t3 = p[3]; tc = p[4]; }
+                const float iw = torch_clamp0(torch_min(b2, t2) - torch_max(b0, t0) + 1.f);
+                const float ih = torch_clamp0(torch_min(b3, t3) - torch_max(b1, t1) + 1.f);
+                const float inter = iw * ih;
+                const float a2 = (t2 - t0 + 1.f) * (t3 - t1 + 1.f);
+                const float iou = inter / (a1 + a2 - inter + 1e-16f);
+                over = tc == cls && iou > thres;
+            }
+            const unsigned long long m = __ballot(over);
+            if (m) {
+                if (lane == 0) s_alive[c] = alive & ~(1ull << (__ffsll((long long)m) - 1));   // the lowest index wins and is removed
+                hit = 1;
+                break;
+            }
+        }
+        __syncthreads();
+        if (lane == 0 && at + k >= 0 && at + k < cap) {       // (a negative cursor is garbage: count on, write nothing)
+            int32_t* o = rec + (at + k) * 3;
+            o[0] = (int32_t)__float_as_uint(conf); o[1] = (int32_t)cls; o[2] = hit;
+        }
+    }
+}
+
+void launch_val_match(const float* det, const int32_t* counts, int N, int kmax, const float* targets, int T, float thres, const int64_t* base,
+                      int64_t* next, int32_t* records, int64_t cap, hipStream_t s)
+{
+    const size_t lds = (size_t)((T + 63) / 64) * sizeof(unsigned long long);   // T <= VAL_MATCH_MAX_T: at most 8 KB
+    hipLaunchKernelGGL(val_match_kernel, dim3(N), dim3(64), lds, s, det, counts, N, kmax, targets, T, thres, reinterpret_cast<const long long*>(base),
+                       reinterpret_cast<long long*>(next), records, (long long)cap);
+}
+
 static int pow2_at_least(int n)
 {
     int p = 64;

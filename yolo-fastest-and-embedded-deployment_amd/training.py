@@ -528,7 +528,7 @@ def cosine_factor(epoch, total_epochs):
     return ((1 + math.cos(epoch * math.pi / total_epochs)) / 2) * 0.8 + 0.2
 
 
-def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, logger=None):
+def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, logger=None, val_match="host"):
     """The reference's `train(params, device, tbwriter)` (train.py:44-160) with the iteration on the GPU kernels of this package.
     Same control flow and arithmetic: one YOLOLossV3 per stride (:50-53), the model from `pretrained_pth` or initialize_weights()
     (:58-65), DataLoader(batch_size, drop_last, shuffle) (:71-73), Adam(lr0, betas (0.9, 0.999), eps 1e-8) (:84), the cosine
@@ -538,7 +538,8 @@ def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, l
     config paths, train.py:68-76; here: `dataset.DetectDataset(io["input_shape"], io["origin_img_shape"], logger,
     aug_params=params["augment_params"])` and the same with `augment=False, val=True`); items are DetectDataset's ((h, w, c) uint8-range
     image, (64, 6) boxes), batched by validation.collate_fn (= DetectDataset.collate_fn), or DetectDataset's whole-batch
-    `__getitems__` (device images), which the collate passes through.  tbwriter may be None.
+    `__getitems__` (device images), which the collate passes through.  tbwriter may be None.  `val_match` is Validation's `match`
+    ("host", the default, or "device": the TP / FP matching of get_mAP on the GPU, same result).
     Returns the trained model."""
     import logging
     import os
@@ -576,8 +577,8 @@ def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, l
         data_parallel(model)
     dataloader = DataLoader(train_dataset, batch_size=batch_size, num_workers=0, drop_last=True, pin_memory=True, shuffle=sampler is None,
                             sampler=sampler, collate_fn=validation.collate_fn)
-    val = validation.Validation(params=params, logger=logger, dataset=val_dataset, device=device, model_loss=model_loss) \
-        if val_dataset is not None else None
+    val = validation.Validation(params=params, logger=logger, dataset=val_dataset, device=device, model_loss=model_loss,
+                                match=val_match) if val_dataset is not None else None
     batch_per_epoch = len(dataloader)
     num_warm = max(3 * batch_per_epoch, 1000)
     optimizer = Adam(model.parameters(), lr=tp["lr0"], betas=(0.9, 0.999), eps=1e-08)

@@ -6,6 +6,7 @@ analytic backward to the head tensor (yf_train_loss; SURVEY.md 8(f).4, first sli
 H and W, which come from `input_shape`).  The model is passed explicitly (`model=` / `loss.model = m`); `bind(model)` sets the
 default used when none is given.  The engine is chosen by (H, W, device of the tensor) -- never "whichever exists"."""
 import ctypes
+import math
 
 import torch
 
@@ -121,9 +122,8 @@ def _train_loss(self, input, targets):
 YOLOLossV3._train_loss = _train_loss
 
 
-def non_max_suppression(prediction, num_classes, conf_thres=0.5, nms_thres=0.4, kmax=None, model=None):
-    """-> list with one [n,7] tensor (x1,y1,x2,y2,obj_conf,class_conf,class_pred) or None per image, like the reference.
-    (The reference also overwrites prediction[..., :4] with the corners in place; this does not touch its input.)"""
+def _nms_device(prediction, num_classes, conf_thres, nms_thres, kmax, model):
+    """yf_val_nms_ex on the current stream -> (det float32 [bs, kmax, 7], cnt int32 [bs], kmax), all on the device, nothing read back."""
     if not prediction.is_cuda:
         raise RuntimeError("validation path (HIP) has no CPU implementation: pass GPU tensors")
     p = prediction.contiguous().float()
@@ -137,10 +137,40 @@ def non_max_suppression(prediction, num_classes, conf_thres=0.5, nms_thres=0.4, 
     stream = torch.cuda.current_stream(p.device).cuda_stream
     _lib.check(e.lib.yf_val_nms_ex(e.handle, p.data_ptr(), bs, M, int(num_classes), float(conf_thres), float(nms_thres), kmax, det.data_ptr(),
                                    cnt.data_ptr(), ctypes.c_void_p(stream)))
+    return det, cnt, kmax
+
+
+def non_max_suppression(prediction, num_classes, conf_thres=0.5, nms_thres=0.4, kmax=None, model=None):
+    """-> list with one [n,7] tensor (x1,y1,x2,y2,obj_conf,class_conf,class_pred) or None per image, like the reference.
+    (The reference also overwrites prediction[..., :4] with the corners in place; this does not touch its input.)"""
+    det, cnt, kmax = _nms_device(prediction, num_classes, conf_thres, nms_thres, kmax, model)
     counts = cnt.cpu().tolist()
     if max(counts) > kmax:
         raise OverflowError("more than kmax detections in an image")
     return [det[i, :n].clone() if n else None for i, n in enumerate(counts)]
+
+
+def _key_fallback(t):
+    """the sort key of validate.py:72 for one confidence (a 0-dim tensor): its printed form"""
+    return str(t)
+
+
+def _conf_keys(conf):
+    """[str(c) for c in conf] for a 1-D float32 host tensor, without printing a tensor per value.  With torch's default print options a
+    float32 scalar v in [0, 1] prints as 'tensor(0.)' / 'tensor(1.)' if it is integral, 'tensor(%.4e)' if v < 1e-4 (torch's sci_mode rule
+    for a single value), else 'tensor(%.4f)', all from float(v).  Anything else -- other print options, another default dtype (str() then
+    names float32), NaN, -0.0, values outside [0, 1] -- goes through str() itself."""
+    opts = torch._tensor_str.PRINT_OPTS
+    fast = opts.precision == 4 and opts.sci_mode is None and torch.get_default_dtype() == torch.float32 and conf.dtype == torch.float32
+    keys = []
+    for i, v in enumerate(conf.tolist()):
+        if fast and 0.0 < v < 1.0:
+            keys.append("tensor(%.4e)" % v if v < 1e-4 else "tensor(%.4f)" % v)
+        elif fast and (v == 1.0 or (v == 0.0 and math.copysign(1.0, v) > 0)):
+            keys.append("tensor(%.0f.)" % v)
+        else:
+            keys.append(_key_fallback(conf[i]))
+    return keys
 
 
 def collate_fn(batch):
@@ -168,10 +198,17 @@ class Validation:
       * recall is float32 (target_num is a float32 tensor), precision a Python float; equal consecutive recalls keep the
         larger precision; AP = sum over the P-R points of (recall step) x (max precision from that point on) (:87-119).
     `dataset` is anything a DataLoader accepts; items are ((h,w,c) image, (64,6) boxes) like DetectDataset's, batched with
-    `collate_fn` above (images / 255) -- dataset.DetectDataset(..., val=True, augment=False) itself, batch by batch on the GPU."""
+    `collate_fn` above (images / 255) -- dataset.DetectDataset(..., val=True, augment=False) itself, batch by batch on the GPU.
+    `match="device"` (not in the reference; default "host"): the matching runs on the GPU too (yf_val_match behind the NMS, one launch per
+    batch, no read-back per batch); the (confidence, class, hit) records read back after the last batch rebuild the same `match_list`,
+    sort keys included (`_conf_keys`), and the same `target_num`, so everything from the sort on is the code below either way."""
 
-    def __init__(self, params, logger, dataset, device, model_loss):
+    def __init__(self, params, logger, dataset, device, model_loss, match="host"):
         from torch.utils.data import DataLoader
+        if match not in ("host", "device"):
+            raise ValueError("match must be 'host' or 'device', not %r" % (match,))
+        self.match = match
+        self._record_capacity = 1 << 20           # match="device": records the buffer of one get_mAP starts with (12 bytes each)
         self.logger = logger
         self.model_loss = model_loss
         self.device = device
@@ -233,21 +270,83 @@ class Validation:
                         hit = True
                 self.match_list[c].append((str(t[4]), hit))
 
+    def _count_targets(self, targets):
+        """`target_num` of a batch of recovered targets [bs, T, 6]: what `_match_image`'s loop adds, image by image."""
+        cls = targets[..., 4][targets[..., 5] > 1]
+        if bool(((cls == cls.trunc()) & (cls >= 0) & (cls < self.num_cls)).all()):
+            self.target_num += torch.bincount(cls.long(), minlength=self.num_cls).to(self.target_num.dtype)
+        else:                                     # negative, fractional, NaN or too large: the loop's own wrap-around / exception
+            for v in cls:
+                self.target_num[int(v)] += 1
+
+    def _match_device(self, model):
+        """The batches of `get_mAP` with the matching on the device.  Records (conf bits, class, hit) go to one int32 [cap, 3] buffer; the
+        write cursor is two int64 device slots used in turn (yf_val_match reads one and writes the other).  The host only keeps an upper
+        bound of the cursor (+ bs * K_max per batch) and reads the true value -- the one synchronisation before the end -- when a batch
+        could pass the capacity; the buffer is then reallocated if the batch really might not fit.  After the last batch two reads come
+        back: (cursor, overflow flag) as one pair, then the filled part of the buffer."""
+        lib = _lib.lib()
+        dev = torch.device(self.device)
+        index = dev.index if dev.index is not None else torch.cuda.current_device()
+        cap = max(int(self._record_capacity), 1)
+        rec = torch.empty((cap, 3), dtype=torch.int32, device=dev)
+        cursor = torch.zeros(2, dtype=torch.int64, device=dev)
+        over = torch.zeros((), dtype=torch.int64, device=dev)    # images with more than their batch's kmax detections, summed on the stream
+        bound, turn, batches = 0, 0, 0
+        for imgs, targets in self.dataloader:
+            targets = self._recover_targets(targets.float())                      # host, float32, as in host mode
+            self._count_targets(targets)
+            imgs = imgs.to(self.device).float()
+            pred = model(imgs)
+            output = torch.cat([self.model_loss[i](p) for i, p in enumerate(pred)], 1)
+            det, cnt, kmax = _nms_device(output, self.num_cls, self.conf_thres, self.nms_thres, None, model)
+            bs, T = targets.shape[0], targets.shape[1]
+            if bound + bs * kmax > cap:
+                bound = int(cursor[turn])                                         # the true number of records so far
+                if bound + bs * kmax > cap:
+                    cap = max(2 * cap, bound + bs * kmax)
+                    grown = torch.empty((cap, 3), dtype=torch.int32, device=dev)
+                    grown[:bound] = rec[:bound]
+                    rec = grown
+            # a pinned staging block per batch, from torch's caching host allocator (it hands a block out again only after the copy that
+            # reads it has run): ONE reused buffer would be overwritten by the next batch while its copy is still queued, since nothing
+            # here waits for the stream
+            t_dev = targets.contiguous().pin_memory().to(dev, non_blocking=True) if T else det   # (T = 0: never read)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(lib.yf_val_match(index, det.data_ptr(), cnt.data_ptr(), bs, kmax, t_dev.data_ptr(), T, float(self.IOU_threshold),
+                                        cursor[turn:].data_ptr(), cursor[1 - turn:].data_ptr(), rec.data_ptr(), cap, ctypes.c_void_p(stream)))
+            turn = 1 - turn
+            bound += bs * kmax
+            over += (cnt > kmax).sum()            # against THIS batch's kmax
+            batches += 1
+        if not batches:
+            return
+        total, overflow = torch.stack((cursor[turn], over)).tolist()
+        if overflow:
+            raise OverflowError("more than kmax detections in an image")
+        rec = rec[:total].cpu()
+        keys = _conf_keys(rec[:, 0].contiguous().view(torch.float32))
+        for key, c, hit in zip(keys, rec[:, 1].tolist(), rec[:, 2].tolist()):
+            self.match_list[c].append((key, bool(hit)))
+
     def get_mAP(self, model, epoch):
         self.clear()
         model.eval()
         for loss in self.model_loss:
             object.__setattr__(loss, "model", model)      # (not a registered submodule, see YOLOLossV3.__init__)
         with torch.no_grad():
-            for imgs, targets in self.dataloader:
-                targets = self._recover_targets(targets.float())                      # host: the bookkeeping stays on the CPU
-                imgs = imgs.to(self.device).float()
-                pred = model(imgs)
-                output = torch.cat([self.model_loss[i](p) for i, p in enumerate(pred)], 1)
-                output = non_max_suppression(output, self.num_cls, conf_thres=self.conf_thres, nms_thres=self.nms_thres, model=model)
-                output = [None if o is None else o.cpu() for o in output]
-                for img_id, img_pred in enumerate(output):
-                    self._match_image(img_pred, targets[img_id])
+            if self.match == "device":
+                self._match_device(model)
+            else:
+                for imgs, targets in self.dataloader:
+                    targets = self._recover_targets(targets.float())                      # host: the bookkeeping stays on the CPU
+                    imgs = imgs.to(self.device).float()
+                    pred = model(imgs)
+                    output = torch.cat([self.model_loss[i](p) for i, p in enumerate(pred)], 1)
+                    output = non_max_suppression(output, self.num_cls, conf_thres=self.conf_thres, nms_thres=self.nms_thres, model=model)
+                    output = [None if o is None else o.cpu() for o in output]
+                    for img_id, img_pred in enumerate(output):
+                        self._match_image(img_pred, targets[img_id])
             for c in range(self.num_cls):
                 self.match_list[c].sort(key=lambda x: x[0], reverse=True)
             mAP = 0
