@@ -676,7 +676,7 @@ int run_forward(yf_engine* e, const float* d_x, int N, float* d_hl, float* d_hs,
             } else if (o.type == OP_K19) {
                 yf::K19Args a{};
                 a.in = ptr(o.in1);
-                a.w8 = W(o.l_exp); a.b8 = B(o.l_exp); a.w9 = W(o.l_dw); a.b9 = B(o.l_dw); a.w21 = W(o.l_proj); a.b21 = B(o.l_proj);
+                a.w8 = W(o.l_exp); a.b8 = B(o.l_exp); a.b9 = B(o.l_dw); a.b21 = B(o.l_proj);
                 a.out = ptr(o.out);
                 a.H = ti.H; a.W = ti.W; a.Ho = to.H; a.Wo = to.W;
                 a.wp = e->d_wmfma + o.mfma_off;

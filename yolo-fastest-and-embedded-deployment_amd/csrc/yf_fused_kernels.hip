@@ -4,7 +4,6 @@
 //   = the reference's BasicResBlock (src/model_training/model/yolo_fastest.py:52-66) and the un-named
 //   bottlenecks conv1_2/1_3/1_4, conv2_2/2_3/3_1, conv3_2/3_3/3_4, conv3_5/3_6/4_1, conv4_2/4_3/5_1 (:80-118);
 //   with PRE it also evaluates conv0 (dense 3x3 s2 on the 1-channel input, :78) in front of the expansion.
-// k19_kernel:          conv1_8 (pw 4->24 +ReLU) -> conv1_9 (dense 3x3 s2 24->24 +ReLU) -> conv2_1 (pw 24->8)   (:86-89)
 //
 // One workgroup = one spatial tile of one frame.  Data flow per tile:
 //   HBM --(narrow NHWC input tile + halo, 16-B loads)--> registers --expand--> LDS (chunk of EC, channel pairs interleaved:
@@ -41,12 +40,12 @@ __device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane
 __host__ __device__ constexpr int fb_chunk_floats(int cin, int cout, int ec) { return cin * ec + ec + 9 * ec + ec + ec * cout; }
 
 template <int CIN, int CEXP, int COUT, int S, bool RES, bool RELU_OUT, bool PRE, int TYB, int TXB, int BH, int BW,
-          int EC, int CG, int PE, bool XL, typename T, int C0 = 1>
+          int EC, int CG, int PE, typename T, int C0 = 1>
 __global__ void __launch_bounds__(TYB* TXB) fused_block_kernel(FbArgs a)
 {
     // C0 (PRE only): input channels of conv0 = io_params input_channel (yolo_fastest.py:78): 1 (gray), 3 (cv2's BGR), or 2 / 4 (NCHW
     // planes; u8 frames: HWC, channel order reversed like `img[:, :, ::-1]`, detect.py:119)
-    static_assert(C0 == 1 || (PRE && !XL && C0 >= 2 && C0 <= 4), "conv0 on 1 .. 4 input channels");
+    static_assert(C0 == 1 || (PRE && C0 >= 2 && C0 <= 4), "conv0 on 1 .. 4 input channels");
     constexpr int NT = TYB * TXB, NW = NT / 64;
     constexpr int O_B1 = CIN * EC, O_WD = O_B1 + EC, O_BD = O_WD + 9 * EC, O_W2 = O_BD + EC, CHF = O_W2 + EC * COUT;
     static_assert(CHF == fb_chunk_floats(CIN, COUT, EC), "pack layout");
@@ -59,12 +58,7 @@ __global__ void __launch_bounds__(TYB* TXB) fused_block_kernel(FbArgs a)
     static_assert(NT % 64 == 0 && CEXP % EC == 0 && EC % CG == 0 && COUT % 4 == 0, "shape");
     static_assert(!RES || (CIN == COUT && S == 1 && !PRE), "residual needs same shape");
     static_assert(CIN % 4 == 0 || PRE, "NHWC 16-B loads");
-    // input tile staged once: X[region px][CIN] (pitch XP: conflict-free 16-B reads); PRE: the raw 1-channel window
-    constexpr int XP = PRE ? 0 : (CIN == 4 ? 4 : CIN + 4);
-    constexpr int IRH = 2 * RH + 1, IRW = 2 * RW + 1, IRWP = (IRW + 3) & ~3;  // PRE: input rows/cols feeding the region
-    constexpr int XFLOATS = !XL ? 4 : PRE ? IRH * IRWP : NRP * XP;  // XL = false: inputs come straight from HBM/L2
     __shared__ __attribute__((aligned(16))) float E[EC * PLANE];
-    __shared__ __attribute__((aligned(16))) float X[XFLOATS];
     // u8 input (PRE): (v - 128) / 255 of the 256 possible pixel values (a 2x2 box mean is an integer 0..255 too).  The IEEE division is
     // ~10 VALU instructions and sat in the loop nine times per region pixel (stem 98 us from u8 against 67 us from f32, batch 256); one
     // division per thread here and an LDS read per tap give the same bits (torch's `(img - 128.0) / 255.0`, detect.py:124)
@@ -80,29 +74,7 @@ __global__ void __launch_bounds__(TYB* TXB) fused_block_kernel(FbArgs a)
         if (a.in_u8)
             for (int i = threadIdx.x; i < 256; i += NT) LUT[i] = ((float)i - 128.0f) / 255.0f;
     }
-    // ---------------- stage the input tile (one exposed HBM latency per workgroup) ----------------
-    if constexpr (!XL) {
-    } else if constexpr (PRE) {
-        const float* __restrict__ src = a.in + (long)n * (4L * a.H * a.W);
-        const int yy0 = 2 * iy0 - 1, xx0 = 2 * ix0 - 1;
-        for (int idx = threadIdx.x; idx < IRH * IRW; idx += NT) {
-            const int r_ = idx / IRW, c_ = idx - r_ * IRW;
-            const int yy = yy0 + r_, xx = xx0 + c_;
-            X[r_ * IRWP + c_] = (yy >= 0 && yy < 2 * a.H && xx >= 0 && xx < 2 * a.W) ? src[(long)yy * (2 * a.W) + xx] : 0.f;
-        }
-    } else {
-        constexpr int C4 = CIN / 4;
-        const T* __restrict__ src = reinterpret_cast<const T*>(a.in) + (long)n * a.H * a.W * CIN;
-        for (int idx = threadIdx.x; idx < NRP * C4; idx += NT) {
-            const int rp = idx / C4, c4 = idx - rp * C4;
-            const int ry_ = rp / RW, rx_ = rp - ry_ * RW;
-            const int iy = iy0 + ry_, ix = ix0 + rx_;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) v = ld4<T>(src + ((long)iy * a.W + ix) * CIN + c4 * 4);
-            *reinterpret_cast<float4*>(&X[rp * XP + c4 * 4]) = v;
-        }
-    }
-    __syncthreads();
+    __syncthreads();   // orders the LUT fill before the expansion reads it
 
     fb_f32x2 acc2[BH * BW][COUT / 2];   // projection accumulators, output-channel pairs
 #pragma unroll
@@ -115,7 +87,7 @@ __global__ void __launch_bounds__(TYB* TXB) fused_block_kernel(FbArgs a)
     // (load, wait, 16 / 32 packed FMAs, next item).  With HOIST the wave's MAXI items are loaded ONCE, all requests in flight together,
     // before the chunk loop, and stay in registers (MAXI x CIN VGPRs).
     constexpr int MAXI = (NITEM + NW - 1) / NW;
-    constexpr bool HOIST = !PRE && !XL && NCG == 1 && PE == 1 && MAXI * CIN <= 32;
+    constexpr bool HOIST = !PRE && NCG == 1 && PE == 1 && MAXI * CIN <= 32;
     float xh[HOIST ? MAXI : 1][CIN];
     int hdst[HOIST ? MAXI : 1];       // ... and so are the item's E offset (-1: no pixel) and its ReLU limit (+inf inside the image, 0 outside):
     float hlim[HOIST ? MAXI : 1];     // 13 of the 64 VALU instructions of an item and chunk were this index arithmetic
@@ -154,17 +126,10 @@ __global__ void __launch_bounds__(TYB* TXB) fused_block_kernel(FbArgs a)
                 const int iy = iy0 + ry[p], ix = ix0 + rx[p];
                 inreg[p] = rp < NRP;
                 inimg[p] = inreg[p] && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
-                const int rpc = inreg[p] ? rp : 0;
                 if constexpr (PRE) {
                     // conv0: 3x3 stride 2 pad 1 on the C0-channel net input (+ReLU); v[(ky * 3 + kx) * C0 + ci]
                     float v[9 * C0];
-                    if constexpr (XL) {  // window rows 2*ry.., cols 2*rx.. of the staged input
-                        const float* win0 = X + (2 * (rpc / RW)) * IRWP + 2 * (rpc % RW);
-#pragma unroll
-                        for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                            for (int kx = 0; kx < 3; ++kx) v[ky * 3 + kx] = win0[ky * IRWP + kx];
-                    } else if (a.in_u8) {
+                    if (a.in_u8) {
                         // Detect_YOLO.__pre_process fused into the load (src/detect.py:115-124): u8 gray frame, optional
                         // exact-2x box mean (a+b+c+d+2)>>2, then (v-128)/255; conv0 zero-pads the NORMALISED tensor
                         // (C0 = 3: the frame is cv2's HWC BGR; net channel ci is source channel 2 - ci, detect.py:119)
@@ -236,12 +201,6 @@ __global__ void __launch_bounds__(TYB* TXB) fused_block_kernel(FbArgs a)
                         for (int t = 0; t < 9 * C0; ++t)
                             s2 = __builtin_elementwise_fma(fb_f32x2{v[t], v[t]}, *(const cfloat2*)(const cfloat*)(a.w0 + t * CIN + c), s2);
                         x[p][c] = fmaxf(s2[0], 0.f); x[p][c + 1] = fmaxf(s2[1], 0.f);
-                    }
-                } else if constexpr (XL) {
-#pragma unroll
-                    for (int k = 0; k < CIN; k += 4) {
-                        float4 t = *reinterpret_cast<const float4*>(&X[rpc * XP + k]);
-                        x[p][k] = t.x; x[p][k + 1] = t.y; x[p][k + 2] = t.z; x[p][k + 3] = t.w;
                     }
                 } else if constexpr (HOIST) {
 #pragma unroll
@@ -355,9 +314,8 @@ __global__ void __launch_bounds__(TYB* TXB) fused_block_kernel(FbArgs a)
             for (int co = 0; co < COUT; co += 4) {
                 float4 v = make_float4(acc2[by * BW + bx][co / 2][0] + b2[co], acc2[by * BW + bx][co / 2][1] + b2[co + 1],
                                        acc2[by * BW + bx][co / 2 + 1][0] + b2[co + 2], acc2[by * BW + bx][co / 2 + 1][1] + b2[co + 3]);
-                if constexpr (RES) {  // the residual is the centre of the staged tile
-                    float4 r = XL ? *reinterpret_cast<const float4*>(&X[((tyb * BH + by + 1) * RW + txb * BW + bx + 1) * XP + co])
-                                  : ld4<T>(reinterpret_cast<const T*>(a.in) + opix * CIN + co);
+                if constexpr (RES) {
+                    float4 r = ld4<T>(reinterpret_cast<const T*>(a.in) + opix * CIN + co);
                     v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
                 }
                 if constexpr (RELU_OUT) {
@@ -369,130 +327,32 @@ __global__ void __launch_bounds__(TYB* TXB) fused_block_kernel(FbArgs a)
 }
 
 // ------------------------------------------------------------------------------------------------
-// conv1_8 (pw 4->24, ReLU) -> conv1_9 (dense 3x3 stride 2 pad 1, 24->24, ReLU) -> conv2_1 (pw 24->8, linear)
-//   tile: 16x16 output pixels (stride-4 resolution), 256 threads, one output pixel per thread.
-//   Measured alternatives that did NOT help (stand-alone kernel benchmark, profiles/): two pixels per lane (each scalar weight feeding
-//   two FMAs) and v_pk_fma_f32 over pixel pairs or output-channel pairs all land at the same ~250 us / 30 TMAC/s although the
-//   packed forms halve the VALU instruction count -- the kernel is not VALU-issue-bound (fully unrolled straight-line code,
-//   instruction fetch is the suspect).  Later finding (tools/isa_mix.py): this fully unrolled form also spills ~900 SGPR values to
-//   VGPR lanes (v_readlane / v_writelane are a third of its VALU instructions).  Superseded by k19m_kernel (yf_k19_kernels.hip);
-//   kept as the VALU reference point.
-//   conv1_8's output over the (33x33) halo'd region goes to LDS in two halves of 12 channels, split into
-//   even-column and odd-column planes ("space to depth") so that lanes on consecutive output columns read
-//   consecutive 48-B pixel records: conflict-free ds_read_b128.
-// ------------------------------------------------------------------------------------------------
-template <typename TT>
-__global__ void __launch_bounds__(256) k19_kernel(K19Args a)
-{
-    constexpr int T = 16, RH = 2 * T + 1, RWE = T + 1, RWO = T;  // even cols 0,2,..,32 (17); odd cols 1,..,31 (16)
-    constexpr int CH = 12;                                       // channels per half
-    constexpr int NE = RH * RWE, NO = RH * RWO, NR = NE + NO;    // records (pixels) in the even / odd plane
-    __shared__ __attribute__((aligned(16))) float A[NR * CH];
-
-    const int b = xcd_tile(blockIdx.x, gridDim.x);
-    const int tx = b % a.tiles_x, ty = (b / a.tiles_x) % a.tiles_y, n = b / (a.tiles_x * a.tiles_y);
-    const int oy0 = ty * T, ox0 = tx * T;
-    const int iy0 = 2 * oy0 - 1, ix0 = 2 * ox0 - 1;  // region origin in stride-2 coordinates
-    const int tyb = threadIdx.x >> 4, txb = threadIdx.x & 15;
-
-    float acc[24];
-#pragma unroll
-    for (int c = 0; c < 24; ++c) acc[c] = a.b9[c];
-
-    for (int half = 0; half < 2; ++half) {
-        // conv1_8 half: region pixels, record index r in [0, NR): first the even plane, then the odd plane
-        for (int r = threadIdx.x; r < NR; r += 256) {
-            int ry, rx;
-            if (r < NE) { ry = r / RWE; rx = 2 * (r - ry * RWE); }
-            else { int q = r - NE; ry = q / RWO; rx = 2 * (q - ry * RWO) + 1; }
-            const int iy = iy0 + ry, ix = ix0 + rx;
-            const bool inimg = iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
-            float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (inimg) t = ld4<TT>(reinterpret_cast<const TT*>(a.in) + (((long)n * a.H + iy) * a.W + ix) * 4);
-            float* dst = A + r * CH;
-#pragma unroll
-            for (int j = 0; j < CH; j += 4) {
-                float o[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int c = half * CH + j + q;
-                    float s = a.b8[c];
-                    s = fmaf(t.x, a.w8[0 * 24 + c], s); s = fmaf(t.y, a.w8[1 * 24 + c], s);
-                    s = fmaf(t.z, a.w8[2 * 24 + c], s); s = fmaf(t.w, a.w8[3 * 24 + c], s);
-                    o[q] = inimg ? fmaxf(s, 0.f) : 0.f;  // conv1_9 pads conv1_8's OUTPUT with zeros
-                }
-                *reinterpret_cast<float4*>(dst + j) = make_float4(o[0], o[1], o[2], o[3]);
-            }
-        }
-        __syncthreads();
-        // conv1_9 partial sums over this half's 12 input channels
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky) {
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx) {
-                const int ry = 2 * tyb + ky;
-                // column 2*txb + kx: kx=0 -> even plane idx txb; kx=1 -> odd plane idx txb; kx=2 -> even plane idx txb+1
-                const int rec = (kx == 1) ? NE + ry * RWO + txb : ry * RWE + txb + (kx >> 1);
-                const float* src = A + rec * CH;
-                const float* w = a.w9 + ((ky * 3 + kx) * 24 + half * CH) * 24;
-#pragma unroll
-                for (int j = 0; j < CH; j += 4) {
-                    float4 x = *reinterpret_cast<const float4*>(src + j);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const float xv = ((const float*)&x)[q];
-#pragma unroll
-                        for (int c = 0; c < 24; ++c) acc[c] = fmaf(xv, w[(j + q) * 24 + c], acc[c]);
-                    }
-                }
-            }
-        }
-        __syncthreads();
-    }
-    // ReLU, conv2_1 (24 -> 8, linear), store
-    const int oy = oy0 + tyb, ox = ox0 + txb;
-    if (oy >= a.Ho || ox >= a.Wo) return;
-    float o8[8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) o8[c] = a.b21[c];
-#pragma unroll
-    for (int k = 0; k < 24; ++k) {
-        const float v = fmaxf(acc[k], 0.f);
-#pragma unroll
-        for (int c = 0; c < 8; ++c) o8[c] = fmaf(v, a.w21[k * 8 + c], o8[c]);
-    }
-    TT* o = reinterpret_cast<TT*>(a.out) + (((long)n * a.Ho + oy) * a.Wo + ox) * 8;
-    st4<TT>(o, make_float4(o8[0], o8[1], o8[2], o8[3]));
-    st4<TT>(o + 4, make_float4(o8[4], o8[5], o8[6], o8[7]));
-}
-
-// ------------------------------------------------------------------------------------------------
 // Launchers
 // ------------------------------------------------------------------------------------------------
-template <int CIN, int CEXP, int COUT, int S, bool RES, bool RELU_OUT, bool PRE, int TYB, int TXB, int BH, int BW, int EC, int CG, int PE, bool XL, typename T, int C0 = 1>
+template <int CIN, int CEXP, int COUT, int S, bool RES, bool RELU_OUT, bool PRE, int TYB, int TXB, int BH, int BW, int EC, int CG, int PE, typename T, int C0 = 1>
 static int launch_fb_t(FbArgs a, int N, hipStream_t s)
 {
     a.tiles_y = (a.Ho + TYB * BH - 1) / (TYB * BH);
     a.tiles_x = (a.Wo + TXB * BW - 1) / (TXB * BW);
     dim3 grid((unsigned)(N * a.tiles_y * a.tiles_x));
-    hipLaunchKernelGGL((fused_block_kernel<CIN, CEXP, COUT, S, RES, RELU_OUT, PRE, TYB, TXB, BH, BW, EC, CG, PE, XL, T, C0>), grid,
+    hipLaunchKernelGGL((fused_block_kernel<CIN, CEXP, COUT, S, RES, RELU_OUT, PRE, TYB, TXB, BH, BW, EC, CG, PE, T, C0>), grid,
                        dim3(TYB * TXB), 0, s, a);
     return 0;
 }
 
-//     cin cexp cout S  res    relu   pre    TYB TXB BH BW EC CG PE XL      (XL: stage the input tile in LDS -- measured
-//     slower at these shapes: it costs occupancy and LDS bandwidth, the L2-served loads were already hidden)
+// (Staging the input tile in LDS was measured slower at these shapes: it costs occupancy and LDS bandwidth, the L2-served loads were already hidden.)
+//     cin cexp cout S  res    relu   pre    TYB TXB BH BW EC CG PE
 #define YF_FB_SHAPES(FB)                                                                                                 \
-    FB(8, 8, 4, 1, false, false, true, 16, 16, 1, 2, 8, 8, 1, false)     /* conv0 + conv1_2/1_3/1_4      @ H/2  */          \
-    FB(8, 8, 4, 1, false, false, false, 16, 16, 1, 2, 8, 8, 1, false)    /* conv1_2/1_3/1_4 behind a separate conv0 (input_channel > 4) */ \
-    FB(4, 8, 4, 1, true, false, false, 16, 16, 1, 2, 8, 8, 1, false)     /* res1_1                        @ H/2  */          \
-    FB(8, 32, 8, 1, true, false, false, 16, 16, RES2_BH, RES2_BW, 8, 8, 1, false)          /* res2_1, res2_2                @ H/4  */          \
-    FB(8, 32, 8, 2, false, false, false, 16, 20, 1, 1, 8, 8, 1, false)   /* conv2_2/2_3/3_1               H/4 -> H/8 */      \
-    FB(8, 48, 8, 1, true, false, false, 16, 20, 1, 2, 8, 8, 2, false)    /* res3_1, res3_2                @ H/8  */          \
-    FB(8, 48, 16, 1, false, false, false, 16, 20, 1, 2, 8, 8, 2, false)  /* conv3_2/3_3/3_4 (fallback)    @ H/8  */          \
-    FB(16, 96, 16, 1, true, false, false, 16, 20, 1, 2, 8, 8, 1, false)  /* res3_3 .. res3_6 (fallback)   @ H/8  */          \
-    FB(16, 96, 24, 2, false, false, false, 16, 20, 1, 1, 8, 8, 1, false) /* conv3_5/3_6/4_1               H/8 -> H/16 */     \
-    FB(24, 136, 24, 1, true, false, false, 16, 20, 1, 1, 8, 8, 1, false) /* res4_1 .. res4_4 (fallback)   @ H/16 */
+    FB(8, 8, 4, 1, false, false, true, 16, 16, 1, 2, 8, 8, 1)            /* conv0 + conv1_2/1_3/1_4      @ H/2  */          \
+    FB(8, 8, 4, 1, false, false, false, 16, 16, 1, 2, 8, 8, 1)           /* conv1_2/1_3/1_4 behind a separate conv0 (input_channel > 4) */ \
+    FB(4, 8, 4, 1, true, false, false, 16, 16, 1, 2, 8, 8, 1)            /* res1_1                        @ H/2  */          \
+    FB(8, 32, 8, 1, true, false, false, 16, 16, RES2_BH, RES2_BW, 8, 8, 1)                 /* res2_1, res2_2                @ H/4  */          \
+    FB(8, 32, 8, 2, false, false, false, 16, 20, 1, 1, 8, 8, 1)          /* conv2_2/2_3/3_1               H/4 -> H/8 */      \
+    FB(8, 48, 8, 1, true, false, false, 16, 20, 1, 2, 8, 8, 2)           /* res3_1, res3_2                @ H/8  */          \
+    FB(8, 48, 16, 1, false, false, false, 16, 20, 1, 2, 8, 8, 2)         /* conv3_2/3_3/3_4 (fallback)    @ H/8  */          \
+    FB(16, 96, 16, 1, true, false, false, 16, 20, 1, 2, 8, 8, 1)         /* res3_3 .. res3_6 (fallback)   @ H/8  */          \
+    FB(16, 96, 24, 2, false, false, false, 16, 20, 1, 1, 8, 8, 1)        /* conv3_5/3_6/4_1               H/8 -> H/16 */     \
+    FB(24, 136, 24, 1, true, false, false, 16, 20, 1, 1, 8, 8, 1)        /* res4_1 .. res4_4 (fallback)   @ H/16 */
 
 int launch_fused_block(int cin, int cexp, int cout, int stride, bool res, bool relu_out, int pre_c0, const FbArgs& a, int N,
                        hipStream_t s, int dtype)
@@ -503,8 +363,8 @@ int launch_fused_block(int cin, int cexp, int cout, int stride, bool res, bool r
         if (!(cin == 8 && cexp == 8 && cout == 4 && stride == 1 && !res && !relu_out)) return -1;
 #define YF_STEM_C0(C0_)                                                                                                                            \
         if (pre_c0 == C0_)                                                                                                                          \
-            return dtype == DT_F16 ? launch_fb_t<8, 8, 4, 1, false, false, true, 16, 16, 1, 2, 8, 8, 1, false, half_t, C0_>(a, N, s) \
-                                   : launch_fb_t<8, 8, 4, 1, false, false, true, 16, 16, 1, 2, 8, 8, 1, false, float, C0_>(a, N, s);
+            return dtype == DT_F16 ? launch_fb_t<8, 8, 4, 1, false, false, true, 16, 16, 1, 2, 8, 8, 1, half_t, C0_>(a, N, s) \
+                                   : launch_fb_t<8, 8, 4, 1, false, false, true, 16, 16, 1, 2, 8, 8, 1, float, C0_>(a, N, s);
         YF_STEM_C0(2) YF_STEM_C0(3) YF_STEM_C0(4)
 #undef YF_STEM_C0
         return -1;
@@ -515,13 +375,13 @@ int launch_fused_block(int cin, int cexp, int cout, int stride, bool res, bool r
         const int n_cu = device_cu_count(current_device());
         const long big = (long)N * ((a.Ho + 16 * RES2_BH - 1) / (16 * RES2_BH)) * ((a.Wo + 16 * RES2_BW - 1) / (16 * RES2_BW));
         if (n_cu > 0 && 2 * big <= n_cu)
-            return dtype == DT_F16 ? launch_fb_t<8, 32, 8, 1, true, false, false, 16, 16, 1, 1, 8, 8, 1, false, half_t>(a, N, s)
-                                   : launch_fb_t<8, 32, 8, 1, true, false, false, 16, 16, 1, 1, 8, 8, 1, false, float>(a, N, s);
+            return dtype == DT_F16 ? launch_fb_t<8, 32, 8, 1, true, false, false, 16, 16, 1, 1, 8, 8, 1, half_t>(a, N, s)
+                                   : launch_fb_t<8, 32, 8, 1, true, false, false, 16, 16, 1, 1, 8, 8, 1, float>(a, N, s);
     }
-#define FB(ci, ce, co, st, rs, ro, pr, tyb, txb, bh, bw, ec, cg, pe, xl)                                          \
+#define FB(ci, ce, co, st, rs, ro, pr, tyb, txb, bh, bw, ec, cg, pe)                                              \
     if (cin == ci && cexp == ce && cout == co && stride == st && res == rs && relu_out == ro && pre == pr)         \
-        return dtype == DT_F16 ? launch_fb_t<ci, ce, co, st, rs, ro, pr, tyb, txb, bh, bw, ec, cg, pe, xl, half_t>(a, N, s)   \
-                               : launch_fb_t<ci, ce, co, st, rs, ro, pr, tyb, txb, bh, bw, ec, cg, pe, xl, float>(a, N, s);
+        return dtype == DT_F16 ? launch_fb_t<ci, ce, co, st, rs, ro, pr, tyb, txb, bh, bw, ec, cg, pe, half_t>(a, N, s)       \
+                               : launch_fb_t<ci, ce, co, st, rs, ro, pr, tyb, txb, bh, bw, ec, cg, pe, float>(a, N, s);
     YF_FB_SHAPES(FB)
 #undef FB
     return -1;
@@ -530,7 +390,7 @@ int launch_fused_block(int cin, int cexp, int cout, int stride, bool res, bool r
 int fb_chunk_channels(int cin, int cexp, int cout, int stride, bool res, bool relu_out, int pre_c0)
 {
     const bool pre = pre_c0 != 0;
-#define FB(ci, ce, co, st, rs, ro, pr, tyb, txb, bh, bw, ec, cg, pe, xl) \
+#define FB(ci, ce, co, st, rs, ro, pr, tyb, txb, bh, bw, ec, cg, pe) \
     if (cin == ci && cexp == ce && cout == co && stride == st && res == rs && relu_out == ro && pre == pr) return ec;
     YF_FB_SHAPES(FB)
 #undef FB
@@ -559,15 +419,6 @@ void fb_pack_weights(const float* w1 /*[cin][cexp]*/, const float* b1, const flo
             for (int co = 0; co < cout; ++co) o[j * cout + co] = w2[(size_t)(ch * ec + j) * cout + co];
     }
     for (int co = 0; co < cout; ++co) out[(size_t)(cexp / ec) * CHF + co] = b2[co];
-}
-
-int launch_k19(K19Args a, int N, hipStream_t s, int dtype)
-{
-    a.tiles_y = (a.Ho + 15) / 16;
-    a.tiles_x = (a.Wo + 15) / 16;
-    if (dtype == DT_F16) hipLaunchKernelGGL(k19_kernel<half_t>, dim3((unsigned)(N * a.tiles_y * a.tiles_x)), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(k19_kernel<float>, dim3((unsigned)(N * a.tiles_y * a.tiles_x)), dim3(256), 0, s, a);
-    return 0;
 }
 
 }  // namespace yf

@@ -3,8 +3,8 @@
 // of today; the region-buffer scheme below is k19m_kernel, which serves the split-operand (DT_F16X3) engine.            (reference: src/model_training/model/yolo_fastest.py:86-89)
 //
 // conv1_9 is 22 % of the network's MACs: an implicit GEMM  D[cout][pixel] = sum_k W[cout][k] X[k][pixel]  with k = (tap, cin),
-// K = 9 x 24 = 216.  The VALU version (k19_kernel, yf_fused_kernels.hip) runs at ~30 TMAC/s (250 us for 256 frames); this one
-// at 37 TMAC/s fp32 (200 us) and 80 us with fp16 storage:
+// K = 9 x 24 = 216.  The VALU version (removed: DESIGN_HISTORY.md, "Removal of the leftovers") ran at ~30 TMAC/s (250 us for 256 frames); the region-buffer
+// scheme at 37 TMAC/s fp32 (200 us) and 80 us with fp16 storage:
 //   * a persistent workgroup (512 threads: 8 waves, two per SIMD, one output row each) per CU walks over 8x16-pixel output
 //     tiles; two region buffers in LDS (2 x 55 KB fp32), ONE barrier per tile;
 //   * phase 1 (conv1_8 over the tile's 17x33 input region -> LDS, as even-column / odd-column planes of 24-channel records,
@@ -44,19 +44,16 @@ constexpr int RS = 24;                     // record stride in elements
 // (fp16 storage: multiples of 8 halves, the 16-byte pair records of the K = 32 MFMA fragments must stay 16-byte aligned)
 constexpr int plane_stride(bool h16) { return 17 * RS + (h16 ? 8 : 4); }
 constexpr int row_stride(bool h16) { return 2 * plane_stride(h16) + (h16 ? 8 : 4); }
-constexpr int NG = 14;                     // k groups
 constexpr int NU = 5;                      // px-tiles of phase 1 per wave (36 over 8 waves)
-constexpr int NCHUNK = 54;                 // 9 taps x 6 chunks of 4 channels
-constexpr int W9_F32 = NG * 4 * 2 * 64, W21_F32 = 2 * 4 * 64;
-// fp32 only: channels 16..23 of conv1_9 (the half-empty second M-tile) on v_mfma_f32_4x4x1_16B_f32 instead -- weights
-// [g][cg][lane][s] (staged in LDS) and conv2_1's two k-steps for those channels [t][lane]
-constexpr int WQ_F32 = NG * 2 * 64 * 4, W21Q_F32 = 2 * 64;
-constexpr int W9_F16 = NG * 2 * 64 * 2, W21_F16 = 2 * 64 * 2;  // in floats (f16x4 = 2 floats per lane)
-// split-operand mode (DT_F16X3): [W9 hi | W21 hi | W9 lo | W21 lo], each in the fp16 layout
-constexpr int WX3_HALF = W9_F16 + W21_F16;
-// X3 walks K in NG2 = 7 groups of 32 k-values on v_mfma_f32_16x16x32_f16 (the K = 32 form issues in the cycles of the K = 16 one:
+// k19m_kernel walks K in NG2 = 7 groups of 32 k-values on v_mfma_f32_16x16x32_f16 (the K = 32 form issues in the cycles of the K = 16 one:
 // tools/mfma16_probe.hip): lane group j holds the PAIR of 4-channel chunks 2 (4 g + j), 2 (4 g + j) + 1 -- 27 pairs = 9 taps x 3
 constexpr int NG2 = 7, NPAIR = 27;
+// k19m_kernel's packed weights (WM_F16X3), in floats: [W9 hi | W21 hi | W9 lo | W21 lo] -- conv1_9's f16x8 fragments [g][mt][lane] (4 floats
+// per lane) and conv2_1's f16x4 fragments [mt][lane] (2 floats per lane), first the hi halves of the split operands, then the lo halves
+constexpr int W9_F16 = NG2 * 2 * 64 * 4, W21_F16 = 2 * 64 * 2;
+constexpr int WX3_HALF = W9_F16 + W21_F16;
+constexpr int M_FLOATS = 2 * WX3_HALF;
+static_assert(W9_F16 % 4 == 0 && WX3_HALF % 4 == 0, "16-byte loads of the packed weights");
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 }  // namespace
 
@@ -293,6 +290,33 @@ __global__ void __launch_bounds__(512) k19m_kernel(K19Args a)
     }
 }
 
+// w9: [tap][cin][cout] (blob layout of the dense 3x3), w21: [cin][cout] -- for all three packers
+static void k19m_pack_weights(const float* w9, const float* w21, float* out)
+{
+    uint16_t* oh = reinterpret_cast<uint16_t*>(out);
+    uint16_t* ol = reinterpret_cast<uint16_t*>(out + WX3_HALF);   // the lo halves, same layout
+    // K = 32 fragments: lane (cout, jj) holds k = 8 jj + e = chunk 2 (4 g + jj) + (e >> 2), channel e & 3
+    for (int g = 0; g < NG2; ++g)
+        for (int mt = 0; mt < 2; ++mt)
+            for (int l = 0; l < 64; ++l)
+                for (int e = 0; e < 8; ++e) {
+                    const int cout = 16 * mt + (l & 15), jj = l >> 4, fp = 4 * g + jj, fc = 2 * fp + (e >> 2);
+                    const int tap = fc / 6, c = (fc % 6) * 4 + (e & 3);
+                    const float v = (fp < NPAIR && cout < 24) ? w9[((size_t)tap * 24 + c) * 24 + cout] : 0.f;
+                    oh[((size_t)(g * 2 + mt) * 64 + l) * 8 + e] = f32_to_f16_bits(v);
+                    ol[((size_t)(g * 2 + mt) * 64 + l) * 8 + e] = f16_lo_bits(v);
+                }
+    // conv2_1: k-step r of lane group jj <-> channel 16 mt + 4 jj + r, the accumulator layout of phase 2
+    for (int mt = 0; mt < 2; ++mt)
+        for (int r = 0; r < 4; ++r)
+            for (int l = 0; l < 64; ++l) {
+                const int c2 = l & 15, jj = l >> 4, c1 = 16 * mt + 4 * jj + r;
+                const float v = (c2 < 8 && c1 < 24) ? w21[c1 * 8 + c2] : 0.f;
+                oh[(size_t)W9_F16 * 2 + ((size_t)mt * 64 + l) * 4 + r] = f32_to_f16_bits(v);
+                ol[(size_t)W9_F16 * 2 + ((size_t)mt * 64 + l) * 4 + r] = f16_lo_bits(v);
+            }
+}
+
 
 // ------------------------------------------------------------------------------------------------
 // k19r_kernel (fp32): the same three layers WITHOUT the region buffers.  conv1_8 is a K = 4 GEMM, one v_mfma_f32_16x16x4_f32 per 16
@@ -315,7 +339,11 @@ namespace {
 constexpr int R_PS = 100, R_RS = 2 * R_PS;   // floats: plane (17 even-column records + pad) and row stride of a wave's slice
 constexpr int R_SLICE = 3 * R_RS;            // floats per wave
 constexpr int R_WA = 9 * 4 * 64, R_WB = 9 * 2 * 64, R_WQ = 9 * 3 * 64 * 4;   // floats: conv1_9 A fragments (channels 0..15 / 16..23), 4x4x1 table
-constexpr int R_OFF = W9_F32 + W21_F32 + WQ_F32 + W21Q_F32;                     // the k19r stream follows k19m's in the packed blob
+constexpr int R_W21F = 4 * 64, R_W21Q = 2 * 64;                              // floats: conv2_1's k-steps for channels 0..15 / 16..23, [k-step][lane]
+// k19r_kernel's packed weights (WM_F32): [w21f | w21q | WA | WB | 4x4x1 table | lane-major WA | lane-major WB]
+constexpr int R_O_W21F = 0, R_O_W21Q = R_O_W21F + R_W21F, R_O_WA = R_O_W21Q + R_W21Q, R_O_WB = R_O_WA + R_WA, R_O_WQ = R_O_WB + R_WB;
+constexpr int R_FLOATS = R_O_WQ + R_WQ + R_WA + R_WB;
+static_assert(R_O_W21Q % 4 == 0 && R_O_WA % 4 == 0 && R_O_WB % 4 == 0 && R_O_WQ % 4 == 0 && (R_WQ + R_WA) % 4 == 0, "16-byte loads of the packed weights");
 }  // namespace
 
 // WLDS: conv1_9's A fragments (54 per lane) are read from LDS per tap instead of living in registers -- 16 waves per CU fit then
@@ -332,29 +360,29 @@ __global__ void __launch_bounds__(R_NW * 64) k19r_kernel(K19Args a)
 
     // the 4x4x1 table and, WLDS, the lane-major copies of the fragments ([t][lane][4] | [t][lane][2]) that follow it in the blob: one staging
     // pass with every 16-byte load in flight (transposing [t][s][lane] here cost three dependent rounds of 4-byte loads per workgroup)
-    stage_to_lds<R_WQ + (WLDS ? R_WA + R_WB : 0), R_NW * 64>(WQ, a.wp + R_OFF + R_WA + R_WB);
+    stage_to_lds<R_WQ + (WLDS ? R_WA + R_WB : 0), R_NW * 64>(WQ, a.wp + R_O_WQ);
     // ---- weights in registers for the lifetime of the wave ----
     float wA[WLDS ? 1 : 9][4], wB[WLDS ? 1 : 9][2];
     if constexpr (!WLDS) {
 #pragma unroll
         for (int t = 0; t < 9; ++t) {
 #pragma unroll
-            for (int s = 0; s < 4; ++s) wA[t][s] = a.wp[R_OFF + (t * 4 + s) * 64 + lane];
+            for (int s = 0; s < 4; ++s) wA[t][s] = a.wp[R_O_WA + (t * 4 + s) * 64 + lane];
 #pragma unroll
-            for (int s = 0; s < 2; ++s) wB[t][s] = a.wp[R_OFF + R_WA + (t * 2 + s) * 64 + lane];
+            for (int s = 0; s < 2; ++s) wB[t][s] = a.wp[R_O_WB + (t * 2 + s) * 64 + lane];
         }
     }
     float w21f[4], w21q[2], biasq[2], bias9[4], bias21[4], bias8[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        w21f[r] = a.wp[W9_F32 + r * 64 + lane];            // M-tile 0 of k19m's conv2_1 fragments: k-step r <-> channel 4j + r
+        w21f[r] = a.wp[R_O_W21F + r * 64 + lane];          // conv2_1, k-step r <-> channel 4j + r
         bias9[r] = a.b9[4 * j + r];
         bias8[r] = a.b8[4 * j + r];
         bias21[r] = j < 2 ? a.b21[4 * j + r] : 0.f;
     }
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-        w21q[t] = a.wp[W9_F32 + W21_F32 + WQ_F32 + t * 64 + lane];
+        w21q[t] = a.wp[R_O_W21Q + t * 64 + lane];           // conv2_1, k-step t <-> channel 16 + 4t + j
         biasq[t] = a.b9[16 + 4 * t + j];
     }
     const float w8a = a.w8[j * 24 + p];                     // conv1_8's A operand, channels 0..15: row = cout p, k = cin j
@@ -502,6 +530,34 @@ __global__ void __launch_bounds__(R_NW * 64) k19r_kernel(K19Args a)
     }
 }
 
+static void k19r_pack_weights(const float* w9, const float* w21, float* out)
+{
+    for (int l = 0; l < 64; ++l) {
+        const int c2 = l & 15, jj = l >> 4;
+        for (int r = 0; r < 4; ++r) out[R_O_W21F + r * 64 + l] = c2 < 8 ? w21[(4 * jj + r) * 8 + c2] : 0.f;
+        for (int t = 0; t < 2; ++t) out[R_O_W21Q + t * 64 + l] = c2 < 8 ? w21[(16 + 4 * t + jj) * 8 + c2] : 0.f;
+    }
+    // conv1_9 per tap: k-step s of lane group jj is input channel 4 jj + s (channels 0..15) resp. 16 + 2 jj + s (16..23)
+    float* wa = out + R_O_WA;
+    float* wb = out + R_O_WB;
+    float* wr = out + R_O_WQ;
+    for (int tap = 0; tap < 9; ++tap)
+        for (int l = 0; l < 64; ++l) {
+            const int m = l & 15, jj = l >> 4;
+            for (int s = 0; s < 4; ++s) wa[(tap * 4 + s) * 64 + l] = w9[((size_t)tap * 24 + 4 * jj + s) * 24 + m];
+            for (int s = 0; s < 2; ++s) wb[(tap * 2 + s) * 64 + l] = w9[((size_t)tap * 24 + 16 + 2 * jj + s) * 24 + m];
+            // the 4x4x1 table: [tap][0: cg 0, s 0..3 | 1: cg 1, s 0..3 | 2: (cg 0, s 4..5), (cg 1, s 4..5)][lane][4]
+            for (int cg = 0; cg < 2; ++cg) {
+                const int cout = 16 + 4 * cg + (l & 3);
+                for (int s = 0; s < 4; ++s) wr[((tap * 3 + cg) * 64 + l) * 4 + s] = w9[((size_t)tap * 24 + 4 * jj + s) * 24 + cout];
+                for (int s = 0; s < 2; ++s) wr[((tap * 3 + 2) * 64 + l) * 4 + 2 * cg + s] = w9[((size_t)tap * 24 + 16 + 2 * jj + s) * 24 + cout];
+            }
+            // lane-major copies of the A fragments (the 16-wave form reads them from LDS: one b128 + one b64 per tap), behind the 4x4x1 table
+            for (int s = 0; s < 4; ++s) wr[R_WQ + (tap * 64 + l) * 4 + s] = wa[(tap * 4 + s) * 64 + l];
+            for (int s = 0; s < 2; ++s) wr[R_WQ + R_WA + (tap * 64 + l) * 2 + s] = wb[(tap * 2 + s) * 64 + l];
+        }
+}
+
 
 // ------------------------------------------------------------------------------------------------
 // k19h_kernel (fp16 storage): k19r_kernel's scheme on the fp16 matrix pipe.  Per tap and 16 output pixels
@@ -514,7 +570,7 @@ __global__ void __launch_bounds__(R_NW * 64) k19r_kernel(K19Args a)
 //     every lane group, so the second result block costs one conversion and one ReLU, not two; the channel permutation lives in the
 //     host-side packing of A (k19_pack_weights), for conv1_9's own channels 16..23 (rows of its second M-tile) and conv2_1's k order likewise;
 //   * the epilogue (bias + ReLU -> the same k <-> channel map -> ONE K = 32 k-step of conv2_1) stays in registers.
-// Against k19m_kernel<half_t> (138 us at 640x512 batch 128): no region buffers, no workgroup barrier per tile, no phase-1 LDS store traffic;
+// Against the region-buffer scheme with fp16 storage (removed; 138 us at 640x512 batch 128): no region buffers, no workgroup barrier per tile, no phase-1 LDS store traffic;
 // per 16 output pixels 18 v_mfma_f32_16x16x32_f16 + 18 v_mfma_f32_4x4x4_16B_f16 instead of 14 + 9 v_mfma_f32_16x16x4_f32, and the VALU
 // work of a wave (ReLU, conversions, padding selects) runs under the fp16 MFMAs of the SIMD's other waves (tools/coissue_probe.hip:
 // the fp16 matrix pipe co-issues with VALU, the fp32 one does not).  conv1_8's weights are rounded to fp16 here (k19m keeps them fp32).
@@ -525,14 +581,14 @@ constexpr int H_PS = 72, H_RS = 2 * H_PS, H_SLICE = 3 * H_RS;   // halves: plane
 constexpr int H_BT = 48;                                        // floats: the wave's bias table behind its slice ([j][bias9 x 8 | bias21 x 4])
 constexpr int H_WAVE_BYTES = H_SLICE * 2 + H_BT * 4 + 64 * 16; // + conv2_1's fragment, 16 bytes per lane
 constexpr int H_W9 = 9 * 2 * 64 * 4, H_W21 = 64 * 4;            // floats (an f16x8 fragment = 4 floats per lane)
-constexpr int H_OFF = W9_F16 + W21_F16;                         // the k19h stream follows k19m's in the fp16 blob
-constexpr int X_OFF = 2 * WX3_HALF;                             // f16x3 blob: [W9 hi | W9 lo | W21 hi | W21 lo] behind k19m's stream, in
-                                                                // k19h_kernel's fragment layout (packed, read by no kernel since k19x_kernel went)
+// k19h_kernel's packed weights (WM_F16): [W9 | W21] -- conv1_9's fragments [tap][mt][lane], conv2_1's [lane]
+constexpr int H_O_W9 = 0, H_O_W21 = H_O_W9 + H_W9, H_FLOATS = H_O_W21 + H_W21;
+static_assert(H_O_W21 % 4 == 0, "16-byte loads of the packed weights");
 }  // namespace
 
 // WPS: waves per SIMD the register budget is set for (HIP's second launch bound): 3 -> 128 VGPRs without spills; 4 -> two weight fragments
 // are reloaded from scratch per item.  Measured at 640x512 batch 128 (tools/scratch/k19h_forms.sh): 4 waves per workgroup x 3 per SIMD
-// 69.6 us | 4 x 4 70.5 | 8 x 4 70.5 | 4 x 2 78.6 | k19m_kernel<half_t> 138 (with four + four conversions per tap: 74 | 80 | 80 | 87, and conv1_8
+// 69.6 us | 4 x 4 70.5 | 8 x 4 70.5 | 4 x 2 78.6 | the region-buffer scheme 138 (with four + four conversions per tap: 74 | 80 | 80 | 87, and conv1_8
 // on K-padded 16x16x16 MFMAs, 80).
 // Where the time goes (timing builds, at 74 us): the 18 K = 32 k-steps of an item are 288 of its ~1100 SIMD cycles; the 4x4x4 MFMAs, the
 // conversions and the global loads are worth 4 / 10 / 4 us.  The fp16 matrix pipe co-issues with another wave's VALU instruction only
@@ -553,14 +609,14 @@ __global__ void __launch_bounds__(R_NW * 64, WPS) k19h_kernel(K19Args a)
     // ---- weights in registers for the lifetime of the wave: 18 x 4 + 4 + 4 VGPRs ----
     f16x8 wA[9][2];
     {
-        const f16x8* w = reinterpret_cast<const f16x8*>(a.wp + H_OFF);
+        const f16x8* w = reinterpret_cast<const f16x8*>(a.wp + H_O_W9);
 #pragma unroll
         for (int t = 0; t < 9; ++t)
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt) wA[t][mt] = w[(t * 2 + mt) * 64 + lane];
     }
     f32x4* const W21L = reinterpret_cast<f32x4*>(k19_smem + wave * H_WAVE_BYTES + H_SLICE * 2 + H_BT * 4) + lane;   // used once per item: LDS, not 4 VGPRs
-    *W21L = reinterpret_cast<const f32x4*>(a.wp + H_OFF + H_W9)[lane];
+    *W21L = reinterpret_cast<const f32x4*>(a.wp + H_O_W21)[lane];
     f16x4 w8A[2];
     f32x4 bias8[2];
 #pragma unroll
@@ -668,106 +724,33 @@ __global__ void __launch_bounds__(R_NW * 64, WPS) k19h_kernel(K19Args a)
     }
 }
 
-size_t k19_packed_floats(int wmode)
+static void k19h_pack_weights(const float* w9, const float* w21, float* out)
 {
-    return wmode == WM_F16X3 ? (size_t)(X_OFF + 2 * (H_W9 + H_W21)) : wmode == WM_F16 ? (size_t)(H_OFF + H_W9 + H_W21) : (size_t)(R_OFF + 2 * (R_WA + R_WB) + R_WQ);
+    uint16_t* o9 = reinterpret_cast<uint16_t*>(out + H_O_W9);
+    uint16_t* o21 = reinterpret_cast<uint16_t*>(out + H_O_W21);
+    for (int l = 0; l < 64; ++l)
+        for (int e = 0; e < 8; ++e) {
+            // k-value e of lane group jj = row i of conv1_8's two result blocks: channels 4 jj + e (e < 4), 16 + 2 jj + e - 4 (e = 4, 5), none (6, 7);
+            // the second M-tile's rows carry conv1_9's channels 16..23 the same way (row 4 g + i: channel 16 + 2 g + i, i < 2)
+            const int m = l & 15, jj = l >> 4, ch = e < 4 ? 4 * jj + e : e < 6 ? 16 + 2 * jj + e - 4 : -1;
+            for (int tap = 0; tap < 9; ++tap)
+                for (int mt = 0; mt < 2; ++mt) {
+                    const int cout = mt == 0 ? m : (m & 3) < 2 ? 16 + 2 * (m >> 2) + (m & 3) : -1;
+                    const float v = ch >= 0 && cout >= 0 ? w9[((size_t)tap * 24 + ch) * 24 + cout] : 0.f;
+                    o9[((size_t)(tap * 2 + mt) * 64 + l) * 8 + e] = f32_to_f16_bits(v);
+                }
+            const float v21 = ch >= 0 && m < 8 ? w21[ch * 8 + m] : 0.f;
+            o21[(size_t)l * 8 + e] = f32_to_f16_bits(v21);
+        }
 }
 
-// w9: [tap][cin][cout] (blob layout of the dense 3x3), w21: [cin][cout].  The layouts are those of the kernels of rounds 1-6: in the fp32
-// blob the region-buffer segment in front of R_OFF, in the fp16 blob the one in front of H_OFF and in the f16x3 blob the one behind X_OFF
-// are packed but read by no kernel since the forms that read them were removed (follow-up: drop them together with the offsets).
+size_t k19_packed_floats(int wmode) { return wmode == WM_F16X3 ? M_FLOATS : wmode == WM_F16 ? H_FLOATS : R_FLOATS; }
+
 void k19_pack_weights(const float* w9, const float* w21, float* out, int wmode)
 {
-    const bool h16 = wmode != WM_F32, x3 = wmode == WM_F16X3;
-    uint16_t* oh = reinterpret_cast<uint16_t*>(out);
-    uint16_t* ol = reinterpret_cast<uint16_t*>(out + WX3_HALF);   // x3: the lo halves, same layout
-    if (h16) {   // K = 32 fragments: lane (cout, jj) holds k = 8 jj + e = chunk 2 (4 g + jj) + (e >> 2), channel e & 3
-        for (int g = 0; g < NG2; ++g)
-            for (int mt = 0; mt < 2; ++mt)
-                for (int l = 0; l < 64; ++l)
-                    for (int e = 0; e < 8; ++e) {
-                        const int cout = 16 * mt + (l & 15), jj = l >> 4, fp = 4 * g + jj, fc = 2 * fp + (e >> 2);
-                        const int tap = fc / 6, c = (fc % 6) * 4 + (e & 3);
-                        const float v = (fp < NPAIR && cout < 24) ? w9[((size_t)tap * 24 + c) * 24 + cout] : 0.f;
-                        oh[((size_t)(g * 2 + mt) * 64 + l) * 8 + e] = f32_to_f16_bits(v);
-                        if (x3) ol[((size_t)(g * 2 + mt) * 64 + l) * 8 + e] = f16_lo_bits(v);
-                    }
-    }
-    if (h16) {   // k19h_kernel: per tap ONE K = 32 fragment per M-tile (x3: [W9 hi | W9 lo | W21 hi | W21 lo] behind k19m's stream)
-        uint16_t* o9 = reinterpret_cast<uint16_t*>(out + (x3 ? X_OFF : H_OFF));
-        uint16_t* o21 = reinterpret_cast<uint16_t*>(out + (x3 ? X_OFF + 2 * H_W9 : H_OFF + H_W9));
-        uint16_t* o9l = reinterpret_cast<uint16_t*>(out + X_OFF + H_W9);
-        uint16_t* o21l = reinterpret_cast<uint16_t*>(out + X_OFF + 2 * H_W9 + H_W21);
-        for (int l = 0; l < 64; ++l)
-            for (int e = 0; e < 8; ++e) {
-                // k-value e of lane group jj = row i of conv1_8's two result blocks: channels 4 jj + e (e < 4), 16 + 2 jj + e - 4 (e = 4, 5), none (6, 7);
-                // the second M-tile's rows carry conv1_9's channels 16..23 the same way (row 4 g + i: channel 16 + 2 g + i, i < 2)
-                const int m = l & 15, jj = l >> 4, ch = e < 4 ? 4 * jj + e : e < 6 ? 16 + 2 * jj + e - 4 : -1;
-                for (int tap = 0; tap < 9; ++tap)
-                    for (int mt = 0; mt < 2; ++mt) {
-                        const int cout = mt == 0 ? m : (m & 3) < 2 ? 16 + 2 * (m >> 2) + (m & 3) : -1;
-                        const float v = ch >= 0 && cout >= 0 ? w9[((size_t)tap * 24 + ch) * 24 + cout] : 0.f;
-                        o9[((size_t)(tap * 2 + mt) * 64 + l) * 8 + e] = f32_to_f16_bits(v);
-                        if (x3) o9l[((size_t)(tap * 2 + mt) * 64 + l) * 8 + e] = f16_lo_bits(v);
-                    }
-                const float v21 = ch >= 0 && m < 8 ? w21[ch * 8 + m] : 0.f;
-                o21[(size_t)l * 8 + e] = f32_to_f16_bits(v21);
-                if (x3) o21l[(size_t)l * 8 + e] = f16_lo_bits(v21);
-            }
-    }
-    for (int g = 0; g < (h16 ? 0 : NG); ++g)
-        for (int s = 0; s < 4; ++s)
-            for (int mt = 0; mt < 2; ++mt)
-                for (int l = 0; l < 64; ++l) {
-                    const int cout = 16 * mt + (l & 15), jj = l >> 4, fc = 4 * g + jj;
-                    const int tap = fc / 6, c = (fc % 6) * 4 + s;
-                    const float v = (fc < NCHUNK && cout < 24) ? w9[((size_t)tap * 24 + c) * 24 + cout] : 0.f;
-                    out[((g * 4 + s) * 2 + mt) * 64 + l] = v;
-                }
-    for (int mt = 0; mt < 2; ++mt)
-        for (int r = 0; r < 4; ++r)
-            for (int l = 0; l < 64; ++l) {
-                const int c2 = l & 15, jj = l >> 4, c1 = 16 * mt + 4 * jj + r;
-                const float v = (c2 < 8 && c1 < 24) ? w21[c1 * 8 + c2] : 0.f;
-                if (h16) oh[(size_t)W9_F16 * 2 + ((size_t)mt * 64 + l) * 4 + r] = f32_to_f16_bits(v);
-                else out[W9_F32 + (mt * 4 + r) * 64 + l] = v;
-                if (x3) ol[(size_t)W9_F16 * 2 + ((size_t)mt * 64 + l) * 4 + r] = f16_lo_bits(v);
-            }
-    if (!h16) {   // the 4x4-block form of channels 16..23 (the removed fp32 region-buffer form)
-        float* wq = out + W9_F32 + W21_F32;
-        for (int g = 0; g < NG; ++g)
-            for (int cg = 0; cg < 2; ++cg)
-                for (int l = 0; l < 64; ++l)
-                    for (int s = 0; s < 4; ++s) {
-                        const int jj = l >> 4, fc = 4 * g + jj, tap = fc / 6, c = (fc % 6) * 4 + s, cout = 16 + 4 * cg + (l & 3);
-                        wq[((g * 2 + cg) * 64 + l) * 4 + s] = fc < NCHUNK ? w9[((size_t)tap * 24 + c) * 24 + cout] : 0.f;
-                    }
-        float* w21q = wq + WQ_F32;
-        for (int t = 0; t < 2; ++t)
-            for (int l = 0; l < 64; ++l) {
-                const int c2 = l & 15, c1 = 16 + 4 * t + (l >> 4);
-                w21q[t * 64 + l] = c2 < 8 ? w21[c1 * 8 + c2] : 0.f;
-            }
-        // k19r_kernel: per tap, k-step s of lane group jj is input channel 4 jj + s (channels 0..15) resp. 16 + 2 jj + s (16..23)
-        float* wa = out + R_OFF;
-        float* wb = wa + R_WA;
-        float* wr = wb + R_WB;
-        for (int tap = 0; tap < 9; ++tap)
-            for (int l = 0; l < 64; ++l) {
-                const int m = l & 15, jj = l >> 4;
-                for (int s = 0; s < 4; ++s) wa[(tap * 4 + s) * 64 + l] = w9[((size_t)tap * 24 + 4 * jj + s) * 24 + m];
-                for (int s = 0; s < 2; ++s) wb[(tap * 2 + s) * 64 + l] = w9[((size_t)tap * 24 + 16 + 2 * jj + s) * 24 + m];
-                // the 4x4x1 table: [tap][0: cg 0, s 0..3 | 1: cg 1, s 0..3 | 2: (cg 0, s 4..5), (cg 1, s 4..5)][lane][4]
-                for (int cg = 0; cg < 2; ++cg) {
-                    const int cout = 16 + 4 * cg + (l & 3);
-                    for (int s = 0; s < 4; ++s) wr[((tap * 3 + cg) * 64 + l) * 4 + s] = w9[((size_t)tap * 24 + 4 * jj + s) * 24 + cout];
-                    for (int s = 0; s < 2; ++s) wr[((tap * 3 + 2) * 64 + l) * 4 + 2 * cg + s] = w9[((size_t)tap * 24 + 16 + 2 * jj + s) * 24 + cout];
-                }
-                // lane-major copies of the A fragments (the 16-wave form reads them from LDS: one b128 + one b64 per tap), behind the 4x4x1 table
-                for (int s = 0; s < 4; ++s) wr[R_WQ + (tap * 64 + l) * 4 + s] = wa[(tap * 4 + s) * 64 + l];
-                for (int s = 0; s < 2; ++s) wr[R_WQ + R_WA + (tap * 64 + l) * 2 + s] = wb[(tap * 2 + s) * 64 + l];
-            }
-    }
+    if (wmode == WM_F16X3) k19m_pack_weights(w9, w21, out);
+    else if (wmode == WM_F16) k19h_pack_weights(w9, w21, out);
+    else k19r_pack_weights(w9, w21, out);
 }
 
 // Pixels of the 4-channel input that the two kernels' UNCHECKED 16-byte loads may touch before / after the tensor (W = its width in pixels).

@@ -218,7 +218,6 @@ struct FbArgs {
     const uint8_t* in_u8;         // PRE only, optional: u8 frames instead of `in` (pre-process fused into the load): gray [N,h,w], or --
                                   // C0 = 3 -- cv2's HWC BGR [N,h,w,3], channel-flipped on the fly (detect.py:119)
     int u8_down2;                 //   1: the u8 frame is exactly 2x the net input (2x2 box mean first)
-    unsigned long long* dbg;      // unused: kept so that the kernel-argument layout stays as it is
 };
 // pre: 0 = no conv0 in front; 1 / 3 = conv0 on that many input channels evaluated on the fly
 int launch_fused_block(int cin, int cexp, int cout, int stride, bool res, bool relu_out, int pre, const FbArgs& a, int N,
@@ -287,16 +286,15 @@ void dcat_pack_weights_x3(const float* w_cat, const float* b_deconv, const float
 struct K19Args {
     const float* in;              // NHWC [N,H,W,4] (res1_1 output, stride-2 resolution)
     const float *w8, *b8;         // conv1_8 [4][24]
-    const float *w9, *b9;         // conv1_9 [3][3][24][24]
-    const float *w21, *b21;       // conv2_1 [24][8]
+    const float* b9;              // conv1_9's bias [24] (its weights [3][3][24][24] travel in wp)
+    const float* b21;             // conv2_1's bias [8] (its weights [24][8] travel in wp)
     float* out;                   // NHWC [N,Ho,Wo,8]
     int H, W, Ho, Wo;
     int tiles_y, tiles_x;
-    const float* wp;              // k19m: MFMA A fragments of conv1_9 and conv2_1 (k19_pack_weights)
+    const float* wp;              // MFMA A fragments of conv1_9 and conv2_1 (k19_pack_weights)
     int n_frames;
 };
-int launch_k19(K19Args a, int N, hipStream_t s, int dtype = DT_F32);    // VALU version: no caller left (follow-up: remove it with k19_kernel)
-int launch_k19m(K19Args a, int N, hipStream_t s, int dtype = DT_F32);   // matrix-core version (the plan's)
+int launch_k19m(K19Args a, int N, hipStream_t s, int dtype = DT_F32);
 size_t k19_packed_floats(int wmode = WM_F32);
 size_t k19m_guard_elems(int W);   // the engine keeps this many elements free before and after the workspace slots
 void k19_pack_weights(const float* w9, const float* w21, float* out, int wmode = WM_F32);

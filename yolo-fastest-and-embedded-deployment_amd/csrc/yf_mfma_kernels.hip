@@ -187,9 +187,6 @@ __global__ void __launch_bounds__(256) pw_mfma_kernel(PwArgs a)
 // A workgroup is RS "row streams" x NUG unit groups of waves, sized to a multiple of 4 waves: the dispatcher deals a workgroup's
 // waves to the SIMDs in a fixed pattern, so a 6-wave workgroup loads SIMDs 2,2,1,1 and a second one does not fit beside it
 // (measured: 1 workgroup per CU resident, two sequential rounds).
-__device__ __forceinline__ bool v0guard(float v) { return v != 123456.f; }  // DBG: keeps the value alive, never stores
-
-// DBG (timing builds of the removed tools/kbench.hip): 1 = no A refill, 2 = no stores
 // pw_ws_x3_kernel: the same weight-stationary GEMM for DT_F16X3 (fp32 in HBM, split-operand fp16 MFMAs).  A wave keeps the hi AND
 // lo f16x4 fragments of its units' weights in registers (the same register count as the fp32 fragments); every 16-byte piece of
 // the A ring is split into its fp16 halves once per row tile (ten VALU instructions that run beside the matrix pipe) and feeds
@@ -308,7 +305,7 @@ __global__ void __launch_bounds__(64 * RS * ((((N + 15) / 16) * (OMODE == 2 ? 4 
     }
 }
 
-template <int K1, int K2, int N, int UPW, int RS, bool RELU, int OMODE, int DBG = 0>
+template <int K1, int K2, int N, int UPW, int RS, bool RELU, int OMODE>
 __global__ void __launch_bounds__(64 * RS * ((((N + 15) / 16) * (OMODE == 2 ? 4 : 1) + UPW - 1) / UPW)) pw_ws_kernel(PwArgs a)
 {
     constexpr int NT = (N + 15) / 16, NQ = OMODE == 2 ? 4 : 1, NU = NT * NQ;
@@ -374,7 +371,7 @@ __global__ void __launch_bounds__(64 * RS * ((((N + 15) / 16) * (OMODE == 2 ? 4 
 #pragma unroll
                 for (int i = 0; i < UPW; ++i)
                     acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(bw[i][kb * 4 + j], ((const float*)&a1[kb])[j], acc[i], 0, 0, 0);
-            if constexpr (!(DBG & 1)) a1[kb] = *reinterpret_cast<const float4*>(p1 + kb * 16);
+            a1[kb] = *reinterpret_cast<const float4*>(p1 + kb * 16);
         }
         if constexpr (T1) {
 #pragma unroll
@@ -382,7 +379,7 @@ __global__ void __launch_bounds__(64 * RS * ((((N + 15) / 16) * (OMODE == 2 ? 4 
 #pragma unroll
                 for (int i = 0; i < UPW; ++i)
                     acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(bw[i][NB1 * 4 + j], ((const float*)&a1t)[j], acc[i], 0, 0, 0);
-            if constexpr (!(DBG & 1)) a1t = *reinterpret_cast<const float2*>(p1 - 4 * q + NB1 * 16 + 2 * q);
+            a1t = *reinterpret_cast<const float2*>(p1 - 4 * q + NB1 * 16 + 2 * q);
         }
         if constexpr (K2 > 0) {
             const float* p2 = rowptr2(tn);
@@ -393,7 +390,7 @@ __global__ void __launch_bounds__(64 * RS * ((((N + 15) / 16) * (OMODE == 2 ? 4 
 #pragma unroll
                     for (int i = 0; i < UPW; ++i)
                         acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(bw[i][S1 + kb * 4 + j], ((const float*)&a2[kb])[j], acc[i], 0, 0, 0);
-                if constexpr (!(DBG & 1)) a2[kb] = *reinterpret_cast<const float4*>(p2 + kb * 16);
+                a2[kb] = *reinterpret_cast<const float4*>(p2 + kb * 16);
             }
             if constexpr (T2) {
 #pragma unroll
@@ -423,7 +420,6 @@ __global__ void __launch_bounds__(64 * RS * ((((N + 15) / 16) * (OMODE == 2 ? 4 
             const long qoff = OMODE == 2 ? ((long)(uq[i] >> 1) * (2 * a.W) + (uq[i] & 1)) * N : 0;
             float4 v = make_float4(acc[i][0] + bias[i][0], acc[i][1] + bias[i][1], acc[i][2] + bias[i][2], acc[i][3] + bias[i][3]);
             if constexpr (RELU) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-            if ((DBG & 2) && v0guard(v.x)) continue;
             *reinterpret_cast<float4*>(a.out + obase + qoff + c) = v;
         }
     }
