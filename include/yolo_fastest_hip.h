@@ -348,6 +348,26 @@ int yf_augment_u8(int device, const uint8_t *d_src, int src_h, int src_w, int sr
 int yf_augment_warp_u8(int device, const uint8_t *d_src, int src_h, int src_w, int src_c, const int *d_index, int n_src, int N, const void *d_xtab,
                        const void *d_ytab, int dst_h, int dst_w, int dst_c, int gray_bits, const int *d_params, const double *d_warp,
                        uint8_t *d_scratch, uint8_t *d_u8, float *d_x, void *stream);
+/* yolov5's mixup over frames that are ALREADY resized (and gray): per output frame the first frame, warped or not, blended with a partner
+ * frame under the partner's own warp, then yf_augment_warp_u8's blur and flips on the mixture:
+ *     x = flipud?(fliplr?(GaussianBlur_k(mix(warp?(first), warp?(partner), r))))
+ *   d_frames  u8 [n_frames, h, w, c], c 1 or 3: what yf_augment_u8 with all-zero parameters writes to its u8 output (source sizes no longer
+ *             matter here, so a partner may come from another size group)
+ *   d_first   int32 [N]: the frame output n is made of (an entry outside 0 .. n_frames - 1 leaves output frame n untouched)
+ *   d_second  int32 [N]: the partner; negative = none (the frame does not pass through the blend: yf_augment_warp_u8's bytes);
+ *             an entry >= n_frames leaves output frame n untouched as well.  Nothing is read out of bounds.  The frame itself is allowed.
+ *   mix       yolov5's `(im * r + im2 * (1 - r)).astype(np.uint8)` per byte, in IEEE double with one rounding per operation (no FMA, no
+ *             rearrangement): trunc((double)a * r + (double)b * (1.0 - r)), clamped to 0 .. 255 before the conversion (no change for
+ *             0 <= r <= 1; a NaN gives 0).  Both samples are taken as yf_augment_warp_u8 takes them (Pillow's BILINEAR, fill 114).
+ *   d_params  int32 [N]: yf_augment_warp_u8's bits for the first frame and the mixture (k, 8 fliplr, 9 flipud, 10 warp, 11 perspective),
+ *             and bit 12 partner warped, bit 13 partner perspective
+ *   d_warp    float64 [N, 2, 8]: the coefficients of the first frame and of the partner (each read with its warp bit)
+ *   d_ratio   float64 [N]: r (read for frames with a partner)
+ *   outputs   as yf_augment_warp_u8's (at least one; may not overlap d_frames)
+ * Bad arguments are refused with YF_E_INVALID before the GPU is touched.  ONE launch on `stream`; the blur's reflect-101 border is taken
+ * on the mixture.  No allocation or synchronisation; stream-ordered; capturable. */
+int yf_augment_mix_u8(int device, const uint8_t *d_frames, int n_frames, int N, int h, int w, int c, const int *d_first, const int *d_second,
+                      const int *d_params, const double *d_warp, const double *d_ratio, uint8_t *d_u8, float *d_x, void *stream);
 /* cv::resize's INTER_LINEAR tables for one (source, destination) size pair into caller-owned device memory: d_xtab int4 [dst_w],
  * d_ytab int4 [dst_h] (16 bytes each entry).  One small kernel on `stream`, no allocation or synchronisation. */
 int yf_cv_resize_tables(int device, int src_h, int src_w, int dst_h, int dst_w, void *d_xtab, void *d_ytab, void *stream);

@@ -8,7 +8,12 @@
                                                       the kernel's own average duration from the stats file
     python tools/dataset_bench.py --train             train() iterations (DataLoader + train_step) at batch 16, examples/s, interleaved:
                                                       DetectDataset cache="device", decode="device", cache=None (decode="host"), the first
-                                                      two again with the geometric keys active, and tools/train_bench.py's no-data loop"""
+                                                      two again with the geometric keys active, and tools/train_bench.py's no-data loop
+    python tools/dataset_bench.py --kernel --mixup    the mix call (yf_augment_mix_u8 over resized frames: every frame has a partner, both
+                                                      warped with perspective draws) beside the warp call and the plain launch at batch 16
+                                                      and 512, in interleaved rounds: median and spread of each
+    python tools/dataset_bench.py --train --mixup     train() at batch 16, cache="device", geometric keys active: DetectDataset(mixup=True)
+                                                      with mixup 0.5 and 0.0 beside the flag-unset data set and the no-data loop"""
 import argparse
 import csv
 import glob
@@ -32,6 +37,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--kernel", action="store_true")
 ap.add_argument("--profile", action="store_true")
 ap.add_argument("--train", action="store_true")
+ap.add_argument("--mixup", action="store_true", help="the mixup variant of --kernel / --train")
 ap.add_argument("--reps", type=int, default=50)
 ap.add_argument("--steps", type=int, default=30)
 ap.add_argument("--rounds", type=int, default=3)
@@ -103,6 +109,76 @@ def kernel_bench():
     return res
 
 
+def kernel_bench_mixup():
+    """The plain launch, the warp call (two launches: resize + warp) and the mix call (one launch over the warp call's resized frames;
+    with the resize launch in front of it as well), `--rounds` interleaved rounds of `--reps` launches each."""
+    from yolo_fastest_amd.dataset import DetectDataset
+    lib = _lib.lib()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    res = {}
+    for N in (16, 512):
+        src = torch.randint(0, 256, (N, 512, 640, 3), dtype=torch.uint8, device=dev)
+        rng = random.Random(0)
+        prm = []
+        for _ in range(N):
+            k = (7 if rng.random() < 0.4 else 3) if rng.random() < 0.3 else 0
+            prm.append(k | (int(rng.random() < 0.5) << 8))
+        draw = DetectDataset.__new__(DetectDataset)                    # the draws alone: no files behind it
+        draw.input_shape = [256, 320, 1]
+        for key in ("degrees", "translate", "scale", "shear", "perspective"):
+            setattr(draw, key, GEOMETRIC[key])
+        random.seed(0)
+        coeffs = np.stack([draw._draw_warp()[2] for _ in range(2 * N)]).reshape(N, 2, 8)
+        ratios = [random.betavariate(32.0, 32.0) for _ in range(N)]
+        prm2 = [p | (int(rng.random() < GEOMETRIC["flipud"]) << 9) | (3 << 10) for p in prm]
+        d_prm = torch.tensor(prm, dtype=torch.int32, device=dev)
+        d_zero = torch.zeros((N,), dtype=torch.int32, device=dev)
+        d_prm2 = torch.tensor(prm2, dtype=torch.int32, device=dev)
+        d_prm3 = torch.tensor([p | (3 << 12) for p in prm2], dtype=torch.int32, device=dev)
+        d_warp = torch.tensor(coeffs[:, 0].copy(), dtype=torch.float64).to(dev)
+        d_warp2 = torch.tensor(coeffs, dtype=torch.float64).to(dev)
+        d_ratio = torch.tensor(ratios, dtype=torch.float64).to(dev)
+        d_first = torch.arange(N, dtype=torch.int32, device=dev)
+        d_second = torch.tensor([(n + 1) % N for n in range(N)], dtype=torch.int32, device=dev)
+        scratch = torch.empty((N, 256, 320, 1), dtype=torch.uint8, device=dev)
+        x = torch.empty((N, 1, 256, 320), dtype=torch.float32, device=dev)
+        head = (dev.index, src.data_ptr(), 512, 640, 3, None, N, N, None, None, 256, 320, 1, 15)
+
+        def plain():
+            _lib.check(lib.yf_augment_u8(*head, d_prm.data_ptr(), None, x.data_ptr(), stream))
+
+        def warp():
+            _lib.check(lib.yf_augment_warp_u8(*head, d_prm2.data_ptr(), d_warp.data_ptr(), scratch.data_ptr(), None, x.data_ptr(), stream))
+
+        def mix():
+            _lib.check(lib.yf_augment_mix_u8(dev.index, scratch.data_ptr(), N, N, 256, 320, 1, d_first.data_ptr(), d_second.data_ptr(),
+                                             d_prm3.data_ptr(), d_warp2.data_ptr(), d_ratio.data_ptr(), None, x.data_ptr(), stream))
+
+        def resize_mix():
+            _lib.check(lib.yf_augment_u8(*head, d_zero.data_ptr(), scratch.data_ptr(), None, stream))
+            mix()
+        calls = {"plain": plain, "warp": warp, "mix": mix, "resize+mix": resize_mix}
+        for fn in calls.values():                                      # warp first: it fills the scratch the mix call reads
+            for _ in range(5):
+                fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ms = {n: [] for n in calls}
+        for _ in range(a.rounds):
+            for n, fn in calls.items():
+                torch.cuda.synchronize()
+                e0.record()
+                for _ in range(a.reps):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                ms[n].append(e0.elapsed_time(e1) / a.reps)
+        res[N] = {n: {"median_ms": round(float(np.median(v)), 4), "rounds_ms": [round(x_, 4) for x_ in v]} for n, v in ms.items()}
+        for n, v in ms.items():
+            print("batch %d, %s: %.4f ms (median of %d rounds of %d launches: %s) = %.2f x the plain launch"
+                  % (N, n, float(np.median(v)), len(v), a.reps, ["%.4f" % x_ for x_ in v], np.median(v) / np.median(ms["plain"])))
+    return res
+
+
 def profile():
     out = a.out or tempfile.mkdtemp(prefix="dataset_bench_")
     os.makedirs(out, exist_ok=True)
@@ -149,6 +225,10 @@ def train_bench():
     if hasattr(DetectDataset, "draw_ex"):
         active = dict(aug, **GEOMETRIC)
         configs += [("geometric cache=device", active, dict(cache="device")), ("geometric decode=device", active, dict(decode="device"))]
+    if a.mixup:                                                          # one build: the flag unset, set with 0.0, set with 0.5
+        configs = [("cache=device", aug, dict(cache="device")), ("geometric cache=device", active, dict(cache="device")),
+                   ("geometric mixup=0.0 cache=device", dict(active, mixup=0.0), dict(cache="device", mixup=True)),
+                   ("geometric mixup=0.5 cache=device", dict(active, mixup=0.5), dict(cache="device", mixup=True))]
     for name, params, kw in configs:
         ds = DetectDataset(io["input_shape"], io["origin_img_shape"], None, aug_params=params, device=dev, **kw)
         loaders[name] = DataLoader(ds, batch_size=B, num_workers=0, drop_last=True, pin_memory=True, shuffle=True, collate_fn=val.collate_fn)
@@ -182,8 +262,12 @@ def train_bench():
     for n, v in res.items():
         print("train batch %d, %s: %.0f examples/s (median of %d rounds: %s)" % (B, n, float(np.median(v)), len(v), ["%.0f" % x for x in v]))
     print("cache=device / no-data = %.3f" % (np.median(res["cache=device"]) / np.median(res["no-data"])))
+    if a.mixup:
+        print("mixup 0.5 / mixup 0.0 = %.3f; mixup 0.0 / flag unset = %.3f" % (
+            np.median(res["geometric mixup=0.5 cache=device"]) / np.median(res["geometric mixup=0.0 cache=device"]),
+            np.median(res["geometric mixup=0.0 cache=device"]) / np.median(res["geometric cache=device"])))
     for n in ("cache=device", "decode=device"):
-        if "geometric " + n in res:
+        if "geometric " + n in res and n in res and "cache=None" in res:
             print("geometric %s / %s = %.3f, / cache=None (decode=host) = %.3f" % (
                 n, n, np.median(res["geometric " + n]) / np.median(res[n]), np.median(res["geometric " + n]) / np.median(res["cache=None"])))
     return {n: {"median": float(np.median(v)), "rounds": [round(float(x), 1) for x in v]} for n, v in res.items()}
@@ -192,6 +276,8 @@ def train_bench():
 out = {}
 if a.kernel and a.profile:
     profile()
+elif a.kernel and a.mixup:
+    out["kernel_mixup"] = kernel_bench_mixup()
 elif a.kernel:
     out["kernel"] = kernel_bench()
 if a.train:

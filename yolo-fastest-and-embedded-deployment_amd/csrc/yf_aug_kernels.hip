@@ -12,6 +12,8 @@
 //     modules/imgproc/src/smooth.simd.hpp): taps in 1/256 units k3 = [64 128 64], k5 = [16 64 96 64 16], k7 = [8 28 56 72 56 28 8]; the row
 //     pass is exact in uint16, dst = (sum_y k_y * row_y + 2^15) >> 16; BORDER_REFLECT_101 on all four sides; every channel on its own.
 //   flip: after the blur (the taps and reflect-101 are symmetric, so the two commute; tests/test_gpu_dataset.py shows it).
+// yf_augment_warp_u8 adds yolov5's geometric warp between the resize and the blur (warp_kernel, a second launch over the resized frames);
+// yf_augment_mix_u8 adds yolov5's mixup of two resized, warped frames before the blur (mix_kernel, one launch; see below).
 // One workgroup owns `tr` destination rows of one frame: it stages those rows plus a 3-row halo of the resized (gray) image in LDS (computed
 // straight from the source bytes, as cv_pre_kernel does), runs the row pass into a uint16 LDS buffer and the column pass out of it.  A frame
 // whose k is 0 stages no halo and skips both passes (k is uniform per workgroup).  Integer arithmetic only on the byte path.
@@ -291,6 +293,21 @@ __device__ __forceinline__ bool warp_sample(const uint8_t* __restrict__ img, int
     return true;
 }
 
+// One pixel of a resized frame as the blur sees it: the bilinear sample under the frame's coefficients (114 outside), or the frame's own
+// byte for a frame without the warp bit.
+template <int C>
+__device__ __forceinline__ void frame_px(const uint8_t* __restrict__ img, int dh, int dw, bool warped, const double (&m)[8], bool persp, int x,
+                                         int y, int (&v)[C])
+{
+    if (!warped) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) v[c] = img[((long)y * dw + x) * C + c];
+    } else if (!warp_sample<C>(img, dh, dw, m, persp, x, y, v)) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) v[c] = WARP_FILL;
+    }
+}
+
 // Built like aug_kernel: one workgroup owns `tr` destination rows of one frame and stages them plus the blur halo (reflect-101 on the
 // WARPED image) in LDS, each staged pixel a bilinear sample of the resized frame (or that frame's own pixel without bit 10: then the
 // bytes are yf_augment_u8's); the blur passes are aug_kernel's; both flips at the store.
@@ -332,13 +349,7 @@ __global__ void __launch_bounds__(256) warp_kernel(WarpArgs a)
             const int dx = dx0 + i;
             if (dx >= a.dw) break;
             int v[C];
-            if (!warped) {
-#pragma unroll
-                for (int c = 0; c < C; ++c) v[c] = img[((long)y * a.dw + dx) * C + c];
-            } else if (!warp_sample<C>(img, a.dh, a.dw, m, persp, dx, y, v)) {
-#pragma unroll
-                for (int c = 0; c < C; ++c) v[c] = WARP_FILL;
-            }
+            frame_px<C>(img, a.dh, a.dw, warped, m, persp, dx, y, v);
 #pragma unroll
             for (int c = 0; c < C; ++c) {
                 const int kk = i * C + c;
@@ -355,6 +366,116 @@ __global__ void __launch_bounds__(256) warp_kernel(WarpArgs a)
     blur_cols_store<C>(tile, hb, taps, k, n, dy0, rows, a.dh, a.dw, a.pitch, fliplr, flipud, a.u8, a.x);
 }
 
+// ---- mixup (yf_augment_mix_u8): one launch over frames that are already resized (and gray) ----
+struct MixArgs {
+    const uint8_t* frames;        // [n_frames, dh, dw, C] resized frames (aug_kernel without parameters)
+    int n_frames, n, dh, dw;
+    const int* first;             // [n] frame the output is made of; outside 0 .. n_frames - 1: the output frame is left untouched
+    const int* second;            // [n] the partner: negative = none; >= n_frames: the output frame is left untouched
+    const int* params;            // [n] WarpArgs' bits (the first frame and the mixture) | partner warped << 12 | partner perspective << 13
+    const double* warp;           // [n, 2, 8] coefficients of the first frame and of the partner (each read with its warp bit)
+    const double* ratio;          // [n] r: mix = trunc(first * r + partner * (1 - r)) (read for frames with a partner)
+    uint8_t* u8;
+    float* x;
+    int tr, pitch;
+};
+
+// yolov5's `(im * r + im2 * (1 - r)).astype(np.uint8)` for one byte pair: IEEE double, one rounding per operation (no FMA, no
+// rearrangement: with r = 0.4809054919537687, 127 mixed with 127 is 126).  q = 1.0 - r.  The clamp changes nothing for 0 <= r <= 1; it
+// keeps a caller's bad ratio or a NaN (-> 0) from wrapping in the conversion.
+__device__ __forceinline__ int mix_px(int a, int b, double r, double q)
+{
+#pragma clang fp contract(off)
+    const double t = (double)a * r + (double)b * q;
+    return t >= 0.0 ? (t <= 255.0 ? (int)t : 255) : 0;
+}
+
+// The staging of mix_kernel: 4 destination pixels (all channels) per task, each the first frame's pixel (frame_px) and, with PARTNER,
+// that blended with the partner's pixel under the partner's own coefficients.
+template <int C, bool PARTNER>
+__device__ __forceinline__ void mix_stage(const MixArgs& a, uint8_t* tile, const uint8_t* __restrict__ img, const uint8_t* __restrict__ img2,
+                                          int dy0, int halo, int T, bool warped, bool persp, const double (&m)[8], bool warped2, bool persp2,
+                                          const double (&m2)[8], double r, double q)
+{
+    const int quads = (a.dw + 3) >> 2;
+#pragma unroll 1
+    for (int t = threadIdx.x; t < T * quads; t += 256) {
+        const int row = t / quads, dx0 = (t - row * quads) * 4;
+        const int y = reflect101(dy0 - halo + row, a.dh);
+        uint32_t packed[C];
+#pragma unroll
+        for (int w = 0; w < C; ++w) packed[w] = 0u;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int dx = dx0 + i;
+            if (dx >= a.dw) break;
+            int v[C];
+            frame_px<C>(img, a.dh, a.dw, warped, m, persp, dx, y, v);
+            if constexpr (PARTNER) {
+                int u[C];
+                frame_px<C>(img2, a.dh, a.dw, warped2, m2, persp2, dx, y, u);
+#pragma unroll
+                for (int c = 0; c < C; ++c) v[c] = mix_px(v[c], u[c], r, q);
+            }
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                const int kk = i * C + c;
+                packed[kk >> 2] |= (uint32_t)(v[c] & 255) << (8 * (kk & 3));
+            }
+        }
+        uint32_t* const o = reinterpret_cast<uint32_t*>(tile + row * a.pitch + dx0 * C);
+#pragma unroll
+        for (int w = 0; w < C; ++w) o[w] = packed[w];
+    }
+}
+
+// Built like warp_kernel: one workgroup owns `tr` destination rows of one output frame and stages them plus the blur halo (reflect-101 on
+// the MIXTURE) in LDS; a frame without a partner is staged exactly as warp_kernel stages it (no blend); the blur passes and both flips
+// are the shared ones.  k, the flags, "has partner", r, 1 - r and the sixteen coefficients are uniform per workgroup.
+template <int C>
+__global__ void __launch_bounds__(256) mix_kernel(MixArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t aug_smem[];
+    const int groups = (a.dh + a.tr - 1) / a.tr;
+    const int n = blockIdx.x / groups, dy0 = (blockIdx.x - n * groups) * a.tr;
+    const int f = a.first[n], f2 = a.second[n];
+    if (f < 0 || f >= a.n_frames || f2 >= a.n_frames) return;  // nothing is read out of bounds; the output frame stays as it was
+    const bool partner = f2 >= 0;
+    const int p = a.params[n];
+    const int k = ((p & 15) == 3 || (p & 15) == 5 || (p & 15) == 7) ? (p & 15) : 0;
+    const bool fliplr = (p >> 8) & 1, flipud = (p >> 9) & 1, warped = (p >> 10) & 1, persp = (p >> 11) & 1;
+    const bool warped2 = partner && ((p >> 12) & 1), persp2 = (p >> 13) & 1;
+    const int* const taps = k ? aug_taps[(k - 3) >> 1] : aug_taps[0];
+    const int rows = min(a.tr, a.dh - dy0);
+    const int halo = k ? AUG_R : 0;
+    const int T = rows + 2 * halo;
+    const long frame = (long)a.dh * a.dw * C;
+    const uint8_t* const img = a.frames + f * frame;
+    uint8_t* const tile = aug_smem;                                                              // [T][pitch]
+    uint16_t* const hb = reinterpret_cast<uint16_t*>(aug_smem + (size_t)(a.tr + 2 * AUG_R) * a.pitch);   // [T][dw * C]
+    double m[8] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0}, m2[8] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0};
+    if (warped) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) m[i] = a.warp[(long)n * 16 + i];
+    }
+    if (warped2) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) m2[i] = a.warp[(long)n * 16 + 8 + i];
+    }
+
+    if (partner) {
+#pragma clang fp contract(off)
+        const double r = a.ratio[n], q = 1.0 - r;
+        mix_stage<C, true>(a, tile, img, a.frames + f2 * frame, dy0, halo, T, warped, persp, m, warped2, persp2, m2, r, q);
+    } else {
+        mix_stage<C, false>(a, tile, img, img, dy0, halo, T, warped, persp, m, false, false, m2, 0.0, 0.0);
+    }
+    __syncthreads();
+
+    blur_rows<C>(tile, hb, taps, k, T, a.dw, a.pitch);
+    blur_cols_store<C>(tile, hb, taps, k, n, dy0, rows, a.dh, a.dw, a.pitch, fliplr, flipud, a.u8, a.x);
+}
+
 template <int GRAY, int C>
 void launch_aug_mode(const AugArgs& a, size_t lds, hipStream_t s)
 {
@@ -362,6 +483,22 @@ void launch_aug_mode(const AugArgs& a, size_t lds, hipStream_t s)
     if (a.mode == 0) hipLaunchKernelGGL((aug_kernel<GRAY, 0, C>), dim3(grid), dim3(256), lds, s, a);
     else if (a.mode == 1) hipLaunchKernelGGL((aug_kernel<GRAY, 1, C>), dim3(grid), dim3(256), lds, s, a);
     else hipLaunchKernelGGL((aug_kernel<GRAY, 2, C>), dim3(grid), dim3(256), lds, s, a);
+}
+
+// The LDS geometry aug_kernel, warp_kernel and mix_kernel share: destination rows per workgroup, the u8 tile's row pitch and the LDS bytes of
+// a workgroup for N frames of dst_h x dst_w x dst_c.
+int aug_tile(const char* who, int N, int dst_h, int dst_w, int dst_c, int& tr_out, int& pitch, size_t& lds)
+{
+    const int quads = (dst_w + 3) >> 2;
+    pitch = (quads * 4 * dst_c + 15) & ~15;
+    const long per_row = (long)pitch + 2L * dst_w * dst_c;   // u8 tile row + uint16 row-pass row
+    const long tr = AUG_LDS / per_row - 2 * AUG_R;
+    if (tr < 1) return fail(YF_E_INVALID, "%s: rows of %d x %d bytes do not fit the LDS tile", who, dst_w, dst_c);
+    tr_out = tr < AUG_MAX_TR ? (int)tr : AUG_MAX_TR;
+    lds = (size_t)(tr_out + 2 * AUG_R) * per_row;
+    const long groups = (long)N * ((dst_h + tr_out - 1) / tr_out);
+    if (groups > 0x7fffffffL) return fail(YF_E_INVALID, "%s: batch too large for one launch", who);
+    return YF_OK;
 }
 
 // The arguments yf_augment_u8 and yf_augment_warp_u8 share, checked, into AugArgs (parameters left to the caller) + the LDS bytes of a
@@ -388,16 +525,7 @@ int aug_setup(const char* who, const uint8_t* d_src, int src_h, int src_w, int s
         if (!d_xtab || !d_ytab) return fail(YF_E_INVALID, "%s: a %dx%d -> %dx%d resize needs the tables of yf_cv_resize_tables", who, src_h, src_w, dst_h, dst_w);
         a.xtab = static_cast<const int4*>(d_xtab); a.ytab = static_cast<const int4*>(d_ytab);
     }
-    const int quads = (dst_w + 3) >> 2;
-    a.pitch = (quads * 4 * dst_c + 15) & ~15;
-    const long per_row = (long)a.pitch + 2L * dst_w * dst_c;   // u8 tile row + uint16 row-pass row
-    const long tr = AUG_LDS / per_row - 2 * AUG_R;
-    if (tr < 1) return fail(YF_E_INVALID, "%s: rows of %d x %d bytes do not fit the LDS tile", who, dst_w, dst_c);
-    a.tr = tr < AUG_MAX_TR ? (int)tr : AUG_MAX_TR;
-    lds = (size_t)(a.tr + 2 * AUG_R) * per_row;
-    const long groups = (long)N * ((dst_h + a.tr - 1) / a.tr);
-    if (groups > 0x7fffffffL) return fail(YF_E_INVALID, "%s: batch too large for one launch", who);
-    return YF_OK;
+    return aug_tile(who, N, dst_h, dst_w, dst_c, a.tr, a.pitch, lds);
 }
 
 void launch_aug(const AugArgs& a, size_t lds, hipStream_t s)
@@ -459,6 +587,27 @@ int yf_augment_warp_u8(int device, const uint8_t* d_src, int src_h, int src_w, i
     const unsigned grid = (unsigned)((long)N * ((dst_h + a.tr - 1) / a.tr));
     if (dst_c == 1) hipLaunchKernelGGL((warp_kernel<1>), dim3(grid), dim3(256), lds, s, w);
     else hipLaunchKernelGGL((warp_kernel<3>), dim3(grid), dim3(256), lds, s, w);
+    HIP_OK(hipGetLastError());
+    return YF_OK;
+}
+
+int yf_augment_mix_u8(int device, const uint8_t* d_frames, int n_frames, int N, int h, int w, int c, const int* d_first, const int* d_second,
+                      const int* d_params, const double* d_warp, const double* d_ratio, uint8_t* d_u8, float* d_x, void* stream)
+{
+    if (!d_frames || !d_first || !d_second || !d_params || !d_warp || !d_ratio || (!d_u8 && !d_x) || N <= 0 || n_frames <= 0)
+        return fail(YF_E_INVALID, "yf_augment_mix_u8: null pointer, no output, N <= 0 or n_frames <= 0");
+    if (h <= 0 || w <= 0 || h > 16384 || w > 16384) return fail(YF_E_INVALID, "yf_augment_mix_u8: frames of %dx%d", h, w);
+    if (c != 1 && c != 3) return fail(YF_E_INVALID, "yf_augment_mix_u8: %d-channel frames (1 or 3)", c);
+    MixArgs m{};
+    size_t lds;
+    const int rc = aug_tile("yf_augment_mix_u8", N, h, w, c, m.tr, m.pitch, lds);
+    if (rc != YF_OK) return rc;
+    m.frames = d_frames; m.n_frames = n_frames; m.n = N; m.dh = h; m.dw = w; m.first = d_first; m.second = d_second; m.params = d_params;
+    m.warp = d_warp; m.ratio = d_ratio; m.u8 = d_u8; m.x = d_x;
+    HIP_OK(hipSetDevice(device));
+    const unsigned grid = (unsigned)((long)N * ((h + m.tr - 1) / m.tr));
+    if (c == 1) hipLaunchKernelGGL((mix_kernel<1>), dim3(grid), dim3(256), lds, (hipStream_t)stream, m);
+    else hipLaunchKernelGGL((mix_kernel<3>), dim3(grid), dim3(256), lds, (hipStream_t)stream, m);
     HIP_OK(hipGetLastError());
     return YF_OK;
 }

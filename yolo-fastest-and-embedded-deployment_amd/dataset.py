@@ -19,7 +19,17 @@ Beyond the reference: the geometric keys of `augment_params` -- `degrees`, `tran
 the reference reads nowhere, are honoured as yolov5's random_perspective (draw_ex, _draw_warp, _warp_labels): the warp runs on the device
 between the resize and the blur (`yf_augment_warp_u8`; pixels pinned to Pillow's Image.transform with BILINEAR and fill 114; OpenCV parity
 not claimed), the vertical flip after the horizontal one.  At their neutral values (the reference's _config.py: 0, 0, 1.0, 0, 0, 0) or
-absent, draws, labels, launch and bytes are the reference's.  `mixup` stays ignored.
+absent, draws, labels, launch and bytes are the reference's.
+
+`mixup`, the last key, is OPT-IN: the reference ignores it, so a DetectDataset built without `mixup=True` does not read the key at all (a
+config copied from yolov5 with `mixup: 0.9` changes nothing).  With `mixup=True` and augment_params["mixup"] = p > 0 it is yolov5's mixup
+(draw_mix): with probability p an item is blended with a partner item `j = random.randint(0, len - 1)` (which may be the item itself) under
+`r = random.betavariate(32.0, 32.0)` -- yolov5's np.random.beta(32, 32), taken from `random` instead of numpy's generator so that
+random.seed alone still reproduces an epoch.  Each of the two frames is grayed, resized and warped on its own (the partner under eight
+draws of its own), the bytes are blended as `(im * r + im2 * (1 - r)).astype(np.uint8)` (IEEE double, one rounding per operation), and the
+blur and the flips act on the mixture; the partner's label rows (normalised and warped as its own) follow the item's, before the flips and
+the max_boxes fill.  On the device a batch with at least one hit is one resize launch per source size into a u8 scratch and ONE
+`yf_augment_mix_u8` launch; a batch without a hit goes through the calls above.
 
 Deviation: the reference cannot return an image without objects -- `np.array([])` is 1-D, so a flip raises IndexError (`labels[:, 1]`,
 :143) and otherwise the box copy raises ValueError (:159); here such an image is blurred / flipped as drawn and gets all-zero boxes (the
@@ -66,7 +76,7 @@ class DetectBatch:
 
 class DetectDataset(torch.utils.data.Dataset):
     def __init__(self, input_shape, origin_img_shape, logger, augment=True, aug_params=None, max_boxes=64, val=False, device=None,
-                 gray_bits=15, cache=None, class_names=None, decode="host", progressive=False):
+                 gray_bits=15, cache=None, class_names=None, decode="host", progressive=False, mixup=False):
         if aug_params is None:
             aug_params = config_params["augment_params"]
         self.aug_params = aug_params
@@ -92,7 +102,7 @@ class DetectDataset(torch.utils.data.Dataset):
             self.dataset_dir = aug_params["train_dataset_dir"]
         self.fliplr = aug_params["fliplr"]
         self.gussian_filter = aug_params["gussian_filter"]
-        # yolov5's geometric keys (absent = the reference's _config.py value = neutral); `mixup` stays ignored
+        # yolov5's geometric keys (absent = the reference's _config.py value = neutral); `mixup` is read with mixup=True only (below)
         self.degrees = float(aug_params.get("degrees", 0.0))
         self.translate = float(aug_params.get("translate", 0.0))
         self.scale = float(aug_params.get("scale", 1.0))
@@ -108,6 +118,11 @@ class DetectDataset(torch.utils.data.Dataset):
             raise ValueError("augment_params['translate'] must lie inside [0, 1)")
         self.geometric = bool(augment) and (self.degrees != 0.0 or self.translate != 0.0 or self.scale != 1.0 or self.shear != 0.0
                                             or self.perspective != 0.0)
+        self.mixup = 0.0                                    # the probability in use: 0.0 unless opted in (the key is not read then)
+        if mixup:
+            self.mixup = float(aug_params.get("mixup", 0.0))
+            if not 0.0 <= self.mixup <= 1.0:
+                raise ValueError("augment_params['mixup'] must lie inside [0, 1]: it is a probability")
         self.max_boxes = max_boxes
         self.augment = augment
         self.gray_bits = gray_bits
@@ -213,19 +228,52 @@ class DetectDataset(torch.utils.data.Dataset):
     def draw_ex(self, index):
         """draw() with the geometric part: -> (k, flip, boxes, flipud, coeffs), coeffs the eight float64 output -> input coefficients of
         the item's warp, or None while the geometric keys are neutral.  Draws: [eight for the warp, when any of degrees / translate /
-        scale / shear / perspective is set], blur?, which blur, fliplr?, [flipud?, when flipud > 0].  Labels: the reference's
-        normalisation, the warp (boxes it drops are compacted out before the max_boxes fill), x = 1 - x for fliplr, y = 1 - y for flipud."""
+        scale / shear / perspective is set], [the mixup draws, see draw_mix], blur?, which blur, fliplr?, [flipud?, when flipud > 0].
+        Labels: the reference's normalisation, the warp (boxes it drops are compacted out before the max_boxes fill), [the partner's rows],
+        x = 1 - x for fliplr, y = 1 - y for flipud.  draw_mix returns the mixup draws as well."""
+        return self.draw_mix(index)[:5]
+
+    def _labels(self, index):
+        """The reference's normalised (cls, xc, yc, w, h) rows of one item, by the configured origin_img_shape (:126-131)."""
         labels = np.array(self.dataset_dict[self.img_list[index]])
         if len(labels):
             labels[:, 1:5] = xyxy2xywh(labels[:, 1:5])
             labels[:, [2, 4]] /= self.origin_img_shape[0]
             labels[:, [1, 3]] /= self.origin_img_shape[1]
+        return labels
+
+    def draw_mix(self, index):
+        """The whole record of one item: -> (k, flip, boxes, flipud, coeffs, partner, partner_coeffs, r); the last three are None unless
+        mixup is active (mixup=True, augment, augment_params["mixup"] = p > 0) and the item was hit.  The draws, all from the global
+        `random` module, in order:
+          1. the item's eight warp draws (_draw_warp), when the geometric keys are active;
+          2. random.random() < p, when mixup is active; on a hit:
+          3.   partner = random.randint(0, len(self) - 1) -- it may be the item itself;
+          4.   the partner's own eight warp draws (_draw_warp, with its redraw rule), when geometric;
+          5.   r = random.betavariate(32.0, 32.0): yolov5 draws np.random.beta(32.0, 32.0) from numpy's generator; here the value comes
+               from `random`, so that random.seed alone reproduces an epoch;
+          6. as without mixup: blur?, which blur, fliplr?, [flipud?].
+        The partner gets no blur or flip draws: those act on the mixture.  Labels: the partner's rows (the reference's normalisation, then
+        the partner's own warp) are appended AFTER the item's; both flips act on all rows; the max_boxes fill runs last, so truncation
+        drops partner rows first; an image without objects contributes no rows, on either side."""
+        labels = self._labels(index)
         k, flip, flipud, coeffs = 0, False, False, None
+        partner = partner_coeffs = r = None
         if self.augment:
             if self.geometric:
                 M, gain, coeffs = self._draw_warp()
                 if len(labels):
                     labels = self._warp_labels(labels, M, gain)
+            if self.mixup > 0 and random.random() < self.mixup:
+                partner = random.randint(0, len(self) - 1)
+                other = self._labels(partner)
+                if self.geometric:
+                    M, gain, partner_coeffs = self._draw_warp()
+                    if len(other):
+                        other = self._warp_labels(other, M, gain)
+                r = random.betavariate(32.0, 32.0)
+                if len(other):
+                    labels = np.concatenate([labels, other]) if len(labels) else other
             if random.random() < self.gussian_filter:
                 _ret = random.random()
                 k = 7 if _ret < 0.4 else 3          # the reference's `elif _ret < 0.2` (5 x 5) cannot be reached
@@ -247,7 +295,7 @@ class DetectDataset(torch.utils.data.Dataset):
         if m:                                       # deviation: the reference's copy raises ValueError for no objects
             out[:m, 0:5] = labels[:m]
             out[:m, 5] = 255.0
-        return k, flip, out, flipud, coeffs
+        return k, flip, out, flipud, coeffs, partner, partner_coeffs, r
 
     # ---- images (GPU) ----
     def _need_gpu(self):
@@ -345,9 +393,50 @@ class DetectDataset(torch.utils.data.Dataset):
             _lib.check(_lib.lib().yf_cv_resize_tables(self.device.index, hw[0], hw[1], H, W, t.data_ptr(), t.data_ptr() + W * 16, stream))
         return t.data_ptr(), t.data_ptr() + W * 16
 
+    def _groups(self, indices):
+        """Where the frames `indices` are, by the configured cache / decode."""
+        if self.cache == "device":
+            return self._from_cache(indices)
+        if self.decode == "device":
+            return self._from_device_decode(indices)
+        return self._from_host_decode(indices)
+
+    def _mix_images(self, indices, packed, warps, mixes, out, out_u8, stream):
+        """A batch with at least one mixup hit: every distinct frame of items and partners resized once (yf_augment_u8 with zero
+        parameters, one launch per source size, each into its slice of one u8 scratch), then one yf_augment_mix_u8 into `out`."""
+        H, W, C = self.input_shape
+        dev, lib = self.device, _lib.lib()
+        distinct = list(dict.fromkeys(list(indices) + [m[0] for m in mixes if m is not None]))
+        scratch = torch.empty((len(distinct), H, W, C), dtype=torch.uint8, device=dev)
+        where, base = {}, 0                                  # item -> its frame in the scratch
+        for stack, slots, pos in self._groups(distinct):
+            hw = tuple(stack.shape[1:3])
+            index = None if slots is None else torch.tensor(slots, dtype=torch.int32).to(dev)
+            zero = torch.zeros((len(pos),), dtype=torch.int32, device=dev)
+            xt, yt = self._resize_tables(hw, stream)
+            _lib.check(lib.yf_augment_u8(dev.index, stack.data_ptr(), hw[0], hw[1], 3, None if index is None else index.data_ptr(),
+                                         stack.shape[0], len(pos), xt, yt, H, W, C, self.gray_bits, zero.data_ptr(),
+                                         scratch[base:base + len(pos)].data_ptr(), None, ctypes.c_void_p(stream)))
+            for j, p in enumerate(pos):
+                where[distinct[p]] = base + j
+            base += len(pos)
+        neutral = [1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0]
+        first = torch.tensor([where[i] for i in indices], dtype=torch.int32).to(dev)
+        second = torch.tensor([-1 if m is None else where[m[0]] for m in mixes], dtype=torch.int32).to(dev)
+        prm = torch.tensor(packed, dtype=torch.int32).to(dev)
+        warp = torch.tensor([[neutral if w is None else [float(v) for v in w],
+                              neutral if m is None or m[1] is None else [float(v) for v in m[1]]] for w, m in zip(warps, mixes)],
+                            dtype=torch.float64).to(dev)
+        ratio = torch.tensor([1.0 if m is None else m[2] for m in mixes], dtype=torch.float64).to(dev)
+        _lib.check(lib.yf_augment_mix_u8(dev.index, scratch.data_ptr(), len(distinct), len(indices), H, W, C, first.data_ptr(), second.data_ptr(),
+                                         prm.data_ptr(), warp.data_ptr(), ratio.data_ptr(), out.data_ptr() if out_u8 else None,
+                                         None if out_u8 else out.data_ptr(), ctypes.c_void_p(stream)))
+
     def augment_images(self, indices, params, out_u8=False):
-        """The frames `indices` with per-frame `params` -- (k, flip) or (k, flip, flipud, coeffs), draw_ex's values -- through
-        yf_augment_u8, one launch per source size; a size group with a warped or flipud frame goes through yf_augment_warp_u8 (two).
+        """The frames `indices` with per-frame `params` -- (k, flip), (k, flip, flipud, coeffs), draw_ex's values, or those extended by
+        draw_mix's (partner, partner_coeffs, r) -- through yf_augment_u8, one launch per source size; a size group with a warped or
+        flipud frame goes through yf_augment_warp_u8 (two).  With at least one partner: the distinct frames of items and partners resized
+        by yf_augment_u8 (one launch per source size) into one u8 scratch, then ONE yf_augment_mix_u8 for the whole batch.
         -> float32 device [N, C, H, W] ((v - 128) / 255), or uint8 device [N, H, W, C] with out_u8."""
         self._need_gpu()
         H, W, C = self.input_shape
@@ -355,19 +444,19 @@ class DetectDataset(torch.utils.data.Dataset):
         dev = self.device
         stream = torch.cuda.current_stream(dev).cuda_stream
         out = torch.empty((N, H, W, C) if out_u8 else (N, C, H, W), dtype=torch.uint8 if out_u8 else torch.float32, device=dev)
-        packed, warps = [], []
+        packed, warps, mixes = [], [], []
         for k, f, *rest in params:
-            ud, coeffs = rest if rest else (False, None)
+            ud, coeffs, partner, pcoeffs, r = (tuple(rest) + (None, None, None))[:5] if rest else (False, None, None, None, None)
             warps.append(coeffs)
+            mixes.append(None if partner is None else (int(partner), pcoeffs, float(r)))
             packed.append(int(k) | (int(bool(f)) << 8) | (int(bool(ud)) << 9) |
-                          (0 if coeffs is None else (1 << 10) | (int(coeffs[6] != 0 or coeffs[7] != 0) << 11)))
-        if self.cache == "device":
-            groups = self._from_cache(indices)
-        elif self.decode == "device":
-            groups = self._from_device_decode(indices)
-        else:
-            groups = self._from_host_decode(indices)
+                          (0 if coeffs is None else (1 << 10) | (int(coeffs[6] != 0 or coeffs[7] != 0) << 11)) |
+                          (0 if partner is None or pcoeffs is None else (1 << 12) | (int(pcoeffs[6] != 0 or pcoeffs[7] != 0) << 13)))
         lib = _lib.lib()
+        if any(m is not None for m in mixes):
+            self._mix_images(indices, packed, warps, mixes, out, out_u8, stream)
+            return out
+        groups = self._groups(indices)
         for stack, slots, pos in groups:
             hw = tuple(stack.shape[1:3])
             index = None if slots is None else torch.tensor(slots, dtype=torch.int32).to(dev)
@@ -392,8 +481,8 @@ class DetectDataset(torch.utils.data.Dataset):
     def __getitem__(self, index):
         """The reference's item: (float64 [H, W, C] image u8 - 128.0, float64 [max_boxes, 6] boxes)."""
         self._need_gpu()
-        k, flip, boxes, flipud, coeffs = self.draw_ex(index)
-        u8 = self.augment_images([index], [(k, flip, flipud, coeffs)], out_u8=True)[0].cpu().numpy()
+        k, flip, boxes, flipud, coeffs, partner, partner_coeffs, r = self.draw_mix(index)
+        u8 = self.augment_images([index], [(k, flip, flipud, coeffs, partner, partner_coeffs, r)], out_u8=True)[0].cpu().numpy()
         img = u8 - 128.0
         return np.ascontiguousarray(img), boxes
 
@@ -402,8 +491,8 @@ class DetectDataset(torch.utils.data.Dataset):
         -> DetectBatch(float32 device [N, C, H, W], float64 host [N, max_boxes, 6]); collate_fn passes it through."""
         self._need_gpu()
         indices = [int(i) for i in indices]
-        draws = [self.draw_ex(i) for i in indices]
-        imgs = self.augment_images(indices, [(k, f, ud, coeffs) for k, f, _, ud, coeffs in draws])
+        draws = [self.draw_mix(i) for i in indices]
+        imgs = self.augment_images(indices, [(k, f, ud, coeffs) + tuple(mix) for k, f, _, ud, coeffs, *mix in draws])
         targets = torch.from_numpy(np.stack([d[2] for d in draws])) if draws else torch.zeros((0, self.max_boxes, 6), dtype=torch.float64)
         return DetectBatch(imgs, targets)
 
