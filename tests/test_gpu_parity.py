@@ -1009,24 +1009,9 @@ def test_random_weights_against_oracle(yf, dev, seed):
     identity, negative biases) through every kernel of the fused plan, fp32 and fp16 storage, against the oracle evaluated in
     fp32 and fp64 (same accuracy-class bound as for the shipped weights)."""
     from oracle import backbone_oracle as bo
-    from yolo_fastest_amd import packer
+    from tests.random_weights import random_state_dict
     io = yf.io_params_for(256)
-    g = torch.Generator().manual_seed(seed)
-    sd = {}
-    for name, kind, cin, cout, k, stride, relu in packer.layer_table(24, 1):
-        if kind == packer.KIND_HEAD:
-            sd[name + ".weight"] = torch.randn((cout, cin, 1, 1), generator=g) * (1.0 / cin) ** 0.5
-            sd[name + ".bias"] = torch.randn((cout,), generator=g) * 0.5
-            continue
-        shape = {packer.KIND_PW: (cout, cin, 1, 1), packer.KIND_DENSE: (cout, cin, k, k), packer.KIND_DW: (cout, 1, k, k),
-                 packer.KIND_DECONV: (cin, cout, 2, 2)}[kind]
-        fan = cin * (k * k if kind == packer.KIND_DENSE else 1) if kind != packer.KIND_DW else k * k
-        sd[name + ".0.weight"] = torch.randn(shape, generator=g) * (1.0 / fan) ** 0.5   # keeps the 86-layer chain in range
-        sd[name + ".1.weight"] = 0.5 + torch.rand((cout,), generator=g)
-        sd[name + ".1.bias"] = torch.randn((cout,), generator=g) * 0.2
-        sd[name + ".1.running_mean"] = torch.randn((cout,), generator=g) * 0.2
-        sd[name + ".1.running_var"] = 0.5 + torch.rand((cout,), generator=g)
-        sd[name + ".1.num_batches_tracked"] = torch.zeros((), dtype=torch.int64)
+    sd = random_state_dict(seed)
     m = yf.YoloFastest(io).to(dev).eval()
     m.load_state_dict(sd)
     u8 = np.random.default_rng(seed).integers(0, 256, size=(3, 256, 320), dtype=np.uint8)

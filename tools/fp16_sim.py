@@ -7,7 +7,9 @@ Folded-BN forward in fp32 (torch CPU) with optional fp16 rounding of
   T  the tensors that live in HBM between launches of the fused plan (the narrow residual trunk + head-branch tensors),
   A  the activation operand of every pointwise MFMA (block input as the expansion's operand, depthwise result as the
      projection's operand),
-  E  the expanded tensor kept in LDS between expansion and depthwise.
+  E  the expanded tensor a kernel rounds on chip: conv1_8's result inside k19h_kernel (the MFMA block kernels keep E in LDS as float).
+The plan decides where a tensor is stored, hence T-rounded: the figures are for the default fusion level 2 at the checkpoint's size
+(res 256: res4 / res5 run as chained launches, the small head as one launch; see oracle/fp16_rounding_sim.py).
 Compared with the reference's fp32 head logits in tests/golden/golden_<res>.npz.
 """
 import os, sys
@@ -31,7 +33,7 @@ def main():
     for label, kw in (("fp32 folded", {}), ("W", dict(W=True)), ("T", dict(T=True)), ("A", dict(A=True)), ("E", dict(E=True)),
                       ("W+A+E (trunk fp32)", dict(W=True, A=True, E=True)), ("W+T+A+E (round 1)", dict(W=True, T=True, A=True, E=True)),
                       ("T+A+E", dict(T=True, A=True, E=True)), ("A+E", dict(A=True, E=True))):
-        out = Sim(fw, **kw).forward(x)
+        out = Sim(fw, size=x.shape[2:], fusion=2, **kw).forward(x)
         s = []
         for o, r in zip(out, ref):
             d = np.abs(o.numpy() - r)
