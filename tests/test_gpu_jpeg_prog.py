@@ -344,8 +344,13 @@ def test_dataset_progressive_device_decode_equals_host_decode(tmp_path, dev, cac
             random.seed(100 + i)
             ib, bb = devd[i]
             assert np.array_equal(ia, ib) and np.array_equal(ba, bb)
+    # four items of which at least one IS a progressive file: the list's order is os.listdir's (the file system's), so the first four alone
+    # can all be baseline files (11 of the 23 are), and then nothing is refused
+    from PIL import Image
+    prog = [i for i, p in enumerate(host.img_list) if Image.open(p).info.get("progressive")]
+    assert 0 < len(prog) < len(host.img_list)
     with pytest.raises(ValueError, match=r"progressive JPEG \(SOF2\) is not supported"):
-        ds(decode="device").__getitems__(list(range(4)))
+        ds(decode="device").__getitems__([prog[0]] + [i for i in range(4) if i != prog[0]][:3])
 
 
 def test_batch_detect_on_a_directory_that_mixes_kinds(dev, tmp_path):
