@@ -12,7 +12,7 @@ Folded-BN forward in fp32 (torch CPU) with optional fp16 rounding of
      inside k19h_kernel (ReLU + RNE = the fp16 operand of conv1_9's MFMAs).  The MFMA block kernels (mres_kernel / mres_pc_kernel) keep
      E in LDS as float: their depthwise reads the un-rounded expansion, also conv4_3 (conv4_2 is rounded only on its way to HBM).
 
-T depends on the plan, because a tensor is rounded where it is STORED (tests/f16_replay.py lists every launch's rounding points with the
+T depends on the plan, because a tensor is rounded where it is STORED (tests/replay.py lists every launch's rounding points with the
 kernel line of each; tests/test_cpu_f16_replay.py holds this class bitwise to that launch-by-launch model):
   size=(H, W)  frames whose stride-16 / stride-32 maps fit one tile (16x20 / 8x10: mres_can_chain) run res4_1..4 / res5_1..5 as ONE launch
                each; a block's result stays in LDS as float, the next expansion rounds its operand (A), the residual adds the un-rounded
