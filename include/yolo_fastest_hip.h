@@ -169,9 +169,16 @@ int yf_val_match(int device, const float *d_det, const int32_t *d_counts, int N,
  *   yf_train_head_loss: 3, 3; yf_train_head_loss_ex: as given -- yolo_loss.py:28-33); d_targets float32 [N,T,6] =
  *   (x, y, w, h normalised to 0..1, class, marker >= 1; the first row with marker < 1 ends an image's list, yolo_loss.py:158);
  *   ignore_thres = config train_params.IOU_loss_thre.
- *   d_losses float32 [8] = total, x, y, w, h, conf, cls (the 7-tuple of yolo_loss.py:94-95) and, in [7], the number of targets whose
- *   cell lies outside the feature map (the reference raises IndexError for those; they are skipped here).
- *   d_work: yf_train_loss_workspace_bytes(N, fh, fw) bytes of device scratch, 8-byte aligned. */
+ *   d_losses float32 [8] = total, x, y, w, h, conf, cls (the 7-tuple of yolo_loss.py:94-95) and, in [7], the number of targets the
+ *   reference cannot index: the cell (int(x * fw), int(y * fh)) lies outside the feature map, or the class int(class) lies outside
+ *   0 .. C-1 (yolo_loss.py:195).  The reference raises IndexError for those; here such a target is skipped whole (no mask, no box, no
+ *   class, no ignore mark), counted, and the caller decides (validation.YOLOLossV3 raises IndexError).  One departure: a NEGATIVE
+ *   column, row or class index wraps round in the reference (Python indexing); that is not reproduced, it is counted like the rest.
+ *   d_work: yf_train_loss_workspace_bytes(N, fh, fw) bytes of device scratch, 8-byte aligned.  Its layout is fixed (the tests read
+ *   the target planes back): double[16] -- [0..6] the sums of the x, y, w, h, conf-object, conf-no-object and class terms over the
+ *   cells, [7] the number of positive cells, [8] the count reported in d_losses[7], the rest zero -- then, with E = N*A*fh*fw cells in
+ *   d_head's (n, anchor, row, column) order, float32 [6 + C][E]: the planes mask, noobj_mask, tx, ty, tw, th, class 0 .. C-1 of
+ *   get_target (yolo_loss.py:144-196); up to 64 bytes behind them are reserved and not written. */
 int yf_train_loss_workspace_bytes(yf_handle h, int N, int fh, int fw, size_t *out);
 int yf_train_loss(yf_handle h, const float *d_head, int N, int fh, int fw, const double *anchors, const float *d_targets, int T,
                   double ignore_thres, void *d_work, size_t work_bytes, float *d_losses, float *d_grad_head, void *stream);

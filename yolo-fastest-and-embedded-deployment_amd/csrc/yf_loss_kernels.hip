@@ -29,8 +29,9 @@ __global__ void loss_init_kernel(float* __restrict__ dense, long E, int planes, 
 }
 
 // yolo_loss.py:156-194 for image n.  anc: the three (w, h) anchors in feature-map units as float32 (torch turns the Python-double
-// scaled anchors into float32 for both the IoU and the division).  acc[8] counts targets whose cell is outside the map (the
-// reference raises IndexError there).
+// scaled anchors into float32 for both the IoU and the division).  acc[8] counts the targets the reference cannot index: a cell
+// outside the map, or a class outside 0 .. nc-1 (:195 raises IndexError).  Such a target is skipped whole.  (A NEGATIVE index wraps
+// round in the reference; that is not reproduced: it is counted like any other index outside the range.)
 __global__ void loss_targets_kernel(const float* __restrict__ targets, int T, float* __restrict__ dense, long E, int N, int fh, int fw,
                                     LossAnchors anc, int na, int nc, float ignore_thres, double* __restrict__ acc)
 {
@@ -44,7 +45,8 @@ __global__ void loss_targets_kernel(const float* __restrict__ targets, int T, fl
         const float gx = g[0] * (float)fw, gy = g[1] * (float)fh, gw = g[2] * (float)fw, gh = g[3] * (float)fh;   // :161-164
         if (gw <= 0.f || gh <= 0.f) continue;                          // :166
         const int gi = (int)gx, gj = (int)gy;                          // :170-171 int() truncates
-        if (gi < 0 || gi >= fw || gj < 0 || gj >= fh) { atomicAdd(&acc[8], 1.0); continue; }
+        const int c = (int)g[4];                                       // :195 int() truncates
+        if (gi < 0 || gi >= fw || gj < 0 || gj >= fh || c < 0 || c >= nc) { atomicAdd(&acc[8], 1.0); continue; }
         float iou[LOSS_MAX_ANCHORS];
         int best = 0;
         for (int a = 0; a < na; ++a) {                                 // bbox_iou([0,0,gw,gh], [0,0,aw,ah]), +1 convention (general.py:29-52)
@@ -63,8 +65,7 @@ __global__ void loss_targets_kernel(const float* __restrict__ targets, int T, fl
         dense[LT_TY * E + e] = gy - (float)gj;
         dense[LT_TW * E + e] = (float)log((double)(gw / aw[best] + 1e-16f));   // :190-191 math.log of the float32 quotient, in double
         dense[LT_TH * E + e] = (float)log((double)(gh / ah[best] + 1e-16f));
-        const int c = (int)g[4];
-        if (c >= 0 && c < nc) dense[(LT_C0 + c) * E + e] = 1.f;         // :195 one-hot (accumulates over targets sharing the cell)
+        dense[(LT_C0 + c) * E + e] = 1.f;                              // :195 one-hot (accumulates over targets sharing the cell)
     }
 }
 
@@ -133,7 +134,7 @@ __global__ void __launch_bounds__(256) loss_cells_kernel(const float* __restrict
     }
 }
 
-// losses[0..6] = total, x, y, w, h, conf, cls (float32, combined like yolo_loss.py:90-92); losses[7] = targets outside the map
+// losses[0..6] = total, x, y, w, h, conf, cls (float32, combined like yolo_loss.py:90-92); losses[7] = targets skipped: cell outside the map or class outside 0 .. nc-1
 __global__ void loss_final_kernel(const double* __restrict__ acc, long E, int nc, float* __restrict__ losses)
 {
     const float lx = (float)(acc[0] / (double)E), ly = (float)(acc[1] / (double)E), lw = (float)(acc[2] / (double)E), lh = (float)(acc[3] / (double)E);

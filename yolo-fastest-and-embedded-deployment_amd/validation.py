@@ -103,7 +103,8 @@ class _TrainLossFn(torch.autograd.Function):
 
 def _train_loss(self, input, targets):
     """yolo_loss.py:70-97 with targets: (loss, x, y, w, h, conf, cls) -- loss a 0-dim tensor whose backward() fills input.grad, the rest
-    Python floats like the reference's .item() values.  Targets outside the feature map raise IndexError like the reference's indexing."""
+    Python floats like the reference's .item() values.  A target whose cell lies outside the feature map or whose class lies outside
+    0 .. num_classes-1 raises IndexError like the reference's indexing (a negative index wraps round there; here it raises too)."""
     if input.dim() != 4 or input.shape[1] != self.num_anchors * self.bbox_attrs:
         raise RuntimeError("input must be [batch, %d x (5 + %d), h, w]" % (self.num_anchors, self.num_classes))   # yolo_loss.py:58's view
     if not input.is_cuda:
@@ -115,7 +116,8 @@ def _train_loss(self, input, targets):
     loss, parts = _TrainLossFn.apply(x, t, self)
     v = parts.tolist()
     if v[7] > 0:
-        raise IndexError("%d target(s) fall outside the %dx%d feature map" % (int(v[7]), x.shape[2], x.shape[3]))
+        raise IndexError("%d target(s) fall outside the %dx%d feature map or name a class outside 0 .. %d"
+                         % (int(v[7]), x.shape[2], x.shape[3], self.num_classes - 1))
     return loss, v[1], v[2], v[3], v[4], v[5], v[6]
 
 
