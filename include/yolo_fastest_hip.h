@@ -250,6 +250,39 @@ int yf_train_adam_multi_pinned(int device, int ntensors, void *const *d_p, const
                                const long *sizes, double lr, double beta1, double beta2, double eps, int step, void *d_table, size_t table_bytes,
                                void *h_table_pinned, int upload, void *stream);
 
+/* Every tensor of every param group of an optimizer in ONE launch (training.SGD, training.Adam).  `kind` selects the update:
+ *   YF_OPT_SGD   torch.optim.SGD(lr, momentum, weight_decay, nesterov), bit for bit, every scalar rounded once from double to float:
+ *                    d = weight_decay != 0 ? fma(weight_decay, p, g) : g
+ *                    buf = first[t] ? d : round(momentum * buf) + d          (momentum != 0 only; d_s1[t] is the momentum buffer)
+ *                    d = nesterov ? fma(momentum, buf, d) : buf
+ *                    p = fma(-lr, d, p)
+ *                first[t] != 0 marks a tensor's first step (its buffer is written, not read); first NULL = no tensor is on its first
+ *                step.  d_s1 may be NULL when no group has momentum, d_s2 is not read.
+ *   YF_OPT_ADAM  torch.optim.Adam(lr, betas, eps, weight_decay) (L2, not AdamW): g' = weight_decay != 0 ? fma(weight_decay, p, g) : g,
+ *                then the arithmetic of yf_train_adam_multi (with weight_decay == 0: its bits).  d_s1 = exp_avg, d_s2 = exp_avg_sq,
+ *                groups[i].step counts from 1; first is not read.
+ * group_of[t] names tensor t's group, 0 .. ngroups-1, ngroups <= YF_OPT_MAX_GROUPS.  The per-group scalars travel as kernel arguments,
+ * not in the table: a call that only changes them (the warm-up's per-iteration lr) passes upload == 0.  d_table / h_table_pinned /
+ * upload as in yf_train_adam_multi_pinned, with YF_OPT_TABLE_ENTRY_BYTES per tensor; upload != 0 too when group_of or first changed.
+ * YF_E_INVALID before the GPU is touched for: a null pointer, a size <= 0, a group index out of range, ngroups outside
+ * 1 .. YF_OPT_MAX_GROUPS, dampening != 0, maximize != 0, nesterov without momentum, a negative momentum, Adam step < 1, an unknown kind. */
+#define YF_OPT_ADAM 0
+#define YF_OPT_SGD 1
+#define YF_OPT_MAX_GROUPS 8
+#define YF_OPT_TABLE_ENTRY_BYTES 56
+typedef struct yf_opt_group {
+    double lr, weight_decay;
+    double momentum, dampening;         /* SGD; dampening must be 0 */
+    double beta1, beta2, eps;           /* Adam */
+    int nesterov;                       /* SGD */
+    int step;                           /* Adam: this step's number, >= 1 */
+    int maximize;                       /* must be 0 */
+    int reserved;
+} yf_opt_group;
+int yf_train_opt_multi_pinned(int device, int kind, int ntensors, void *const *d_p, const void *const *d_g, void *const *d_s1, void *const *d_s2,
+                              const long *sizes, const int *group_of, const int *first, int ngroups, const yf_opt_group *groups, void *d_table,
+                              size_t table_bytes, void *h_table_pinned, int upload, void *stream);
+
 /* The same training forward / backward as ONE call each: the whole graph of yolo_fastest.py:150-218 in train mode (what
  * `pred = model(imgs)` and `loss.backward()` run, train.py:114, :131), launched from C++ into a caller-owned workspace.
  *   d_params / d_grads: HOST arrays of yf_trainer_num_params() device pointers in `model.parameters()` order (per conv block: conv

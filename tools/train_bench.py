@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Training-step throughput (train.py:111-132: zero_grad, train-mode forward, two-head loss, backward, Adam) on synthetic frames.
-GPU box: python tools/train_bench.py [--batch 16] [--steps 20] [--cpu]   (--cpu also times oracle/ on the host cores: the baseline)"""
+GPU box: python tools/train_bench.py [--batch 16] [--steps 20] [--optimizer reference|adam|sgd] [--cpu]   (--cpu also times oracle/ on the host cores: the baseline)"""
 import argparse
 import os
 import sys
@@ -19,6 +19,10 @@ ap.add_argument("--batch", type=int, default=16)
 ap.add_argument("--steps", type=int, default=20)
 ap.add_argument("--warmup", type=int, default=8)
 ap.add_argument("--res", type=int, default=256)
+ap.add_argument("--optimizer", choices=["reference", "adam", "sgd"], default="reference",
+                help="reference: train.py:84's Adam on one group; adam / sgd: what training.train(optimizer=...) builds, three groups")
+ap.add_argument("--branch-weight", type=float, nargs=2, default=None, metavar=("LARGE", "SMALL"),
+                help="train_step(branch_weight=...): factors other than 1 take one backward per head")
 ap.add_argument("--cpu", action="store_true")
 ap.add_argument("--json", action="store_true", help="also print one JSON line (metric, value, ms per iteration, cpu baseline)")
 a = ap.parse_args()
@@ -39,21 +43,27 @@ for b in range(a.batch):
     t[b, :k, 4] = rng.integers(0, 3, k); t[b, :k, 5] = 255.0
 tt = torch.from_numpy(t)
 crit = [val.YOLOLossV3(io["anchors"][i], 3, io["input_shape"], dev, model=m) for i in range(2)]
-opt = training.Adam(m.parameters(), lr=0.001)
+tp = yf.config_params["train_params"]
+if a.optimizer == "reference":               # train.py:84: one group
+    opt = training.Adam(m.parameters(), lr=0.001)
+elif a.optimizer == "adam":                  # train(optimizer="adam"): yolov5's three groups, the decay on the convolution weights
+    opt = training.Adam(training.param_groups(m, tp["weight_decay"]), lr=0.001, betas=(tp["momentum"], 0.999))
+else:                                        # train(optimizer="sgd")
+    opt = training.SGD(training.param_groups(m, tp["weight_decay"]), lr=0.001, momentum=tp["momentum"], nesterov=True)
 xd, td = x.to(dev), tt.to(dev)
 for _ in range(a.warmup):
-    training.train_step(m, crit, opt, xd, td)
+    training.train_step(m, crit, opt, xd, td, a.branch_weight)
 torch.cuda.synchronize()
 t0 = time.perf_counter()
 for _ in range(a.steps):
-    loss = training.train_step(m, crit, opt, xd, td)[0]
+    loss = training.train_step(m, crit, opt, xd, td, a.branch_weight)[0]
 torch.cuda.synchronize()
 dt = (time.perf_counter() - t0) / a.steps
 print("GPU  batch %d %dx%d: %.2f ms / iteration, %.0f examples/s, loss %.4f" % (a.batch, H, W, dt * 1e3, a.batch / dt, float(loss.detach())))
 line = {"metric": "training_examples_per_second", "value": round(a.batch / dt, 1), "unit": "examples/s", "ms_per_iteration": round(dt * 1e3, 3),
         "steps": a.steps, "warmup": a.warmup, "dtype": "f32", "data": "synthetic",
         "config": {"workload": "train.py:111-132 iteration (zero_grad, train-mode forward, two-head loss, backward, Adam)", "batch": a.batch,
-                   "input": [H, W]}, "cpu_baseline": None}
+                   "input": [H, W], "optimizer": a.optimizer}, "cpu_baseline": None}
 if a.cpu:
     from oracle import backbone_oracle as bo, loss_oracle as lo
     sd = bo.training_state(sd0)

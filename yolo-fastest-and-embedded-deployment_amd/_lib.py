@@ -14,6 +14,17 @@ YF_JPEG_PROGRESSIVE = 1                            # yf_jpeg_pack_ex flag
 YF_OK, YF_E_INVALID, YF_E_BLOB, YF_E_HIP, YF_E_WORKSPACE, YF_E_NOPROBE = 0, -1, -2, -3, -4, -5
 
 _c = ctypes
+
+YF_OPT_ADAM, YF_OPT_SGD, YF_OPT_MAX_GROUPS, YF_OPT_TABLE_ENTRY_BYTES = 0, 1, 8, 56     # yf_train_opt_multi_pinned
+
+
+class OptGroup(_c.Structure):
+    """yf_opt_group: one param group's scalars of yf_train_opt_multi_pinned"""
+    _fields_ = [("lr", _c.c_double), ("weight_decay", _c.c_double), ("momentum", _c.c_double), ("dampening", _c.c_double),
+                ("beta1", _c.c_double), ("beta2", _c.c_double), ("eps", _c.c_double), ("nesterov", _c.c_int), ("step", _c.c_int),
+                ("maximize", _c.c_int), ("reserved", _c.c_int)]
+
+
 _SIGS = {
     "yf_abi_version": (_c.c_int, []),
     "yf_last_error_string": (_c.c_char_p, []),
@@ -89,6 +100,8 @@ _SIGS = {
     "yf_train_adam_multi_pinned": (_c.c_int, [_c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_double,
                                               _c.c_double, _c.c_double, _c.c_double, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_int,
                                               _c.c_void_p]),
+    "yf_train_opt_multi_pinned": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int] + [_c.c_void_p] * 7 + [_c.c_int, _c.c_void_p, _c.c_void_p, _c.c_size_t,
+                                             _c.c_void_p, _c.c_int, _c.c_void_p]),
     "yf_train_channel_sum": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_long, _c.c_void_p]),
     "yf_train_channel_sum_split": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_long, _c.c_void_p, _c.c_void_p]),
     "yf_train_add": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_long, _c.c_void_p]),

@@ -44,9 +44,9 @@ config_params = {
         "total_epochs": 30,
         "batch_size": 16,
         "lr0": 0.001,                       # initial learning rate (Adam)
-        "momentum": 0.937,                  # unused by the reference's Adam call (train.py:84 passes betas explicitly)
-        "weight_decay": 0.0005,             # unused by the reference (no weight_decay argument at train.py:84)
-        "branch_weight": [1.0, 1.0],
+        "momentum": 0.937,                  # SGD momentum / Adam beta1 (yolov5's hyp key): read by training.train(optimizer="sgd" | "adam") only; the reference's Adam call (train.py:84) passes betas explicitly
+        "weight_decay": 0.0005,             # on the convolution weights: read by training.train(optimizer="sgd" | "adam") only; the reference passes none (train.py:84)
+        "branch_weight": [1.0, 1.0],        # per-head loss factors: read by training.train(branch_weight=True) only; the reference sums the heads unweighted (train.py:129-130)
         "IOU_loss_thre": 0.5,               # anchors whose shape IoU with a target exceeds this are not punished as background
         "IOU_val_thre": 0.5,                # match threshold of the mAP computation
     },

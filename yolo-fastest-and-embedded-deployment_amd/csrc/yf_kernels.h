@@ -379,6 +379,11 @@ void launch_tbn_bwd(const float* x, const float* dy, const float* stats, const f
                     int N, int C, long HW, int relu, void* scratch, hipStream_t s, const TBnRed* red = nullptr);
 int launch_tadam_multi(int nt, float* const* p, const float* const* g, float* const* m, float* const* v, const long* sizes, double lr, double b1,
                        double b2, double eps, int step, void* d_table, void* h_table, int upload, hipStream_t s);
+// one param group of launch_topt_multi (the C ABI's yf_opt_group, checked); kind: 0 Adam, 1 SGD; table entries are 56 bytes
+struct TOptGroup { double lr, wd, mom, b1, b2, eps; int nesterov, step; };
+int launch_topt_multi(int kind, int nt, float* const* p, const float* const* g, float* const* s1, float* const* s2, const long* sizes,
+                      const int* group_of, const int* first, int ngroups, const TOptGroup* groups, void* d_table, void* h_table, int upload,
+                      hipStream_t s);
 void launch_tchan_sum(const float* dy, float* out, int N, int C, long HW, hipStream_t s, void* scratch = nullptr /* >= 64 C doubles */);
 void launch_tadd(const float* a, const float* b, float* out, long total, hipStream_t s);
 void launch_tslice(const float* src, float* dst, int N, int C, long HW, int Cs, int sc0, int Cd, int dc0, hipStream_t s);

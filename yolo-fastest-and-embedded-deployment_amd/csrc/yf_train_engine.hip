@@ -369,6 +369,45 @@ int yf_train_adam_multi_pinned(int device, int ntensors, void* const* d_p, const
     HIP_OK(hipGetLastError());
     return YF_OK;
 }
+int yf_train_opt_multi_pinned(int device, int kind, int ntensors, void* const* d_p, const void* const* d_g, void* const* d_s1, void* const* d_s2,
+                              const long* sizes, const int* group_of, const int* first, int ngroups, const yf_opt_group* groups, void* d_table,
+                              size_t table_bytes, void* h_table_pinned, int upload, void* stream)
+{
+    static_assert(YF_OPT_MAX_GROUPS == 8 && YF_OPT_TABLE_ENTRY_BYTES == 56, "the kernels' group array and table entry (yf_train_opt_kernels.h)");
+    if (kind != YF_OPT_ADAM && kind != YF_OPT_SGD) return fail(YF_E_INVALID, "yf_train_opt_multi: unknown kind %d", kind);
+    if (!d_p || !d_g || !sizes || !group_of || !groups || !d_table || ntensors <= 0 || table_bytes < (size_t)ntensors * YF_OPT_TABLE_ENTRY_BYTES)
+        return fail(YF_E_INVALID, "yf_train_opt_multi: bad argument");
+    if (ngroups < 1 || ngroups > YF_OPT_MAX_GROUPS) return fail(YF_E_INVALID, "yf_train_opt_multi: %d groups (1 .. %d)", ngroups, YF_OPT_MAX_GROUPS);
+    if (kind == YF_OPT_ADAM && (!d_s1 || !d_s2)) return fail(YF_E_INVALID, "yf_train_opt_multi: Adam needs both state arrays");
+    yf::TOptGroup gs[YF_OPT_MAX_GROUPS];
+    for (int i = 0; i < ngroups; ++i) {
+        const yf_opt_group& q = groups[i];
+        if (q.maximize) return fail(YF_E_INVALID, "yf_train_opt_multi: group %d: maximize is not implemented", i);
+        if (kind == YF_OPT_SGD) {
+            if (q.dampening != 0) return fail(YF_E_INVALID, "yf_train_opt_multi: group %d: dampening is not implemented", i);
+            if (!(q.momentum >= 0)) return fail(YF_E_INVALID, "yf_train_opt_multi: group %d: negative momentum", i);
+            if (q.nesterov && q.momentum == 0) return fail(YF_E_INVALID, "yf_train_opt_multi: group %d: nesterov needs a momentum", i);
+        } else if (q.step < 1) {
+            return fail(YF_E_INVALID, "yf_train_opt_multi: group %d: step %d (counts from 1)", i, q.step);
+        }
+        gs[i] = yf::TOptGroup{q.lr, q.weight_decay, q.momentum, q.beta1, q.beta2, q.eps, q.nesterov, q.step};
+    }
+    long blocks = 0;
+    for (int t = 0; t < ntensors; ++t) {
+        if (group_of[t] < 0 || group_of[t] >= ngroups) return fail(YF_E_INVALID, "yf_train_opt_multi: tensor %d: group %d of %d", t, group_of[t], ngroups);
+        const bool need1 = kind == YF_OPT_ADAM || gs[group_of[t]].mom != 0;
+        if (!d_p[t] || !d_g[t] || sizes[t] <= 0 || (need1 && (!d_s1 || !d_s1[t])) || (kind == YF_OPT_ADAM && !d_s2[t]))
+            return fail(YF_E_INVALID, "yf_train_opt_multi: tensor %d: null pointer or empty", t);
+        blocks += (sizes[t] + 255) / 256;
+        if (blocks > 0x7fffffffL) return fail(YF_E_INVALID, "yf_train_opt_multi: more than 2^31 workgroups");
+    }
+    HIP_OK(hipSetDevice(device));
+    if (yf::launch_topt_multi(kind, ntensors, (float* const*)d_p, (const float* const*)d_g, (float* const*)d_s1, (float* const*)d_s2, sizes, group_of,
+                              first, ngroups, gs, d_table, h_table_pinned, upload, (hipStream_t)stream))
+        return fail(YF_E_HIP, "yf_train_opt_multi: the upload of the pointer table failed");
+    HIP_OK(hipGetLastError());
+    return YF_OK;
+}
 // ---- the trainer: forward and backward of the whole network as one call each ----
 int yf_trainer_create(int H, int W, int device, yf_trainer* out) { return yf_trainer_create_ex(H, W, device, 1, 24, out); }
 

@@ -589,4 +589,42 @@ int launch_tadam_multi(int nt, float* const* p, const float* const* g, float* co
     return 0;
 }
 
+// The same scheme for every tensor of every param group (kind 0 = Adam, 1 = SGD): the table entry names its group and carries the
+// first-step mark; the groups' scalars, formed in double and rounded once to float like torch's Python-double scalars, are kernel
+// arguments.  h_table null: staged from pageable memory on every call, as above.  The caller has checked every argument.
+int launch_topt_multi(int kind, int nt, float* const* p, const float* const* g, float* const* s1, float* const* s2, const long* sizes,
+                      const int* group_of, const int* first, int ngroups, const TOptGroup* groups, void* d_table, void* h_table, int upload,
+                      hipStream_t s)
+{
+    static_assert(sizeof(TOptEntry) == 56, "YF_OPT_TABLE_ENTRY_BYTES");
+    static thread_local std::vector<TOptEntry> tab;
+    TOptEntry* host = static_cast<TOptEntry*>(h_table);
+    if (!host) { tab.resize(nt); host = tab.data(); upload = 1; }
+    long blocks = 0;
+    for (int t = 0; t < nt; ++t) {
+        if (upload) host[t] = TOptEntry{p[t], g[t], s1 ? s1[t] : nullptr, s2 ? s2[t] : nullptr, blocks, sizes[t], group_of[t], first ? first[t] : 0};
+        blocks += (sizes[t] + 255) / 256;
+    }
+    if (upload && hipMemcpyAsync(d_table, host, (size_t)nt * sizeof(TOptEntry), hipMemcpyHostToDevice, s) != hipSuccess) return -1;
+    if (kind == 1) {
+        TSgdGroups gs = {};
+        for (int i = 0; i < ngroups; ++i) {
+            const TOptGroup& q = groups[i];
+            gs.g[i] = TSgdGroup{(float)q.wd, (float)q.mom, (float)-q.lr,
+                                (q.nesterov ? TOPT_NESTEROV : 0) | (q.wd != 0 ? TOPT_DECAY : 0) | (q.mom != 0 ? TOPT_MOMENTUM : 0)};
+        }
+        hipLaunchKernelGGL(tsgd_group_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const TOptEntry*)d_table, nt, gs);
+    } else {
+        TAdamGroups gs = {};
+        for (int i = 0; i < ngroups; ++i) {
+            const TOptGroup& q = groups[i];
+            const double bc1 = 1.0 - pow(q.b1, (double)q.step), bc2 = 1.0 - pow(q.b2, (double)q.step);
+            gs.g[i] = TAdamGroup{(float)q.wd, (float)(1.0 - q.b1), (float)q.b2, (float)(1.0 - q.b2), (float)q.eps, (float)(q.lr / bc1),
+                                 (float)sqrt(bc2), q.wd != 0 ? TOPT_DECAY : 0};
+        }
+        hipLaunchKernelGGL(tadam_group_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const TOptEntry*)d_table, nt, gs);
+    }
+    return 0;
+}
+
 }  // namespace yf

@@ -1,4 +1,4 @@
-// yf_train_opt_kernels.h -- sums of split partial results, channel sums (bias gradients), add / slice, Adam
+// yf_train_opt_kernels.h -- sums of split partial results, channel sums (bias gradients), add / slice, Adam, SGD
 // Part of the training-step operators: yf_train_kernels.hip includes the family headers into ONE translation unit, INSIDE namespace yf, so the
 // kernels keep their internal linkage and the launchers in that file see all of them.  Device code: include from there only.
 #pragma once
@@ -114,4 +114,59 @@ __global__ void __launch_bounds__(256) tadam_multi_kernel(const TAdamEntry* __re
     const float vi = e.v[idx] * b2 + (w2 * gi) * gi;
     e.m[idx] = mi; e.v[idx] = vi;
     e.p[idx] += -step_size * (mi / (sqrtf(vi) / bc2_sqrt + eps));
+}
+
+// ---- every tensor of every param group of an optimizer in one launch (training.SGD, training.Adam) ----
+// tab[t] = {p, g, state 1, state 2, first block, elements, param group, first step}; the groups' scalars are kernel arguments, indexed by
+// the entry's group (wave-uniform: a workgroup lies inside one tensor), so an lr edit between two steps changes no device memory.
+struct TOptEntry { float* p; const float* g; float* s1; float* s2; long block0; long n; int group; int first; };
+enum { TOPT_MAX_GROUPS = 8, TOPT_NESTEROV = 1, TOPT_DECAY = 2, TOPT_MOMENTUM = 4 };
+struct TSgdGroup { float wd, mom, neg_lr; int flags; };
+struct TSgdGroups { TSgdGroup g[TOPT_MAX_GROUPS]; };
+struct TAdamGroup { float wd, w1, b2, w2, eps, step_size, bc2_sqrt; int flags; };
+struct TAdamGroups { TAdamGroup g[TOPT_MAX_GROUPS]; };
+
+__device__ __forceinline__ TOptEntry topt_entry(const TOptEntry* __restrict__ tab, int nt)
+{
+    int lo = 0, hi = nt - 1;                                   // the tensor this workgroup belongs to
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (tab[mid].block0 <= (long)blockIdx.x) lo = mid; else hi = mid - 1; }
+    return tab[lo];
+}
+
+// torch.optim.SGD(momentum, weight_decay, nesterov; dampening 0), bit for bit (the operations of torch's _single_tensor_sgd, each
+// `add(x, alpha=a)` one fused multiply-add, `buf.mul_(momentum)` a rounded product of its own):
+//   d = g + wd p;  buf = mom buf + d (first step: buf = d);  d = nesterov ? d + mom buf : buf;  p += -lr d
+// The wd == 0 and first-step branches keep signed zeros: fma(0, p, -0.0) and 0 * mom + (-0.0) are +0.0 where torch keeps -0.0.
+__global__ void __launch_bounds__(256) tsgd_group_kernel(const TOptEntry* __restrict__ tab, int nt, TSgdGroups gs)
+{
+    const TOptEntry e = topt_entry(tab, nt);
+    const long idx = ((long)blockIdx.x - e.block0) * 256 + threadIdx.x;
+    if (idx >= e.n) return;
+    const TSgdGroup s = gs.g[__builtin_amdgcn_readfirstlane(e.group) & (TOPT_MAX_GROUPS - 1)];
+    const float pi = e.p[idx];
+    float d = e.g[idx];
+    if (s.flags & TOPT_DECAY) d = __fmaf_rn(s.wd, pi, d);
+    if (s.flags & TOPT_MOMENTUM) {
+        float buf = d;
+        if (!e.first) { const float mb = s.mom * e.s1[idx]; buf = mb + d; }
+        e.s1[idx] = buf;
+        d = (s.flags & TOPT_NESTEROV) ? __fmaf_rn(s.mom, buf, d) : buf;
+    }
+    e.p[idx] = __fmaf_rn(s.neg_lr, d, pi);
+}
+
+// torch.optim.Adam with weight_decay (L2: the gradient becomes g + wd p, one fused multiply-add), then tadam_multi_kernel's sequence
+// unchanged -- with wd == 0 its bits.
+__global__ void __launch_bounds__(256) tadam_group_kernel(const TOptEntry* __restrict__ tab, int nt, TAdamGroups gs)
+{
+    const TOptEntry e = topt_entry(tab, nt);
+    const long idx = ((long)blockIdx.x - e.block0) * 256 + threadIdx.x;
+    if (idx >= e.n) return;
+    const TAdamGroup s = gs.g[__builtin_amdgcn_readfirstlane(e.group) & (TOPT_MAX_GROUPS - 1)];
+    float gi = e.g[idx];
+    if (s.flags & TOPT_DECAY) gi = __fmaf_rn(s.wd, e.p[idx], gi);
+    const float mi = e.s1[idx] + s.w1 * (gi - e.s1[idx]);
+    const float vi = e.s2[idx] * s.b2 + (s.w2 * gi) * gi;
+    e.s1[idx] = mi; e.s2[idx] = vi;
+    e.p[idx] += -s.step_size * (mi / (sqrtf(vi) / s.bc2_sqrt + s.eps));
 }

@@ -5,13 +5,13 @@
     pred = model(imgs)                                   # train-mode forward: BatchNorm on batch statistics, running stats updated
     loss = sum(model_loss[i](pred[i], targets)[0] ...)   # validation.YOLOLossV3 (yf_train_loss)
     loss.backward()                                      # backward of every layer -> param.grad
-    optimizer.step()                                     # training.Adam (yf_train_adam_multi) -- or any torch optimizer
+    optimizer.step()                                     # training.Adam / training.SGD (yf_train_opt_multi_pinned) -- or any torch optimizer
 
 `YoloFastest.forward` routes here when the module is in train mode.  Forward and backward of the whole network are ONE C call each
 (`yf_trainer_forward` / `yf_trainer_backward`: the graph walked in C++ over a workspace that is the pass's tape); `model.train_impl =
 "ops"` selects the same computation orchestrated from Python, one C call per block (bring-up, probing).  Every operator is a HIP
 kernel behind the C ABI (`yf_train_*`, csrc/yf_train_kernels.hip): Conv2d / ConvTranspose2d forward, backward-data, backward-weight; BatchNorm2d in train
-mode with its backward (ReLU fused); channel slices for the torch.cat; Adam.  torch.autograd only carries the gradient across the
+mode with its backward (ReLU fused); channel slices for the torch.cat; Adam and SGD.  torch.autograd only carries the gradient across the
 boundary (one Function for the whole network whose inputs are the parameters) -- no torch operator computes anything.
 NCHW fp32 like the reference -- not the tuned inference engine (which folds BatchNorm into the weights and so cannot train); kernels
 and measurements: DESIGN.md section 4 "The training step".  `train()` is the reference's epoch loop around the iteration,
@@ -287,6 +287,9 @@ def _structure(model):
     return st
 
 
+_KEEP_TAPE = [0]     # > 0 while train_step takes the heads back one at a time: the backward only reads the tape, so it may run again
+
+
 class _TrainForwardFn(torch.autograd.Function):
     """The whole network as one autograd node: inputs = the parameters, outputs = the two heads."""
 
@@ -306,7 +309,8 @@ class _TrainForwardFn(torch.autograd.Function):
             raise RuntimeError("backward through the training forward a second time: its saved activations were freed")
         if ctx.tr is None:
             grads = train_backward(ctx.model, ctx.tape, g_hl.contiguous(), g_hs.contiguous())
-            ctx.tape = None
+            if not _KEEP_TAPE[0]:
+                ctx.tape = None
             return (None, None) + tuple(grads[p] for p in ctx.params)
         x, ws = ctx.tape
         tr, params = ctx.tr, ctx.params
@@ -322,7 +326,8 @@ class _TrainForwardFn(torch.autograd.Function):
                                               gp, ws.data_ptr(), ws.numel(),
                                               ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
         grads = [g.view(shp) for g, shp in zip(flat.split(lay["sizes"]), lay["shapes"])]
-        ctx.tape = None
+        if not _KEEP_TAPE[0]:
+            ctx.tape = None
         sync = getattr(ctx.model, "_grad_sync", None)
         if sync is not None:                                     # data_parallel(): one all-reduce of the flat gradient buffer
             from . import dist as yfd
@@ -414,17 +419,28 @@ def sync_buffers(model, process_group=None):
     return model
 
 
-class Adam(torch.optim.Optimizer):
-    """`optim.Adam(model.parameters(), lr=lr0, betas=(0.9, 0.999), eps=1e-08)` (train.py:84) with the update done by yf_train_adam_multi (one launch for all tensors).
-    A torch.optim.Optimizer, so `param_groups[..]['lr']` edits (train.py:106-109) and `lr_scheduler.LambdaLR` (:89) work unchanged; the
-    state uses torch's names (step, exp_avg, exp_avg_sq)."""
-
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
+class _MultiTensorOptimizer(torch.optim.Optimizer):
+    """What training.Adam and training.SGD share: `step()` is ONE launch (yf_train_opt_multi_pinned) for every tensor of every param
+    group -- the table entry of a tensor names its group, the groups' scalars (lr, weight_decay, ...) travel as kernel arguments -- when
+    the tensors share a device and, for Adam, a step count; otherwise one launch per (device, step).  A torch.optim.Optimizer, so
+    `param_groups[..]['lr']` edits (train.py:106-109) and `lr_scheduler.LambdaLR` (:89) work unchanged, and the state uses torch's names."""
+    _kind = None
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
-        self.__dict__.pop("_groups", None)               # the cached state tensors may have been replaced
+        self.__dict__.pop("_cache", None)                # the cached state tensors may have been replaced
+
+    def _state(self, q, group):
+        """-> (state tensor 1 or None, state tensor 2 or None, 1 if this is the tensor's first step of a kind the kernel must know)"""
+        raise NotImplementedError
+
+    def _scalars(self, og, group, step):
+        """fill the yf_opt_group `og` from the param group"""
+        raise NotImplementedError
+
+    def _shape_key(self):
+        """what, beside the participating tensors, decides which state tensors a step needs"""
+        return None
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -432,92 +448,202 @@ class Adam(torch.optim.Optimizer):
             raise NotImplementedError("closure")
         lib = _lib.lib()
         f32 = torch.float32
-        for gi, group in enumerate(self.param_groups):
-            b1, b2 = group["betas"]
-            ps = group["params"]
-            gs = [p.grad for p in ps]
-            if any(g is None for g in gs):               # (not `None in gs`: that compares tensors with ==)
-                ps = [p for p, g in zip(ps, gs) if g is not None]
-                gs = [g for g in gs if g is not None]
-            if not ps:
-                continue
-            # per group, cached while the same Parameter objects take part: the state tensors, their pointers, the ctypes arrays of
-            # everything that does not change between steps (at batch 16 the host, not the GPU, was the slower side of an iteration)
-            cg = self.__dict__.setdefault("_groups", {}).get(gi)
-            if cg is None or len(cg["ps"]) != len(ps) or any(a is not b for a, b in zip(cg["ps"], ps)):
-                for q in ps:
-                    if not q.is_cuda or q.dtype is not f32 or not q.is_contiguous():
-                        raise RuntimeError("training.Adam (HIP) has no CPU path: contiguous float32 GPU parameters only")
-                    st = self.state[q]
-                    if not st:
-                        st["step"], st["exp_avg"], st["exp_avg_sq"] = 0, torch.zeros_like(q), torch.zeros_like(q)
-                sts = [self.state[q] for q in ps]
-                n = len(ps)
-                cg = self._groups[gi] = dict(ps=list(ps), sts=sts, m=[st["exp_avg"] for st in sts], v=[st["exp_avg_sq"] for st in sts],
-                                             sizes=(ctypes.c_long * n)(*[q.numel() for q in ps]))
-                cg["mp"] = tuple(t.data_ptr() for t in cg["m"])
-                cg["vp"] = tuple(t.data_ptr() for t in cg["v"])
-                cg["ma"], cg["va"] = (ctypes.c_void_p * n)(*cg["mp"]), (ctypes.c_void_p * n)(*cg["vp"])
-                cg["pp"] = None
+        name = type(self).__name__
+        groups = self.param_groups
+        if len(groups) > _lib.YF_OPT_MAX_GROUPS:
+            raise ValueError("training.%s takes up to %d param groups (got %d)" % (name, _lib.YF_OPT_MAX_GROUPS, len(groups)))
+        ps, gs, gof = [], [], []
+        for gi, group in enumerate(groups):
+            for p in group["params"]:
+                g = p.grad
+                if g is not None:
+                    ps.append(p); gs.append(g); gof.append(gi)
+        if not ps:
+            return
+        # cached while the same Parameter objects take part: the state tensors, their pointers, the ctypes arrays of everything that does
+        # not change between steps (at batch 16 the host, not the GPU, was the slower side of an iteration)
+        c = self.__dict__.get("_cache")
+        key = self._shape_key()
+        if c is None or c["gof"] != gof or c["key"] != key or any(a is not b for a, b in zip(c["ps"], ps)):
+            s1, s2, first = [], [], []
+            for q, gi in zip(ps, gof):
+                if not q.is_cuda or q.dtype is not f32 or not q.is_contiguous():
+                    raise RuntimeError("training.%s (HIP) has no CPU path: contiguous float32 GPU parameters only" % name)
+                a, b, f = self._state(q, groups[gi])
+                s1.append(a); s2.append(b); first.append(f)
             n = len(ps)
-            pp = tuple(q.data_ptr() for q in ps)
-            if pp != cg["pp"]:                               # (a .to() / .float() of the model moves the parameters)
-                cg["pp"], cg["pa"] = pp, (ctypes.c_void_p * n)(*pp)
-            gs = [g if g.is_contiguous() else g.contiguous() for g in gs]
-            gp = tuple(g.data_ptr() for g in gs)
+            c = self._cache = dict(ps=list(ps), gof=gof, key=key, sts=[self.state[q] for q in ps], s1=s1, s2=s2, first=first,
+                                   sizes=[q.numel() for q in ps], s1p=tuple(_ptr(t) for t in s1), s2p=tuple(_ptr(t) for t in s2), pp=None)
+            c["full"] = dict(s1a=(ctypes.c_void_p * n)(*c["s1p"]), s2a=(ctypes.c_void_p * n)(*c["s2p"]), sizes=(ctypes.c_long * n)(*c["sizes"]),
+                             gof=(ctypes.c_int * n)(*gof))
+        n = len(ps)
+        pp = tuple(q.data_ptr() for q in ps)
+        if pp != c["pp"]:                                    # (a .to() / .float() of the model moves the parameters)
+            c["pp"], c["full"]["pa"] = pp, (ctypes.c_void_p * n)(*pp)
+        gs = [g if g.is_contiguous() else g.contiguous() for g in gs]
+        gp = tuple(g.data_ptr() for g in gs)
+        first = tuple(c["first"])
+        klist = None
+        if self._kind == _lib.YF_OPT_ADAM:
             klist = []
-            for st in cg["sts"]:
+            for st in c["sts"]:
                 k = st["step"] = int(st["step"]) + 1         # (a loaded torch.optim.Adam state carries `step` as a tensor)
                 klist.append(k)
-            device = ps[0].device
-            if min(klist) == max(klist) and all(q.device == device for q in ps):
-                launches = [(device, klist[0], None)]        # the usual case: one launch for the whole group
-            else:                                            # mixed devices / step counts: one launch per (device, step)
-                parts = {}
-                for i, (q, k) in enumerate(zip(ps, klist)):
-                    parts.setdefault((q.device, k), []).append(i)
-                launches = [(d, k, idx) for (d, k), idx in parts.items()]
-            for device, step, idx in launches:
-                if idx is None:
-                    n, ptrs = len(ps), (pp, gp, cg["mp"], cg["vp"])
-                    arrs = (cg["pa"], (ctypes.c_void_p * n)(*gp), cg["ma"], cg["va"], cg["sizes"])
-                else:
-                    n = len(idx)
-                    ptrs = tuple(tuple(t[i] for i in idx) for t in (pp, gp, cg["mp"], cg["vp"]))
-                    arrs = tuple((ctypes.c_void_p * n)(*t) for t in ptrs) + ((ctypes.c_long * n)(*[cg["sizes"][i] for i in idx]),)
-                # The pointer table lives on the device, with a pinned host copy, per (device, tensor count); it is re-uploaded only when
-                # a pointer changed (p, exp_avg, exp_avg_sq never do; the gradients are views of the trainer's flat buffer, which the
-                # caching allocator hands back every iteration) -- so a step is normally ONE asynchronous launch and the host runs ahead.
-                cache = self.__dict__.setdefault("_tables", {})
-                ent = cache.get((device, n))
-                if ent is None:
-                    ent = cache[(device, n)] = dict(dev=torch.empty(48 * n, dtype=torch.uint8, device=device),
-                                                    host=torch.empty(48 * n, dtype=torch.uint8).pin_memory(), key=None, event=None)
-                upload = ent["key"] != ptrs
-                if upload and ent["event"] is not None:
-                    ent["event"].synchronize()           # the previous upload has left the pinned buffer
-                dev = device.index if device.index is not None else torch.cuda.current_device()
-                stream = torch.cuda.current_stream(device)
-                _lib.check(lib.yf_train_adam_multi_pinned(dev, n, arrs[0], arrs[1], arrs[2], arrs[3], arrs[4], float(group["lr"]), float(b1),
-                                                          float(b2), float(group["eps"]), int(step), ent["dev"].data_ptr(), ent["dev"].numel(),
-                                                          ent["host"].data_ptr(), int(upload), ctypes.c_void_p(stream.cuda_stream)))
-                if upload:
-                    ent["key"] = ptrs
-                    ent["event"] = torch.cuda.Event()
-                    ent["event"].record(stream)
-            self._keep = gs                      # alive until the next step: the launch is asynchronous
+        device = ps[0].device
+        if all(q.device == device for q in ps) and (klist is None or min(klist) == max(klist)):
+            launches = [(device, klist[0] if klist else 0, None)]     # the usual case: one launch for everything
+        else:                                                # mixed devices / step counts: one launch per (device, step)
+            parts = {}
+            for i, q in enumerate(ps):
+                parts.setdefault((q.device, klist[i] if klist else 0), []).append(i)
+            launches = [(d, k, idx) for (d, k), idx in parts.items()]
+        ng = len(groups)
+        for device, step, idx in launches:
+            og = (_lib.OptGroup * ng)()                      # per launch: lr is edited between steps, Adam's step differs per launch
+            for gi, group in enumerate(groups):
+                self._scalars(og[gi], group, step)
+            if idx is None:
+                ptrs = (pp, gp, c["s1p"], c["s2p"], first)
+                f = c["full"]
+                arrs = (f["pa"], (ctypes.c_void_p * n)(*gp), f["s1a"], f["s2a"], f["sizes"], f["gof"], (ctypes.c_int * n)(*first))
+                m = n
+            else:
+                m = len(idx)
+                ptrs = tuple(tuple(t[i] for i in idx) for t in (pp, gp, c["s1p"], c["s2p"], first))
+                arrs = tuple((ctypes.c_void_p * m)(*t) for t in ptrs[:4]) + ((ctypes.c_long * m)(*[c["sizes"][i] for i in idx]),
+                                                                             (ctypes.c_int * m)(*[gof[i] for i in idx]), (ctypes.c_int * m)(*ptrs[4]))
+            # The pointer table lives on the device, with a pinned host copy, per (device, tensor count); it is re-uploaded only when
+            # an entry changed (p and the state tensors never do; the gradients are views of the trainer's flat buffer, which the
+            # caching allocator hands back every iteration; SGD's first-step marks fall after the first step) -- so a step is normally
+            # ONE asynchronous launch and the host runs ahead.
+            cache = self.__dict__.setdefault("_tables", {})
+            ent = cache.get((device, m))
+            if ent is None:
+                nb = _lib.YF_OPT_TABLE_ENTRY_BYTES * m
+                ent = cache[(device, m)] = dict(dev=torch.empty(nb, dtype=torch.uint8, device=device),
+                                                host=torch.empty(nb, dtype=torch.uint8).pin_memory(), key=None, event=None)
+            upload = ent["key"] != ptrs
+            if upload and ent["event"] is not None:
+                ent["event"].synchronize()                   # the previous upload has left the pinned buffer
+            dev = device.index if device.index is not None else torch.cuda.current_device()
+            stream = torch.cuda.current_stream(device)
+            _lib.check(lib.yf_train_opt_multi_pinned(dev, self._kind, m, arrs[0], arrs[1], arrs[2], arrs[3], arrs[4], arrs[5], arrs[6], ng, og,
+                                                     ent["dev"].data_ptr(), ent["dev"].numel(), ent["host"].data_ptr(), int(upload),
+                                                     ctypes.c_void_p(stream.cuda_stream)))
+            if upload:
+                ent["key"] = ptrs
+                ent["event"] = torch.cuda.Event()
+                ent["event"].record(stream)
+        if any(first):
+            c["first"] = [0] * n
+        self._keep = gs                          # alive until the next step: the launch is asynchronous
 
 
-def train_step(model, model_loss, optimizer, imgs, targets):
-    """One iteration of train.py:111-132: returns the summed losses [total, x, y, w, h, conf, cls] (total a 0-dim tensor)."""
+class Adam(_MultiTensorOptimizer):
+    """`optim.Adam(model.parameters(), lr=lr0, betas=(0.9, 0.999), eps=1e-08)` (train.py:84) with the update done by one launch for all
+    tensors and groups.  `weight_decay` (per group, default 0) is torch's L2 form: the gradient becomes g + weight_decay p before the
+    moments, not AdamW; with 0 the update is bit for bit yf_train_adam_multi's.  State: torch's names (step, exp_avg, exp_avg_sq)."""
+    _kind = _lib.YF_OPT_ADAM
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0):
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+
+    def _state(self, q, group):
+        st = self.state[q]
+        if not st:
+            st["step"], st["exp_avg"], st["exp_avg_sq"] = 0, torch.zeros_like(q), torch.zeros_like(q)
+        return st["exp_avg"], st["exp_avg_sq"], 0
+
+    def _scalars(self, og, group, step):
+        og.lr, og.weight_decay, og.eps, og.step = float(group["lr"]), float(group.get("weight_decay", 0)), float(group["eps"]), int(step)
+        og.beta1, og.beta2 = float(group["betas"][0]), float(group["betas"][1])
+        if group.get("maximize") or group.get("amsgrad"):
+            raise ValueError("training.Adam: maximize and amsgrad are not implemented")
+
+
+class SGD(_MultiTensorOptimizer):
+    """`torch.optim.SGD(params, lr, momentum, weight_decay=.., nesterov=..)` with the update done by one launch for all tensors and
+    groups, bit for bit torch's arithmetic (csrc/yf_train_opt_kernels.h: tsgd_group_kernel).  State: torch's `momentum_buffer`, created at
+    a tensor's first step (which stores d, without reading the buffer); no state without momentum.  No dampening, no maximize."""
+    _kind = _lib.YF_OPT_SGD
+
+    def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False):
+        if dampening != 0:
+            raise ValueError("training.SGD: dampening is not implemented")
+        if momentum < 0 or lr < 0 or weight_decay < 0:
+            raise ValueError("training.SGD: lr, momentum and weight_decay must not be negative")
+        if nesterov and momentum <= 0:
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")         # torch's words
+        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov))
+
+    def _shape_key(self):
+        return tuple(g["momentum"] != 0 for g in self.param_groups)
+
+    def _state(self, q, group):
+        if group["momentum"] == 0:
+            return None, None, 0
+        st = self.state[q]
+        buf = st.get("momentum_buffer")
+        if buf is None:                                      # the first step writes it
+            st["momentum_buffer"] = buf = torch.empty_like(q)
+            return buf, None, 1
+        return buf, None, 0
+
+    def _scalars(self, og, group, step):
+        og.lr, og.weight_decay, og.momentum = float(group["lr"]), float(group.get("weight_decay", 0)), float(group["momentum"])
+        og.dampening, og.nesterov, og.maximize = float(group.get("dampening", 0)), int(bool(group.get("nesterov"))), int(bool(group.get("maximize")))
+        if og.dampening != 0 or og.maximize or (og.nesterov and og.momentum <= 0):
+            raise ValueError("training.SGD: dampening, maximize and nesterov without momentum are not implemented")
+
+
+def param_groups(model, weight_decay):
+    """yolov5's three optimizer groups (its train.py), by module type over named_modules(), in yolov5's order: BatchNorm2d weights (no
+    decay), every other module's .weight (Conv2d, ConvTranspose2d; `weight_decay`), every .bias (BatchNorm2d's included; no decay)."""
+    bn, w, b = [], [], []
+    for _, mod in model.named_modules():
+        if isinstance(getattr(mod, "bias", None), torch.nn.Parameter):
+            b.append(mod.bias)
+        if isinstance(mod, torch.nn.BatchNorm2d):
+            if isinstance(mod.weight, torch.nn.Parameter):
+                bn.append(mod.weight)
+        elif isinstance(getattr(mod, "weight", None), torch.nn.Parameter):
+            w.append(mod.weight)
+    ids = [id(p) for p in bn + w + b]
+    if len(set(ids)) != len(ids) or set(ids) != {id(p) for p in model.parameters()}:
+        raise ValueError("param_groups: a parameter that is no module's .weight or .bias, or one shared by two modules")
+    return [{"params": bn}, {"params": w, "weight_decay": weight_decay}, {"params": b}]
+
+
+def train_step(model, model_loss, optimizer, imgs, targets, branch_weight=None):
+    """One iteration of train.py:111-132: returns the summed losses [total, x, y, w, h, conf, cls] (total a 0-dim tensor).
+    `branch_weight` (a sequence, one factor per head; the reference sums the heads unweighted, :129-130): head i's seven values are
+    multiplied by branch_weight[i] before the sum, so the backward reaches head i scaled by it.  With factors other than 1 the heads
+    are taken back one at a time over the same tape and `p.grad` accumulates: every gradient is sum_i round(branch_weight[i] * g_i), g_i
+    head i's own gradient, added once -- the fp32 backward of a sum of head gradients is not the sum of their backwards (it rounds at
+    every accumulation), and only this form is linear in the heads to the last bit.  It costs one backward per head.  None and all-ones
+    are the reference's single backward, bit for bit."""
     optimizer.zero_grad()
     pred = model(imgs)
+    if branch_weight is not None and len(branch_weight) != len(pred):
+        raise ValueError("branch_weight has %d entries, the model %d heads" % (len(branch_weight), len(pred)))
+    weights = None if branch_weight is None else [float(v) for v in branch_weight]
     losses = [[] for _ in range(7)]
     for i, item_pred in enumerate(pred):
         for j, v in enumerate(model_loss[i](item_pred, targets)):
-            losses[j].append(v)
-    losses = [sum(v) for v in losses]
-    losses[0].backward()
+            losses[j].append(v if weights is None else v * weights[i])
+    per_head = weights is not None and any(v != 1.0 for v in weights)
+    heads = losses[0] if per_head else None                  # (held only when needed: live tensors shift the allocator's pattern, and a
+    losses = [sum(v) for v in losses]                        #  pass is replayed as a graph only when its pointers repeat)
+    if not per_head:
+        losses[0].backward()
+    else:
+        _KEEP_TAPE[0] += 1
+        try:
+            for h in heads[:-1]:
+                h.backward(retain_graph=True)
+        finally:
+            _KEEP_TAPE[0] -= 1
+        heads[-1].backward()                                 # the last one frees the tape
     optimizer.step()
     return losses
 
@@ -528,7 +654,8 @@ def cosine_factor(epoch, total_epochs):
     return ((1 + math.cos(epoch * math.pi / total_epochs)) / 2) * 0.8 + 0.2
 
 
-def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, logger=None, val_match="host"):
+def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, logger=None, val_match="host", optimizer=None,
+          branch_weight=False):
     """The reference's `train(params, device, tbwriter)` (train.py:44-160) with the iteration on the GPU kernels of this package.
     Same control flow and arithmetic: one YOLOLossV3 per stride (:50-53), the model from `pretrained_pth` or initialize_weights()
     (:58-65), DataLoader(batch_size, drop_last, shuffle) (:71-73), Adam(lr0, betas (0.9, 0.999), eps 1e-8) (:84), the cosine
@@ -540,6 +667,12 @@ def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, l
     image, (64, 6) boxes), batched by validation.collate_fn (= DetectDataset.collate_fn), or DetectDataset's whole-batch
     `__getitems__` (device images), which the collate passes through.  tbwriter may be None.  `val_match` is Validation's `match`
     ("host", the default, or "device": the TP / FP matching of get_mAP on the GPU, same result).
+    Opt-in, the three train_params keys the reference carries but does not read, with yolov5's meaning (the keys come from its hyp
+    files): `optimizer="adam"` = Adam(param_groups(model, weight_decay), lr0, betas=(momentum, 0.999)), `optimizer="sgd"` =
+    SGD(param_groups(model, weight_decay), lr0, momentum, nesterov=True) -- three groups, the decay on the convolution weights only;
+    `branch_weight=True` weights the heads' losses by train_params["branch_weight"] (train_step).  The defaults (None, False) read none of
+    the three: the reference's Adam on one group, the heads summed unweighted.  The warm-up and the cosine schedule are the reference's in
+    every case (yolov5's momentum / bias-lr warm-up is not part of this).
     Returns the trained model."""
     import logging
     import os
@@ -553,6 +686,13 @@ def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, l
         raise ValueError("pass train_dataset (e.g. dataset.DetectDataset over a Pascal-VOC tree, as train.py:68-76 builds it)")
     logger = logger or logging.getLogger(__name__)
     io, tp = params["io_params"], params["train_params"]
+    if optimizer not in (None, "adam", "sgd"):
+        raise ValueError("optimizer must be None (the reference's Adam), \"adam\" or \"sgd\", got %r" % (optimizer,))
+    head_weights = None
+    if branch_weight:
+        head_weights = [float(v) for v in tp["branch_weight"]]
+        if len(head_weights) != len(io["strides"]):
+            raise ValueError("train_params['branch_weight'] has %d entries, io_params['strides'] %d" % (len(head_weights), len(io["strides"])))
     save_path = io["save_path"]
     os.makedirs(save_path, exist_ok=True)
     total_epochs, batch_size = tp["total_epochs"], tp["batch_size"]
@@ -581,7 +721,12 @@ def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, l
                                 match=val_match) if val_dataset is not None else None
     batch_per_epoch = len(dataloader)
     num_warm = max(3 * batch_per_epoch, 1000)
-    optimizer = Adam(model.parameters(), lr=tp["lr0"], betas=(0.9, 0.999), eps=1e-08)
+    if optimizer is None:
+        optimizer = Adam(model.parameters(), lr=tp["lr0"], betas=(0.9, 0.999), eps=1e-08)
+    elif optimizer == "adam":
+        optimizer = Adam(param_groups(model, tp["weight_decay"]), lr=tp["lr0"], betas=(tp["momentum"], 0.999), eps=1e-08)
+    else:
+        optimizer = SGD(param_groups(model, tp["weight_decay"]), lr=tp["lr0"], momentum=tp["momentum"], nesterov=True)
 
     def lf(epoch):
         return cosine_factor(epoch, total_epochs)
@@ -604,7 +749,10 @@ def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, l
             if iteration <= num_warm:
                 for x in optimizer.param_groups:
                     x["lr"] = np.interp(iteration, [0, num_warm], [0.0, x["initial_lr"] * lf(epoch)])
-            losses = train_step(model, model_loss, optimizer, imgs, targets)
+            if head_weights is None:
+                losses = train_step(model, model_loss, optimizer, imgs, targets)
+            else:
+                losses = train_step(model, model_loss, optimizer, imgs, targets, head_weights)
             step_count += 1
             if step_count > 0 and step_count % 10 == 0:
                 _loss = losses[0].item()
