@@ -3,7 +3,9 @@
 // fused_block_kernel:  pw-expand(+ReLU) -> dw3x3(+ReLU) -> pw-project (+residual) (+ReLU)
 //   = the reference's BasicResBlock (src/model_training/model/yolo_fastest.py:52-66) and the un-named
 //   bottlenecks conv1_2/1_3/1_4, conv2_2/2_3/3_1, conv3_2/3_3/3_4, conv3_5/3_6/4_1, conv4_2/4_3/5_1 (:80-118);
-//   with PRE it also evaluates conv0 (dense 3x3 s2 on the 1-channel input, :78) in front of the expansion.
+//   with PRE it also evaluates conv0 (dense 3x3 s2 on the 1-channel input, :78) in front of the expansion.  A 1-channel stem first
+//   copies the input patch of its region into LDS (f32 planes, u8 frames or 2x u8 frames alike: floats, the pre-process applied once
+//   per input pixel) and reads conv0's taps there; the patch shares E's storage.  2 .. 4 input channels fetch every tap from memory.
 //
 // One workgroup = one spatial tile of one frame.  Data flow per tile:
 //   HBM --(narrow NHWC input tile + halo, 16-B loads)--> registers --expand--> LDS (chunk of EC, channel pairs interleaved:
@@ -61,7 +63,8 @@ __global__ void __launch_bounds__(TYB* TXB) fused_block_kernel(FbArgs a)
     __shared__ __attribute__((aligned(16))) float E[EC * PLANE];
     // u8 input (PRE): (v - 128) / 255 of the 256 possible pixel values (a 2x2 box mean is an integer 0..255 too).  The IEEE division is
     // ~10 VALU instructions and sat in the loop nine times per region pixel (stem 98 us from u8 against 67 us from f32, batch 256); one
-    // division per thread here and an LDS read per tap give the same bits (torch's `(img - 128.0) / 255.0`, detect.py:124)
+    // division per thread here and an LDS read per tap (STAGE: per input pixel) give the same bits (torch's `(img - 128.0) / 255.0`,
+    // detect.py:124)
     __shared__ float LUT[PRE ? 256 : 1];
 
     const int b = xcd_tile(blockIdx.x, gridDim.x);
@@ -70,11 +73,90 @@ __global__ void __launch_bounds__(TYB* TXB) fused_block_kernel(FbArgs a)
     const int wave = wave_id(), lane = threadIdx.x & 63;
     const int tyb = threadIdx.x / TXB, txb = threadIdx.x % TXB;
 
+    // STAGE (the stem of a 1-channel model): conv0's taps come from a copy of the input patch in LDS.  The region's RH x RW pixels read
+    // input rows 2 * iy0 - 1 .. + 2 * RH and columns 2 * ix0 - 1 .. + 2 * RW: each input pixel up to 9/4 times, and fetched per tap every read
+    // had its own address arithmetic, bounds test and branch (9 global_load_dword per item under 9 exec masks, an exposed L2 round trip
+    // per item; from u8 frames 18 loads and 9 table look-ups).  Staged, a unit of four pixels (16 bytes of an f32 plane, 4 bytes of a u8
+    // frame, 2 x 8 bytes of a 2x u8 frame) is loaded once under one predicate -- a unit lies wholly inside its row or wholly outside,
+    // and the address of one outside may lie in front of the first frame or behind the last: it is never formed (the load goes to the
+    // frame's first unit, not under a branch: a branch per load made the compiler wait for each load before the next); zeros take its
+    // place, conv0's padding -- and the table look-up (and the 2x2 box mean) runs once per input pixel.  The patch is stored as floats in two
+    // planes per row, [even columns: tap kx = 1 | odd columns: taps kx = 0 and 2] (the split k19r_kernel uses for its slice): a tap's
+    // 64 lanes read consecutive dwords at an immediate offset from ONE per-lane base.  All loads are issued before the first LDS write.
+    constexpr bool STAGE = PRE && C0 == 1;
+    constexpr int PR = 2 * RH + 1, PU = (2 * RW + 5) / 4, PP = 4 * PU;   // patch rows, 4-pixel units per row, row pitch (floats)
+    constexpr int NU = PR * PU, UPT = STAGE ? (NU + NT - 1) / NT : 1;
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+    typedef u32x4 __attribute__((aligned(4))) u32x4_u;   // the caller's frames: no alignment beyond the element's is promised
+    typedef u32x2 __attribute__((aligned(1))) u32x2_u;
+    typedef unsigned __attribute__((aligned(1))) u32_u;
+    u32x4 raw[UPT];
+    bool uok[UPT];
+    if constexpr (STAGE) {
+        static_assert(CEXP == EC && NCG == 1 && PE == 1, "the patch is read before the one chunk's expansion overwrites it");
+        static_assert(PR * PP <= EC * PLANE && 2 * PU >= RW + 2 && (TW * S) % 2 == 0, "patch layout");
+        static_assert(RWP > RW && (TXB - 1) * BW * S + WC <= RW, "a pad column behind every E row that no depthwise window reads");
+        const int IH = 2 * a.H, IW = 2 * a.W;              // the net input's size
+        const int py0 = 2 * iy0 - 1, px0 = 2 * ix0 - 2;   // input row / column of the patch's first unit (px0 is a multiple of 4)
+        int uy[UPT], ux[UPT];   // the unit's first pixel within frame n; a unit outside the frame reads the frame's first unit instead, as mres_stage does
+#pragma unroll
+        for (int k = 0; k < UPT; ++k) {
+            const int u = threadIdx.x + k * NT, r = u / PU, yy = py0 + r, xx = px0 + 4 * (u - r * PU);
+            uok[k] = u < NU && yy >= 0 && yy < IH && xx >= 0 && xx < IW;
+            uy[k] = uok[k] ? yy : 0; ux[k] = uok[k] ? xx : 0;
+        }
+        if (!a.in_u8) {
+            const float* __restrict__ src = a.in + (long)n * IH * IW;
+#pragma unroll
+            for (int k = 0; k < UPT; ++k) raw[k] = *reinterpret_cast<const u32x4_u*>(src + (uy[k] * IW + ux[k]));
+        } else if (!a.u8_down2) {
+            const uint8_t* __restrict__ src = a.in_u8 + (long)n * IH * IW;
+#pragma unroll
+            for (int k = 0; k < UPT; ++k) raw[k] = u32x4{*reinterpret_cast<const u32_u*>(src + (uy[k] * IW + ux[k])), 0u, 0u, 0u};
+        } else {   // the 2x2 source blocks of the unit's four pixels: 8 bytes of two source rows
+            const uint8_t* __restrict__ src = a.in_u8 + (long)n * 4 * IH * IW;
+#pragma unroll
+            for (int k = 0; k < UPT; ++k) {
+                const uint8_t* q = src + ((long)uy[k] * (2 * IW) + ux[k]) * 2;
+                const u32x2 r0 = *reinterpret_cast<const u32x2_u*>(q), r1 = *reinterpret_cast<const u32x2_u*>(q + 2 * IW);
+                raw[k] = u32x4{r0.x, r0.y, r1.x, r1.y};
+            }
+        }
+    }
     if constexpr (PRE) {
         if (a.in_u8)
             for (int i = threadIdx.x; i < 256; i += NT) LUT[i] = ((float)i - 128.0f) / 255.0f;
     }
-    __syncthreads();   // orders the LUT fill before the expansion reads it
+    __syncthreads();   // orders the LUT fill before the look-ups
+    if constexpr (STAGE) {
+        // Detect_YOLO.__pre_process (src/detect.py:115-124) for u8 frames: optional exact-2x box mean (a+b+c+d+2)>>2, then (v-128)/255;
+        // conv0 zero-pads the NORMALISED tensor.  The patch lives in E's storage: the wave's conv0 results wait in registers while a
+        // barrier separates the last tap read from the first write of the expansion.
+#pragma unroll
+        for (int k = 0; k < UPT; ++k) {
+            const int u = threadIdx.x + k * NT, r = u / PU, cu = u - r * PU;
+            float v[4];
+            if (!a.in_u8) {
+                const float4 f = __builtin_bit_cast(float4, raw[k]);
+                v[0] = uok[k] ? f.x : 0.f; v[1] = uok[k] ? f.y : 0.f; v[2] = uok[k] ? f.z : 0.f; v[3] = uok[k] ? f.w : 0.f;
+            } else if (!a.u8_down2) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) v[j] = uok[k] ? LUT[(raw[k].x >> (8 * j)) & 255u] : 0.f;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const unsigned t0 = raw[k][j / 2] >> (16 * (j & 1)), t1 = raw[k][2 + j / 2] >> (16 * (j & 1));
+                    v[j] = uok[k] ? LUT[((t0 & 255u) + ((t0 >> 8) & 255u) + (t1 & 255u) + ((t1 >> 8) & 255u) + 2u) >> 2] : 0.f;
+                }
+            }
+            if (u < NU) {
+                *reinterpret_cast<float2*>(E + r * PP + 2 * cu) = make_float2(v[0], v[2]);            // even columns, one slot in
+                *reinterpret_cast<float2*>(E + r * PP + 2 * PU + 2 * cu) = make_float2(v[1], v[3]);   // odd columns
+            }
+        }
+        __syncthreads();
+    }
 
     fb_f32x2 acc2[BH * BW][COUT / 2];   // projection accumulators, output-channel pairs
 #pragma unroll
@@ -112,6 +194,56 @@ __global__ void __launch_bounds__(TYB* TXB) fused_block_kernel(FbArgs a)
     for (int ch = 0; ch < CEXP / EC; ++ch) {
         const cfloat* __restrict__ wc = (const cfloat*)(a.wp + ch * CHF);  // this chunk's weights (wave-uniform, constant address space -> scalar loads)
         // ---------------- expansion of the halo'd region into LDS: PE pixels per lane per item ----------------
+        if constexpr (STAGE) {
+            // two passes over the wave's MAXI items (an item = 64 region pixels): conv0 from the patch, then -- the patch is dead -- the
+            // expansion into E.  The compiler still fetches a pass's weights once per item (every item sits under its own wave-uniform
+            // guard); with the guard of the first items dropped it keeps them across items and spills SGPRs to VGPR lanes, ~100
+            // v_readlane / v_writelane per wave (profiles/stem_lds_taps_ab.txt)
+            float x0[MAXI][CIN];
+            int dst0[MAXI];       // the pixel's E offset; lanes beyond the region write their zeros into a pad column (RW .. RWP - 1: never read)
+            bool in0[MAXI];
+#pragma unroll
+            for (int it = 0; it < MAXI; ++it) {
+                if (wave + it * NW >= NITEM) continue;
+                const int rp = (wave + it * NW) * 64 + lane, rpc = rp < NRP ? rp : 0;
+                const int ry = rpc / RW, rx = rpc - ry * RW, iy = iy0 + ry, ix = ix0 + rx;
+                in0[it] = rp < NRP && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
+                dst0[it] = (ry * RWP + (rp < NRP ? rx : RW)) * 2;
+                // conv0: 3x3 stride 2 pad 1 on the net input (+ReLU); v[ky * 3 + kx].  A pixel outside the image reads whatever its taps
+                // hold: its expansion is replaced by the depthwise conv's zero padding below
+                const float* pt = E + 2 * ry * PP + rx;
+                float v[9];
+#pragma unroll
+                for (int ky = 0; ky < 3; ++ky) {
+                    v[ky * 3] = pt[ky * PP + 2 * PU]; v[ky * 3 + 1] = pt[ky * PP + 1]; v[ky * 3 + 2] = pt[ky * PP + 2 * PU + 1];
+                }
+#pragma unroll
+                for (int c = 0; c < CIN; c += 2) {
+                    fb_f32x2 s2 = *(const cfloat2*)(const cfloat*)(a.b0 + c);
+#pragma unroll
+                    for (int t = 0; t < 9; ++t)
+                        s2 = __builtin_elementwise_fma(fb_f32x2{v[t], v[t]}, *(const cfloat2*)(const cfloat*)(a.w0 + t * CIN + c), s2);
+                    x0[it][c] = fmaxf(s2[0], 0.f); x0[it][c + 1] = fmaxf(s2[1], 0.f);
+                }
+            }
+            __syncthreads();   // every wave has read its taps: E may be written
+#pragma unroll
+            for (int it = 0; it < MAXI; ++it) {
+                if (wave + it * NW >= NITEM) continue;
+                fb_f32x2 e2[CG / 2];
+#pragma unroll
+                for (int j = 0; j < CG; j += 2) e2[j / 2] = *(const cfloat2*)(wc + O_B1 + j);
+#pragma unroll
+                for (int k = 0; k < CIN; ++k)
+#pragma unroll
+                    for (int j = 0; j < CG; j += 2)
+                        e2[j / 2] = __builtin_elementwise_fma(fb_f32x2{x0[it][k], x0[it][k]}, *(const cfloat2*)(wc + k * EC + j), e2[j / 2]);
+#pragma unroll
+                for (int j = 0; j < CG; j += 2)
+                    *reinterpret_cast<float2*>(E + dst0[it] + j * PLANE) =
+                        make_float2(in0[it] ? fmaxf(e2[j / 2][0], 0.f) : 0.f, in0[it] ? fmaxf(e2[j / 2][1], 0.f) : 0.f);
+            }
+        } else {
 #pragma unroll
         for (int it = 0; it < (HOIST ? MAXI : 1); ++it)   // HOIST: item it of this wave, unrolled so that xh[it] is a register; else the plain item loop
         for (int item = HOIST ? wave + it * NW : wave; item < (HOIST ? (wave + it * NW < NITEM ? wave + it * NW + 1 : 0) : NITEM); item += NW) {
@@ -156,13 +288,8 @@ __global__ void __launch_bounds__(TYB* TXB) fused_block_kernel(FbArgs a)
 #pragma unroll
                             for (int t = 0; t < 9 * C0; ++t) {
                                 const uint8_t* q = src + yo[t / C0 / 3] + xo[(t / C0) % 3] + (C0 - 1 - t % C0);
-                                if constexpr (C0 == 1) {   // the two pixels of a row are adjacent bytes: one 16-bit load
-                                    r0[t] = *reinterpret_cast<const unsigned short*>(q);
-                                    r1[t] = *reinterpret_cast<const unsigned short*>(q + sw);
-                                } else {
-                                    r0[t] = (unsigned)q[0] | ((unsigned)q[C0] << 8);
-                                    r1[t] = (unsigned)q[sw] | ((unsigned)q[sw + C0] << 8);
-                                }
+                                r0[t] = (unsigned)q[0] | ((unsigned)q[C0] << 8);
+                                r1[t] = (unsigned)q[sw] | ((unsigned)q[sw + C0] << 8);
                             }
                             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -252,6 +379,7 @@ __global__ void __launch_bounds__(TYB* TXB) fused_block_kernel(FbArgs a)
                                        : make_float2(inimg[p] ? fmaxf(e[p][j], 0.f) : 0.f, inimg[p] ? fmaxf(e[p][j + 1], 0.f) : 0.f);
                 }
         }
+        }
         __syncthreads();
         // ---------------- depthwise 3x3 from LDS + projection into registers ----------------
         // NOT fully unrolled: unrolled, the scalar loads of all EC channels' weights are hoisted to the top and, with the
@@ -340,7 +468,8 @@ static int launch_fb_t(FbArgs a, int N, hipStream_t s)
     return 0;
 }
 
-// (Staging the input tile in LDS was measured slower at these shapes: it costs occupancy and LDS bandwidth, the L2-served loads were already hidden.)
+// (Staging the NHWC block input in LDS was measured slower at these shapes: one use per pixel, it costs occupancy and LDS bandwidth, the
+//  L2-served loads were already hidden.  The stem's net input is another matter: nine uses per pixel, staged in E's own storage -- STAGE above.)
 //     cin cexp cout S  res    relu   pre    TYB TXB BH BW EC CG PE
 #define YF_FB_SHAPES(FB)                                                                                                 \
     FB(8, 8, 4, 1, false, false, true, 16, 16, 1, 2, 8, 8, 1)            /* conv0 + conv1_2/1_3/1_4      @ H/2  */          \
