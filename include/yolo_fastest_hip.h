@@ -408,6 +408,32 @@ int yf_augment_warp_u8(int device, const uint8_t *d_src, int src_h, int src_w, i
  * on the mixture.  No allocation or synchronisation; stream-ordered; capturable. */
 int yf_augment_mix_u8(int device, const uint8_t *d_frames, int n_frames, int N, int h, int w, int c, const int *d_first, const int *d_second,
                       const int *d_params, const double *d_warp, const double *d_ratio, uint8_t *d_u8, float *d_x, void *stream);
+/* yolov5's mosaic over frames that are ALREADY resized (and gray): per output frame four h x w tiles around a centre (xc, yc) on a 2h x 2w
+ * canvas of 114s, that canvas warped and cropped back to h x w as yf_augment_warp_u8 warps a frame, then its blur and flips:
+ *     x = flipud?(fliplr?(GaussianBlur_k(warp(canvas(TL, TR, BL, BR, xc, yc)))))
+ * The canvas is never in memory: each bilinear tap is resolved to one of the four tiles, or to 114.
+ *   d_frames  u8 [n_frames, h, w, c], c 1 or 3: what yf_augment_u8 with all-zero parameters writes to its u8 output
+ *   d_tiles   int32 [N, 4]: the tiles top-left, top-right, bottom-left, bottom-right.  d_tiles[n][1] < 0: output n is NOT a mosaic but
+ *             frame d_tiles[n][0] with yf_augment_warp_u8's bytes (bits 10 / 11 honoured, d_centre not read); otherwise all four are
+ *             read.  d_tiles[n][0] outside 0 .. n_frames - 1, or for a mosaic any of the other three, leaves output frame n untouched;
+ *             nothing is read out of bounds.  The same frame may appear in several tiles.
+ *   d_centre  int32 [N, 2]: (xc, yc); a mosaic whose centre is outside 0 <= xc <= 2w, 0 <= yc <= 2h leaves its output untouched
+ *   canvas    yolov5's load_mosaic with s * 2 replaced by 2w / 2h: canvas[y1a:y2a, x1a:x2a] = tile[y1b:y2b, x1b:x2b], else 114, with
+ *               TL  a = (max(xc - w, 0), max(yc - h, 0), xc, yc)                  b = (w - (x2a - x1a), h - (y2a - y1a), w, h)
+ *               TR  a = (xc, max(yc - h, 0), min(xc + w, 2w), yc)                 b = (0, h - (y2a - y1a), min(w, x2a - x1a), h)
+ *               BL  a = (max(xc - w, 0), yc, xc, min(2h, yc + h))                 b = (w - (x2a - x1a), 0, w, min(y2a - y1a, h))
+ *               BR  a = (xc, yc, min(xc + w, 2w), min(2h, yc + h))                b = (0, 0, min(w, x2a - x1a), min(y2a - y1a, h))
+ *   warp      Pillow's Image.transform((w, h), AFFINE | PERSPECTIVE, coefficients, BILINEAR, fillcolor = 114) of that canvas, in IEEE
+ *             double with one rounding per operation as yf_augment_warp_u8: 114 if sx < 0, sx >= 2w, sy < 0 or sy >= 2h; columns and
+ *             rows clamped to 2w - 1 / 2h - 1; a footprint on a seam mixes two to four tiles, or a tile and 114
+ *   d_params  int32 [N]: yf_augment_warp_u8's bits (k, 8 fliplr, 9 flipud, 10 warp, 11 perspective); for a mosaic bit 10 is not
+ *             consulted: it always samples through its coefficients
+ *   d_warp    float64 [N, 8]: a0 .. a7 of the output -> canvas map (output -> frame for a frame that is no mosaic, read with bit 10)
+ *   outputs   as yf_augment_warp_u8's (at least one; may not overlap d_frames)
+ * Bad arguments are refused with YF_E_INVALID before the GPU is touched.  ONE launch on `stream`; the blur's reflect-101 border is taken
+ * on the warped image.  No allocation or synchronisation; stream-ordered; capturable. */
+int yf_augment_mosaic_u8(int device, const uint8_t *d_frames, int n_frames, int N, int h, int w, int c, const int *d_tiles,
+                         const int *d_centre, const int *d_params, const double *d_warp, uint8_t *d_u8, float *d_x, void *stream);
 /* cv::resize's INTER_LINEAR tables for one (source, destination) size pair into caller-owned device memory: d_xtab int4 [dst_w],
  * d_ytab int4 [dst_h] (16 bytes each entry).  One small kernel on `stream`, no allocation or synchronisation. */
 int yf_cv_resize_tables(int device, int src_h, int src_w, int dst_h, int dst_w, void *d_xtab, void *d_ytab, void *stream);

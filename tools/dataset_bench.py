@@ -13,7 +13,12 @@
                                                       warped with perspective draws) beside the warp call and the plain launch at batch 16
                                                       and 512, in interleaved rounds: median and spread of each
     python tools/dataset_bench.py --train --mixup     train() at batch 16, cache="device", geometric keys active: DetectDataset(mixup=True)
-                                                      with mixup 0.5 and 0.0 beside the flag-unset data set and the no-data loop"""
+                                                      with mixup 0.5 and 0.0 beside the flag-unset data set and the no-data loop
+    python tools/dataset_bench.py --kernel --mosaic   the mosaic call (yf_augment_mosaic_u8 over resized frames: every output a mosaic of
+                                                      four frames under a perspective draw) beside the warp call and the plain launch at
+                                                      batch 16 and 512, in interleaved rounds: median and spread of each
+    python tools/dataset_bench.py --train --mosaic    train() at batch 16, cache="device", geometric keys active: DetectDataset(mosaic=True)
+                                                      with mosaic 1.0 and 0.0 beside the flag-unset data set and the no-data loop"""
 import argparse
 import csv
 import glob
@@ -38,6 +43,7 @@ ap.add_argument("--kernel", action="store_true")
 ap.add_argument("--profile", action="store_true")
 ap.add_argument("--train", action="store_true")
 ap.add_argument("--mixup", action="store_true", help="the mixup variant of --kernel / --train")
+ap.add_argument("--mosaic", action="store_true", help="the mosaic variant of --kernel / --train")
 ap.add_argument("--reps", type=int, default=50)
 ap.add_argument("--steps", type=int, default=30)
 ap.add_argument("--rounds", type=int, default=3)
@@ -179,6 +185,77 @@ def kernel_bench_mixup():
     return res
 
 
+def kernel_bench_mosaic():
+    """The plain launch, the warp call (two launches: resize + warp) and the mosaic call (one launch over the warp call's resized frames;
+    with the resize launch in front of it as well), `--rounds` interleaved rounds of `--reps` launches each."""
+    from yolo_fastest_amd.dataset import DetectDataset
+    lib = _lib.lib()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    res = {}
+    H, W = 256, 320
+    for N in (16, 512):
+        src = torch.randint(0, 256, (N, 512, 640, 3), dtype=torch.uint8, device=dev)
+        rng = random.Random(0)
+        prm = []
+        for _ in range(N):
+            k = (7 if rng.random() < 0.4 else 3) if rng.random() < 0.3 else 0
+            prm.append(k | (int(rng.random() < 0.5) << 8))
+        draw = DetectDataset.__new__(DetectDataset)                    # the draws alone: no files behind it
+        draw.input_shape = [H, W, 1]
+        for key in ("degrees", "translate", "scale", "shear", "perspective"):
+            setattr(draw, key, GEOMETRIC[key])
+        random.seed(0)
+        coeffs = np.stack([draw._draw_warp()[2] for _ in range(N)])
+        canvas_coeffs = np.stack([draw._draw_warp(mosaic=True)[2] for _ in range(N)])
+        centres = [[int(random.uniform(W // 2, 2 * W - W // 2)), int(random.uniform(H // 2, 2 * H - H // 2))] for _ in range(N)]
+        tiles = [[n] + random.choices(range(N), k=3) for n in range(N)]
+        prm2 = [p | (int(rng.random() < GEOMETRIC["flipud"]) << 9) | (3 << 10) for p in prm]
+        d_prm = torch.tensor(prm, dtype=torch.int32, device=dev)
+        d_zero = torch.zeros((N,), dtype=torch.int32, device=dev)
+        d_prm2 = torch.tensor(prm2, dtype=torch.int32, device=dev)
+        d_warp = torch.tensor(coeffs, dtype=torch.float64).to(dev)
+        d_warp2 = torch.tensor(canvas_coeffs, dtype=torch.float64).to(dev)
+        d_tiles = torch.tensor(tiles, dtype=torch.int32, device=dev)
+        d_centre = torch.tensor(centres, dtype=torch.int32, device=dev)
+        scratch = torch.empty((N, H, W, 1), dtype=torch.uint8, device=dev)
+        x = torch.empty((N, 1, H, W), dtype=torch.float32, device=dev)
+        head = (dev.index, src.data_ptr(), 512, 640, 3, None, N, N, None, None, H, W, 1, 15)
+
+        def plain():
+            _lib.check(lib.yf_augment_u8(*head, d_prm.data_ptr(), None, x.data_ptr(), stream))
+
+        def warp():
+            _lib.check(lib.yf_augment_warp_u8(*head, d_prm2.data_ptr(), d_warp.data_ptr(), scratch.data_ptr(), None, x.data_ptr(), stream))
+
+        def mosaic():
+            _lib.check(lib.yf_augment_mosaic_u8(dev.index, scratch.data_ptr(), N, N, H, W, 1, d_tiles.data_ptr(), d_centre.data_ptr(),
+                                                d_prm2.data_ptr(), d_warp2.data_ptr(), None, x.data_ptr(), stream))
+
+        def resize_mosaic():
+            _lib.check(lib.yf_augment_u8(*head, d_zero.data_ptr(), scratch.data_ptr(), None, stream))
+            mosaic()
+        calls = {"plain": plain, "warp": warp, "mosaic": mosaic, "resize+mosaic": resize_mosaic}
+        for fn in calls.values():                                      # warp first: it fills the scratch the mosaic call reads
+            for _ in range(5):
+                fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ms = {n: [] for n in calls}
+        for _ in range(a.rounds):
+            for n, fn in calls.items():
+                torch.cuda.synchronize()
+                e0.record()
+                for _ in range(a.reps):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                ms[n].append(e0.elapsed_time(e1) / a.reps)
+        res[N] = {n: {"median_ms": round(float(np.median(v)), 4), "rounds_ms": [round(x_, 4) for x_ in v]} for n, v in ms.items()}
+        for n, v in ms.items():
+            print("batch %d, %s: %.4f ms (median of %d rounds of %d launches: %s) = %.2f x the plain launch"
+                  % (N, n, float(np.median(v)), len(v), a.reps, ["%.4f" % x_ for x_ in v], np.median(v) / np.median(ms["plain"])))
+    return res
+
+
 def profile():
     out = a.out or tempfile.mkdtemp(prefix="dataset_bench_")
     os.makedirs(out, exist_ok=True)
@@ -229,6 +306,10 @@ def train_bench():
         configs = [("cache=device", aug, dict(cache="device")), ("geometric cache=device", active, dict(cache="device")),
                    ("geometric mixup=0.0 cache=device", dict(active, mixup=0.0), dict(cache="device", mixup=True)),
                    ("geometric mixup=0.5 cache=device", dict(active, mixup=0.5), dict(cache="device", mixup=True))]
+    if a.mosaic:                                                         # one build: the flag unset, set with 0.0, set with 1.0
+        configs = [("cache=device", aug, dict(cache="device")), ("geometric cache=device", active, dict(cache="device")),
+                   ("geometric mosaic=0.0 cache=device", dict(active, mosaic=0.0), dict(cache="device", mosaic=True)),
+                   ("geometric mosaic=1.0 cache=device", dict(active, mosaic=1.0), dict(cache="device", mosaic=True))]
     for name, params, kw in configs:
         ds = DetectDataset(io["input_shape"], io["origin_img_shape"], None, aug_params=params, device=dev, **kw)
         loaders[name] = DataLoader(ds, batch_size=B, num_workers=0, drop_last=True, pin_memory=True, shuffle=True, collate_fn=val.collate_fn)
@@ -266,6 +347,10 @@ def train_bench():
         print("mixup 0.5 / mixup 0.0 = %.3f; mixup 0.0 / flag unset = %.3f" % (
             np.median(res["geometric mixup=0.5 cache=device"]) / np.median(res["geometric mixup=0.0 cache=device"]),
             np.median(res["geometric mixup=0.0 cache=device"]) / np.median(res["geometric cache=device"])))
+    if a.mosaic:
+        print("mosaic 1.0 / mosaic 0.0 = %.3f; mosaic 0.0 / flag unset = %.3f" % (
+            np.median(res["geometric mosaic=1.0 cache=device"]) / np.median(res["geometric mosaic=0.0 cache=device"]),
+            np.median(res["geometric mosaic=0.0 cache=device"]) / np.median(res["geometric cache=device"])))
     for n in ("cache=device", "decode=device"):
         if "geometric " + n in res and n in res and "cache=None" in res:
             print("geometric %s / %s = %.3f, / cache=None (decode=host) = %.3f" % (
@@ -276,6 +361,8 @@ def train_bench():
 out = {}
 if a.kernel and a.profile:
     profile()
+elif a.kernel and a.mosaic:
+    out["kernel_mosaic"] = kernel_bench_mosaic()
 elif a.kernel and a.mixup:
     out["kernel_mixup"] = kernel_bench_mixup()
 elif a.kernel:

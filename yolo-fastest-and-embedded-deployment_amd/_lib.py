@@ -135,6 +135,7 @@ _SIGS = {
                                       _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
                                       _c.c_void_p]),
     "yf_augment_mix_u8": (_c.c_int, [_c.c_int, _c.c_void_p] + [_c.c_int] * 5 + [_c.c_void_p] * 8),
+    "yf_augment_mosaic_u8": (_c.c_int, [_c.c_int, _c.c_void_p] + [_c.c_int] * 5 + [_c.c_void_p] * 7),
     "yf_cv_resize_tables": (_c.c_int, [_c.c_int] * 5 + [_c.c_void_p] * 3),
     "yf_jpeg_pack": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_int),
                                 _c.POINTER(_c.c_int)]),

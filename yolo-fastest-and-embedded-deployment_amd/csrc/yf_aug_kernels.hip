@@ -13,7 +13,8 @@
 //     pass is exact in uint16, dst = (sum_y k_y * row_y + 2^15) >> 16; BORDER_REFLECT_101 on all four sides; every channel on its own.
 //   flip: after the blur (the taps and reflect-101 are symmetric, so the two commute; tests/test_gpu_dataset.py shows it).
 // yf_augment_warp_u8 adds yolov5's geometric warp between the resize and the blur (warp_kernel, a second launch over the resized frames);
-// yf_augment_mix_u8 adds yolov5's mixup of two resized, warped frames before the blur (mix_kernel, one launch; see below).
+// yf_augment_mix_u8 adds yolov5's mixup of two resized, warped frames before the blur (mix_kernel, one launch; see below);
+// yf_augment_mosaic_u8 yolov5's mosaic of four resized frames, warped and cropped back to the frame size (mosaic_kernel, one launch).
 // One workgroup owns `tr` destination rows of one frame: it stages those rows plus a 3-row halo of the resized (gray) image in LDS (computed
 // straight from the source bytes, as cv_pre_kernel does), runs the row pass into a uint16 LDS buffer and the column pass out of it.  A frame
 // whose k is 0 stages no halo and skips both passes (k is uniform per workgroup).  Integer arithmetic only on the byte path.
@@ -254,11 +255,13 @@ struct WarpArgs {
 };
 constexpr int WARP_FILL = 114;    // yolov5's border value, every channel
 
-// One bilinear sample, Pillow's arithmetic (src/libImaging/Geometry.c: affine_transform / perspective_transform + bilinear_filter8) in
-// IEEE double, one rounding per operation: no contraction into FMAs, and the correctly rounded division (no fast-math).  -> false: fill.
-template <int C>
-__device__ __forceinline__ bool warp_sample(const uint8_t* __restrict__ img, int dh, int dw, const double (&m)[8], bool persp, int x, int y,
-                                            int (&v)[C])
+// Pillow's arithmetic (src/libImaging/Geometry.c: affine_transform / perspective_transform + bilinear_filter8) in IEEE double, one rounding
+// per operation: no contraction into FMAs, and the correctly rounded division (no fast-math).  It stands once, in two halves that
+// warp_sample (a frame in memory) and canvas_sample (the mosaic's virtual canvas) share.
+// Half 1, coordinates and weights: the source position of destination pixel (x, y) in an sw x sh image -> false: fill (a NaN fills as
+// well); otherwise the top-left tap (x0, y0), -1 .. sw - 1 and -1 .. sh - 1, and the two weights.
+__device__ __forceinline__ bool warp_coords(int sh, int sw, const double (&m)[8], bool persp, int x, int y, int& x0, int& y0, double& ddx,
+                                            double& ddy)
 {
 #pragma clang fp contract(off)
     const double xin = x + 0.5, yin = y + 0.5;
@@ -269,12 +272,38 @@ __device__ __forceinline__ bool warp_sample(const uint8_t* __restrict__ img, int
         sx = sx / den;
         sy = sy / den;
     }
-    if (!(sx >= 0.0 && sx < dw && sy >= 0.0 && sy < dh)) return false;    // a NaN fills as well
+    if (!(sx >= 0.0 && sx < sw && sy >= 0.0 && sy < sh)) return false;    // a NaN fills as well
     sx -= 0.5;
     sy -= 0.5;
     const double fx = floor(sx), fy = floor(sy);
-    const double ddx = sx - fx, ddy = sy - fy;
-    const int x0 = (int)fx, y0 = (int)fy;                                 // -1 .. dw - 1, -1 .. dh - 1
+    ddx = sx - fx;
+    ddy = sy - fy;
+    x0 = (int)fx;
+    y0 = (int)fy;
+    return true;
+}
+
+// Half 2, the blend of one channel: v1 = warp_lerp on row y0, v2 the same on row y0 + 1 if that row exists, else v1; warp_finish.
+__device__ __forceinline__ double warp_lerp(int a, int b, double ddx)
+{
+#pragma clang fp contract(off)
+    return (double)a + (double)(b - a) * ddx;
+}
+
+__device__ __forceinline__ int warp_finish(double v1, double v2, double ddy)
+{
+#pragma clang fp contract(off)
+    return (int)(v1 + (v2 - v1) * ddy);                                   // (uint8)v: a truncation; 0 <= v <= 255
+}
+
+// One bilinear sample of a frame in memory.  -> false: fill.
+template <int C>
+__device__ __forceinline__ bool warp_sample(const uint8_t* __restrict__ img, int dh, int dw, const double (&m)[8], bool persp, int x, int y,
+                                            int (&v)[C])
+{
+    int x0, y0;
+    double ddx, ddy;
+    if (!warp_coords(dh, dw, m, persp, x, y, x0, y0, ddx, ddy)) return false;
     const int xa = max(x0, 0), xb = min(x0 + 1, dw - 1);
     const uint8_t* const r0 = img + ((long)max(y0, 0) * dw) * C;
     const bool below = y0 + 1 < dh;                                       // y0 + 1 >= 0 always
@@ -282,13 +311,13 @@ __device__ __forceinline__ bool warp_sample(const uint8_t* __restrict__ img, int
 #pragma unroll
     for (int c = 0; c < C; ++c) {
         const int a0 = r0[xa * C + c], b0 = r0[xb * C + c];
-        const double v1 = (double)a0 + (double)(b0 - a0) * ddx;
+        const double v1 = warp_lerp(a0, b0, ddx);
         double v2 = v1;
         if (below) {
             const int a1 = r1[xa * C + c], b1 = r1[xb * C + c];
-            v2 = (double)a1 + (double)(b1 - a1) * ddx;
+            v2 = warp_lerp(a1, b1, ddx);
         }
-        v[c] = (int)(v1 + (v2 - v1) * ddy);                               // (uint8)v: a truncation; 0 <= v <= 255
+        v[c] = warp_finish(v1, v2, ddy);
     }
     return true;
 }
@@ -476,6 +505,169 @@ __global__ void __launch_bounds__(256) mix_kernel(MixArgs a)
     blur_cols_store<C>(tile, hb, taps, k, n, dy0, rows, a.dh, a.dw, a.pitch, fliplr, flipud, a.u8, a.x);
 }
 
+// ---- mosaic (yf_augment_mosaic_u8): one launch over frames that are already resized (and gray) ----
+struct MosaicArgs {
+    const uint8_t* frames;        // [n_frames, dh, dw, C] resized frames (aug_kernel without parameters): the tiles, all dh x dw
+    int n_frames, n, dh, dw;
+    const int* tiles;             // [n, 4] top-left, top-right, bottom-left, bottom-right; [n][1] < 0: no mosaic, frame [n][0] as warp_kernel
+    const int* centre;            // [n, 2] (xc, yc) on the 2 dw x 2 dh canvas (read for mosaics)
+    const int* params;            // [n] WarpArgs' bits; a mosaic always samples through its coefficients (bit 10 is not consulted)
+    const double* warp;           // [n, 8]
+    uint8_t* u8;
+    float* x;
+    int tr, pitch;
+};
+
+// yolov5's load_mosaic canvas, never in memory: four dh x dw tiles around (xc, yc) on a 2 dw x 2 dh canvas of 114s.  Per quadrant the
+// canvas rectangle [x1a, x2a) x [y1a, y2a) and the pads (canvas = tile + pad) by load_mosaic's formulas: x1a / x2a and padw = x1a - x1b
+// depend on the column half only (left of xc or not), y1a / y2a and padh = y1a - y1b on the row half only, so six values per axis hold all four.
+struct Canvas {
+    const uint8_t* tl; const uint8_t* tr; const uint8_t* bl; const uint8_t* br;   // the four tiles
+    int xc, yc, dw;
+    int lx1, lx2, lpad, rx1, rx2, rpad;                                            // left and right column half: x1a, x2a, padw
+    int ty1, ty2, tpad, by1, by2, bpad;                                            // top and bottom row half: y1a, y2a, padh
+};
+
+__device__ __forceinline__ void canvas_of(Canvas& cv, int xc, int yc, int dh, int dw)
+{
+    cv.xc = xc; cv.yc = yc; cv.dw = dw;
+    cv.lx1 = max(xc - dw, 0); cv.lx2 = xc;                   cv.lpad = cv.lx1 - (dw - (cv.lx2 - cv.lx1));   // x1b = w - (x2a - x1a)
+    cv.rx1 = xc;              cv.rx2 = min(xc + dw, 2 * dw); cv.rpad = cv.rx1;                              // x1b = 0
+    cv.ty1 = max(yc - dh, 0); cv.ty2 = yc;                   cv.tpad = cv.ty1 - (dh - (cv.ty2 - cv.ty1));
+    cv.by1 = yc;              cv.by2 = min(yc + dh, 2 * dh); cv.bpad = cv.by1;
+}
+
+// One canvas pixel (cx, cy), 0 <= cx < 2 dw, 0 <= cy < 2 dh: the quadrant from cx < xc, cy < yc; that quadrant's tile byte at (cx - padw,
+// cy - padh) if (cx, cy) lies inside the tile's canvas rectangle, else 114.  Inside the rectangle the tile coordinates lie inside the tile
+// (the source rectangle is the rectangle minus the pads), so nothing is read out of bounds.  Every field is read first and
+// the selects act on the values: the struct stays in registers (a select between fields becomes an indexed load from scratch memory).
+template <int C>
+__device__ __forceinline__ void canvas_px(const Canvas& cv, int cx, int cy, int (&v)[C])
+{
+    const uint8_t* const tl = cv.tl; const uint8_t* const tr = cv.tr; const uint8_t* const bl = cv.bl; const uint8_t* const br = cv.br;
+    const int lx1 = cv.lx1, lx2 = cv.lx2, lpad = cv.lpad, rx1 = cv.rx1, rx2 = cv.rx2, rpad = cv.rpad;
+    const int ty1 = cv.ty1, ty2 = cv.ty2, tpad = cv.tpad, by1 = cv.by1, by2 = cv.by2, bpad = cv.bpad;
+    const bool left = cx < cv.xc, top = cy < cv.yc;
+    const int x1 = left ? lx1 : rx1, x2 = left ? lx2 : rx2, padw = left ? lpad : rpad;
+    const int y1 = top ? ty1 : by1, y2 = top ? ty2 : by2, padh = top ? tpad : bpad;
+    if (cx >= x1 && cx < x2 && cy >= y1 && cy < y2) {
+        const uint8_t* const t = top ? (left ? tl : tr) : (left ? bl : br);
+        const uint8_t* const p = t + ((long)(cy - padh) * cv.dw + (cx - padw)) * C;
+#pragma unroll
+        for (int c = 0; c < C; ++c) v[c] = p[c];
+    } else {
+#pragma unroll
+        for (int c = 0; c < C; ++c) v[c] = WARP_FILL;
+    }
+}
+
+// warp_sample over the virtual canvas: inside test against 2 dw x 2 dh, taps clamped to the canvas, each fetched through canvas_px, so a
+// footprint on a seam mixes two to four tiles, or a tile and 114, as on the materialised canvas.  -> false: fill.
+template <int C>
+__device__ __forceinline__ bool canvas_sample(const Canvas& cv, int dh, int dw, const double (&m)[8], bool persp, int x, int y, int (&v)[C])
+{
+    int x0, y0;
+    double ddx, ddy;
+    if (!warp_coords(2 * dh, 2 * dw, m, persp, x, y, x0, y0, ddx, ddy)) return false;
+    const int xa = max(x0, 0), xb = min(x0 + 1, 2 * dw - 1), ya = max(y0, 0);
+    const bool below = y0 + 1 < 2 * dh;
+    int a0[C], b0[C], a1[C], b1[C];
+    canvas_px<C>(cv, xa, ya, a0);
+    canvas_px<C>(cv, xb, ya, b0);
+    if (below) {
+        canvas_px<C>(cv, xa, y0 + 1, a1);
+        canvas_px<C>(cv, xb, y0 + 1, b1);
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        const double v1 = warp_lerp(a0[c], b0[c], ddx);
+        double v2 = v1;
+        if (below) v2 = warp_lerp(a1[c], b1[c], ddx);
+        v[c] = warp_finish(v1, v2, ddy);
+    }
+    return true;
+}
+
+// Built like warp_kernel / mix_kernel: one workgroup owns `tr` destination rows of one output frame and stages them plus the blur halo
+// (reflect-101 on the WARPED image) in LDS; a staged pixel of a mosaic is canvas_sample's, of any other frame frame_px's (warp_kernel's
+// bytes); the blur passes and both flips are the shared ones.  Mosaic or not, the tiles, the centre, the rectangles, k, the flags and the
+// coefficients are uniform per workgroup.
+template <int C>
+__global__ void __launch_bounds__(256) mosaic_kernel(MosaicArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t aug_smem[];
+    const int groups = (a.dh + a.tr - 1) / a.tr;
+    const int n = blockIdx.x / groups, dy0 = (blockIdx.x - n * groups) * a.tr;
+    const int f = a.tiles[(long)n * 4], f1 = a.tiles[(long)n * 4 + 1];
+    if (f < 0 || f >= a.n_frames) return;                     // nothing is read out of bounds; the output frame stays as it was
+    const bool mosaic = f1 >= 0;
+    const long frame = (long)a.dh * a.dw * C;
+    const uint8_t* const img = a.frames + f * frame;          // the frame itself, or the top-left tile
+    // The canvas record is read for a mosaic only.  It is filled on both paths all the same (centre (0, 0), every tile the frame): filling
+    // it under `if (mosaic)` alone compiles to 4 / 19 spilled SGPRs (1 / 3 channels) where this form has 2 / 7.
+    Canvas cv;
+    cv.tl = cv.tr = cv.bl = cv.br = img;
+    int xc = 0, yc = 0;
+    if (mosaic) {
+        const int f2 = a.tiles[(long)n * 4 + 2], f3 = a.tiles[(long)n * 4 + 3];
+        if (f1 >= a.n_frames || f2 < 0 || f2 >= a.n_frames || f3 < 0 || f3 >= a.n_frames) return;
+        xc = a.centre[(long)n * 2];
+        yc = a.centre[(long)n * 2 + 1];
+        if (xc < 0 || xc > 2 * a.dw || yc < 0 || yc > 2 * a.dh) return;
+        cv.tr = a.frames + f1 * frame; cv.bl = a.frames + f2 * frame; cv.br = a.frames + f3 * frame;
+    }
+    canvas_of(cv, xc, yc, a.dh, a.dw);
+    const int p = a.params[n];
+    const int k = ((p & 15) == 3 || (p & 15) == 5 || (p & 15) == 7) ? (p & 15) : 0;
+    const bool fliplr = (p >> 8) & 1, flipud = (p >> 9) & 1, warped = mosaic || ((p >> 10) & 1), persp = (p >> 11) & 1;
+    const int* const taps = k ? aug_taps[(k - 3) >> 1] : aug_taps[0];
+    const int rows = min(a.tr, a.dh - dy0);
+    const int halo = k ? AUG_R : 0;
+    const int T = rows + 2 * halo;
+    const int quads = (a.dw + 3) >> 2;
+    uint8_t* const tile = aug_smem;                                                              // [T][pitch]
+    uint16_t* const hb = reinterpret_cast<uint16_t*>(aug_smem + (size_t)(a.tr + 2 * AUG_R) * a.pitch);   // [T][dw * C]
+    double m[8] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0};
+    if (warped) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) m[i] = a.warp[(long)n * 8 + i];
+    }
+
+    // ---- stage: 4 destination pixels (all channels) per task, one 4-byte LDS store per channel ----
+#pragma unroll 1
+    for (int t = threadIdx.x; t < T * quads; t += 256) {
+        const int r = t / quads, dx0 = (t - r * quads) * 4;
+        const int y = reflect101(dy0 - halo + r, a.dh);
+        uint32_t packed[C];
+#pragma unroll
+        for (int w = 0; w < C; ++w) packed[w] = 0u;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int dx = dx0 + i;
+            if (dx >= a.dw) break;
+            int v[C];
+            if (!mosaic) {
+                frame_px<C>(img, a.dh, a.dw, warped, m, persp, dx, y, v);
+            } else if (!canvas_sample<C>(cv, a.dh, a.dw, m, persp, dx, y, v)) {
+#pragma unroll
+                for (int c = 0; c < C; ++c) v[c] = WARP_FILL;
+            }
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                const int kk = i * C + c;
+                packed[kk >> 2] |= (uint32_t)(v[c] & 255) << (8 * (kk & 3));
+            }
+        }
+        uint32_t* const o = reinterpret_cast<uint32_t*>(tile + r * a.pitch + dx0 * C);
+#pragma unroll
+        for (int w = 0; w < C; ++w) o[w] = packed[w];
+    }
+    __syncthreads();
+
+    blur_rows<C>(tile, hb, taps, k, T, a.dw, a.pitch);
+    blur_cols_store<C>(tile, hb, taps, k, n, dy0, rows, a.dh, a.dw, a.pitch, fliplr, flipud, a.u8, a.x);
+}
+
 template <int GRAY, int C>
 void launch_aug_mode(const AugArgs& a, size_t lds, hipStream_t s)
 {
@@ -485,7 +677,7 @@ void launch_aug_mode(const AugArgs& a, size_t lds, hipStream_t s)
     else hipLaunchKernelGGL((aug_kernel<GRAY, 2, C>), dim3(grid), dim3(256), lds, s, a);
 }
 
-// The LDS geometry aug_kernel, warp_kernel and mix_kernel share: destination rows per workgroup, the u8 tile's row pitch and the LDS bytes of
+// The LDS geometry aug_kernel, warp_kernel, mix_kernel and mosaic_kernel share: destination rows per workgroup, the u8 tile's row pitch and the LDS bytes of
 // a workgroup for N frames of dst_h x dst_w x dst_c.
 int aug_tile(const char* who, int N, int dst_h, int dst_w, int dst_c, int& tr_out, int& pitch, size_t& lds)
 {
@@ -608,6 +800,27 @@ int yf_augment_mix_u8(int device, const uint8_t* d_frames, int n_frames, int N, 
     const unsigned grid = (unsigned)((long)N * ((h + m.tr - 1) / m.tr));
     if (c == 1) hipLaunchKernelGGL((mix_kernel<1>), dim3(grid), dim3(256), lds, (hipStream_t)stream, m);
     else hipLaunchKernelGGL((mix_kernel<3>), dim3(grid), dim3(256), lds, (hipStream_t)stream, m);
+    HIP_OK(hipGetLastError());
+    return YF_OK;
+}
+
+int yf_augment_mosaic_u8(int device, const uint8_t* d_frames, int n_frames, int N, int h, int w, int c, const int* d_tiles, const int* d_centre,
+                         const int* d_params, const double* d_warp, uint8_t* d_u8, float* d_x, void* stream)
+{
+    if (!d_frames || !d_tiles || !d_centre || !d_params || !d_warp || (!d_u8 && !d_x) || N <= 0 || n_frames <= 0)
+        return fail(YF_E_INVALID, "yf_augment_mosaic_u8: null pointer, no output, N <= 0 or n_frames <= 0");
+    if (h <= 0 || w <= 0 || h > 16384 || w > 16384) return fail(YF_E_INVALID, "yf_augment_mosaic_u8: frames of %dx%d", h, w);
+    if (c != 1 && c != 3) return fail(YF_E_INVALID, "yf_augment_mosaic_u8: %d-channel frames (1 or 3)", c);
+    MosaicArgs m{};
+    size_t lds;
+    const int rc = aug_tile("yf_augment_mosaic_u8", N, h, w, c, m.tr, m.pitch, lds);
+    if (rc != YF_OK) return rc;
+    m.frames = d_frames; m.n_frames = n_frames; m.n = N; m.dh = h; m.dw = w; m.tiles = d_tiles; m.centre = d_centre; m.params = d_params;
+    m.warp = d_warp; m.u8 = d_u8; m.x = d_x;
+    HIP_OK(hipSetDevice(device));
+    const unsigned grid = (unsigned)((long)N * ((h + m.tr - 1) / m.tr));
+    if (c == 1) hipLaunchKernelGGL((mosaic_kernel<1>), dim3(grid), dim3(256), lds, (hipStream_t)stream, m);
+    else hipLaunchKernelGGL((mosaic_kernel<3>), dim3(grid), dim3(256), lds, (hipStream_t)stream, m);
     HIP_OK(hipGetLastError());
     return YF_OK;
 }

@@ -31,6 +31,16 @@ blur and the flips act on the mixture; the partner's label rows (normalised and 
 the max_boxes fill.  On the device a batch with at least one hit is one resize launch per source size into a u8 scratch and ONE
 `yf_augment_mix_u8` launch; a batch without a hit goes through the calls above.
 
+`mosaic` is OPT-IN in the same way (the reference has no such key): with `mosaic=True` and augment_params["mosaic"] = p > 0 it is yolov5's
+load_mosaic (draw_mosaic), restated for the rectangular net input H x W: with probability p an item becomes four resized frames -- itself
+and `random.choices(range(len), k=3)`, shuffled -- around a centre `yc = int(random.uniform(H // 2, 2 * H - H // 2))`, `xc` likewise, on a
+2H x 2W canvas of 114s, and that canvas is warped and cropped back to H x W by the same random_perspective (eight draws ALWAYS; with
+neutral keys the central crop), then blurred and flipped.  The tiles' label rows go to canvas pixels, are clipped to the canvas, warped,
+clipped to the output and filtered (_mosaic_labels over _warp_boxes, the core _warp_labels shares).  On the device a batch with at least
+one hit is one resize launch per source size into a u8 scratch and ONE `yf_augment_mosaic_u8` launch, which samples the canvas without
+building it: bit for bit Pillow's Image.transform of the materialised canvas.  A miss costs one draw and goes on as above.  Not built:
+mosaic together with mixup (both probabilities above 0: ValueError; yolov5 blends two mosaics there), mosaic9, segments, copy-paste.
+
 Deviation: the reference cannot return an image without objects -- `np.array([])` is 1-D, so a flip raises IndexError (`labels[:, 1]`,
 :143) and otherwise the box copy raises ValueError (:159); here such an image is blurred / flipped as drawn and gets all-zero boxes (the
 draws stay in the reference's order, so the items after it are the reference's)."""
@@ -58,6 +68,24 @@ def xyxy2xywh(x):
     return y
 
 
+def mosaic_placement(q, xc, yc, H, W):
+    """yolov5's load_mosaic placement of tile q (0 top-left, 1 top-right, 2 bottom-left, 3 bottom-right; every tile H x W) around the
+    centre (xc, yc) of the 2H x 2W canvas -> (x1a, y1a, x2a, y2a, x1b, y1b, x2b, y2b): canvas[y1a:y2a, x1a:x2a] = tile[y1b:y2b, x1b:x2b]."""
+    if q == 0:
+        x1a, y1a, x2a, y2a = max(xc - W, 0), max(yc - H, 0), xc, yc
+        x1b, y1b, x2b, y2b = W - (x2a - x1a), H - (y2a - y1a), W, H
+    elif q == 1:
+        x1a, y1a, x2a, y2a = xc, max(yc - H, 0), min(xc + W, W * 2), yc
+        x1b, y1b, x2b, y2b = 0, H - (y2a - y1a), min(W, x2a - x1a), H
+    elif q == 2:
+        x1a, y1a, x2a, y2a = max(xc - W, 0), yc, xc, min(H * 2, yc + H)
+        x1b, y1b, x2b, y2b = W - (x2a - x1a), 0, W, min(y2a - y1a, H)
+    else:
+        x1a, y1a, x2a, y2a = xc, yc, min(xc + W, W * 2), min(H * 2, yc + H)
+        x1b, y1b, x2b, y2b = 0, 0, min(W, x2a - x1a), min(y2a - y1a, H)
+    return x1a, y1a, x2a, y2a, x1b, y1b, x2b, y2b
+
+
 class DetectBatch:
     """A batch from `DetectDataset.__getitems__`: `imgs` float32 device [N, C, H, W], `targets` float64 host [N, max_boxes, 6].
     Unpacks as `imgs, targets`.  `pin_memory()` is a no-op: the images already live on the GPU (DataLoader(pin_memory=True) calls it;
@@ -76,7 +104,7 @@ class DetectBatch:
 
 class DetectDataset(torch.utils.data.Dataset):
     def __init__(self, input_shape, origin_img_shape, logger, augment=True, aug_params=None, max_boxes=64, val=False, device=None,
-                 gray_bits=15, cache=None, class_names=None, decode="host", progressive=False, mixup=False):
+                 gray_bits=15, cache=None, class_names=None, decode="host", progressive=False, mixup=False, mosaic=False):
         if aug_params is None:
             aug_params = config_params["augment_params"]
         self.aug_params = aug_params
@@ -123,6 +151,14 @@ class DetectDataset(torch.utils.data.Dataset):
             self.mixup = float(aug_params.get("mixup", 0.0))
             if not 0.0 <= self.mixup <= 1.0:
                 raise ValueError("augment_params['mixup'] must lie inside [0, 1]: it is a probability")
+        self.mosaic = 0.0                                   # likewise: read with mosaic=True only
+        if mosaic:
+            self.mosaic = float(aug_params.get("mosaic", 0.0))
+            if not 0.0 <= self.mosaic <= 1.0:
+                raise ValueError("augment_params['mosaic'] must lie inside [0, 1]: it is a probability")
+            if self.mosaic > 0 and self.mixup > 0:
+                raise ValueError("mosaic=True together with mixup=True, both probabilities above 0: yolov5 blends two mosaics there, "
+                                 "which is not built")
         self.max_boxes = max_boxes
         self.augment = augment
         self.gray_bits = gray_bits
@@ -168,18 +204,20 @@ class DetectDataset(torch.utils.data.Dataset):
         -> (blur kernel size: 0, 3 or 7; flip; float64 boxes [max_boxes, 6]).  draw_ex returns the geometric draws as well."""
         return self.draw_ex(index)[:3]
 
-    def _draw_warp(self):
+    def _draw_warp(self, mosaic=False):
         """yolov5's random_perspective matrix for one item, in continuous pixel coordinates of the net-input image (pixel centres at
         half-integers, as Pillow places them and as the normalised labels mean): M = T S R P C in float64, from eight random.uniform draws
         (perspective x, y, angle, gain, shear x, y, translate x, y; all made even where a range is zero).
         -> (M, gain, the eight coefficients of the output -> input map: inv(M) / inv(M)[2, 2]).
         A draw whose denominator a6 x + a7 y + 1 is not positive at all four corners of the output (the image would fold over) is
-        REDRAWN, all eight values; after 100 such draws in a row the configured `perspective` is refused with a ValueError."""
+        REDRAWN, all eight values; after 100 such draws in a row the configured `perspective` is refused with a ValueError.
+        `mosaic`: the input is the 2H x 2W mosaic canvas and the output still H x W (yolov5's border = -s // 2): C moves the CANVAS
+        centre (W, H) to the origin; T, the fold-over rule and everything else stay those of the output."""
         H, W = self.input_shape[0], self.input_shape[1]
         g = abs(self.scale - 1.0)
         for _ in range(100):
             C = np.eye(3)
-            C[0, 2], C[1, 2] = -W / 2, -H / 2
+            C[0, 2], C[1, 2] = (-W, -H) if mosaic else (-W / 2, -H / 2)
             P = np.eye(3)
             P[2, 0] = random.uniform(-self.perspective, self.perspective)
             P[2, 1] = random.uniform(-self.perspective, self.perspective)
@@ -209,6 +247,12 @@ class DetectDataset(torch.utils.data.Dataset):
         H, W = self.input_shape[0], self.input_shape[1]
         x1, x2 = (labels[:, 1] - labels[:, 3] / 2) * W, (labels[:, 1] + labels[:, 3] / 2) * W
         y1, y2 = (labels[:, 2] - labels[:, 4] / 2) * H, (labels[:, 2] + labels[:, 4] / 2) * H
+        return self._warp_boxes(labels, x1, y1, x2, y2, M, gain)
+
+    def _warp_boxes(self, labels, x1, y1, x2, y2, M, gain):
+        """The pixel-coordinate core of _warp_labels: boxes (x1, y1, x2, y2) in pixels of the warp's INPUT (the net-input image, or the
+        mosaic canvas) through M into the H x W output -> the kept rows of `labels`, columns 1 .. 4 the new normalised boxes."""
+        H, W = self.input_shape[0], self.input_shape[1]
         n = len(labels)
         xy = np.ones((n * 4, 3))
         xy[:, 0] = np.stack([x1, x2, x1, x2], 1).reshape(-1)
@@ -224,6 +268,31 @@ class DetectDataset(torch.utils.data.Dataset):
         out = labels.copy()
         out[:, 1], out[:, 2], out[:, 3], out[:, 4] = (nx1 + nx2) / 2 / W, (ny1 + ny2) / 2 / H, w2 / W, h2 / H
         return out[keep]
+
+    def _mosaic_labels(self, tiles, xc, yc, M, gain):
+        """yolov5's load_mosaic labels: each tile's normalised rows to canvas pixels (xywhn2xyxy with the tile's padw = x1a - x1b, padh =
+        y1a - y1b), concatenated in tile order, clipped to the 2W x 2H canvas, then the label half of random_perspective (_warp_boxes:
+        box_candidates compares with the CLIPPED canvas boxes times gain).  -> normalised (cls, xc, yc, w, h) rows, possibly none."""
+        H, W = self.input_shape[0], self.input_shape[1]
+        rows = []
+        for q, t in enumerate(tiles):
+            lab = self._labels(t)
+            if not len(lab):
+                continue
+            x1a, y1a, _, _, x1b, y1b, _, _ = mosaic_placement(q, xc, yc, H, W)
+            padw, padh = x1a - x1b, y1a - y1b
+            box = lab.copy()
+            box[:, 1] = W * (lab[:, 1] - lab[:, 3] / 2) + padw
+            box[:, 2] = H * (lab[:, 2] - lab[:, 4] / 2) + padh
+            box[:, 3] = W * (lab[:, 1] + lab[:, 3] / 2) + padw
+            box[:, 4] = H * (lab[:, 2] + lab[:, 4] / 2) + padh
+            rows.append(box)
+        if not rows:
+            return np.zeros((0, 5))
+        box = np.concatenate(rows)
+        box[:, [1, 3]] = box[:, [1, 3]].clip(0, 2 * W)
+        box[:, [2, 4]] = box[:, [2, 4]].clip(0, 2 * H)
+        return self._warp_boxes(box, box[:, 1], box[:, 2], box[:, 3], box[:, 4], M, gain)
 
     def draw_ex(self, index):
         """draw() with the geometric part: -> (k, flip, boxes, flipud, coeffs), coeffs the eight float64 output -> input coefficients of
@@ -255,16 +324,41 @@ class DetectDataset(torch.utils.data.Dataset):
           6. as without mixup: blur?, which blur, fliplr?, [flipud?].
         The partner gets no blur or flip draws: those act on the mixture.  Labels: the partner's rows (the reference's normalisation, then
         the partner's own warp) are appended AFTER the item's; both flips act on all rows; the max_boxes fill runs last, so truncation
-        drops partner rows first; an image without objects contributes no rows, on either side."""
+        drops partner rows first; an image without objects contributes no rows, on either side.
+        With mosaic active (draw_mosaic) the draws are draw_mosaic's, and an item that became a mosaic has coeffs None here."""
+        return self.draw_mosaic(index)[:8]
+
+    def draw_mosaic(self, index):
+        """draw_mix's eight values and a ninth: None, or (xc, yc, tiles, coeffs) for an item that became a mosaic -- yolov5's
+        load_mosaic for the rectangular net input H x W.  Mosaic is active with mosaic=True, augment and augment_params["mosaic"] = p > 0;
+        inactive, no draw is added and the ninth value is None.  Active, the draws of an item are:
+          1. random.random() < p; on a miss the item goes on as draw_mix describes, from its step 1;
+          2. on a hit yc = int(random.uniform(H // 2, 2 * H - H // 2)), THEN xc = int(random.uniform(W // 2, 2 * W - W // 2));
+          3. tiles = [index] + random.choices(range(len(self)), k=3), then random.shuffle(tiles): top-left, top-right, bottom-left,
+             bottom-right (mosaic_placement);
+          4. _draw_warp(mosaic=True)'s eight draws, ALWAYS (with neutral keys the ranges are empty; the warp is then the central crop);
+          5. blur?, which blur, fliplr?, [flipud?].
+        A hit's first eight values are (k, flip, boxes, flipud, None, None, None, None): the single frame has no warp of its own and no
+        partner (mosaic and mixup are not combined).  Labels of a hit: _mosaic_labels, then the flips and the max_boxes fill (truncation
+        drops the later rows)."""
         labels = self._labels(index)
         k, flip, flipud, coeffs = 0, False, False, None
-        partner = partner_coeffs = r = None
+        partner = partner_coeffs = r = mosaic = None
         if self.augment:
-            if self.geometric:
+            if self.mosaic > 0 and random.random() < self.mosaic:
+                H, W = self.input_shape[0], self.input_shape[1]
+                yc = int(random.uniform(H // 2, 2 * H - H // 2))
+                xc = int(random.uniform(W // 2, 2 * W - W // 2))
+                tiles = [index] + random.choices(range(len(self)), k=3)
+                random.shuffle(tiles)
+                M, gain, canvas_coeffs = self._draw_warp(mosaic=True)
+                labels = self._mosaic_labels(tiles, xc, yc, M, gain)
+                mosaic = (xc, yc, tiles, canvas_coeffs)
+            elif self.geometric:
                 M, gain, coeffs = self._draw_warp()
                 if len(labels):
                     labels = self._warp_labels(labels, M, gain)
-            if self.mixup > 0 and random.random() < self.mixup:
+            if mosaic is None and self.mixup > 0 and random.random() < self.mixup:
                 partner = random.randint(0, len(self) - 1)
                 other = self._labels(partner)
                 if self.geometric:
@@ -295,7 +389,7 @@ class DetectDataset(torch.utils.data.Dataset):
         if m:                                       # deviation: the reference's copy raises ValueError for no objects
             out[:m, 0:5] = labels[:m]
             out[:m, 5] = 255.0
-        return k, flip, out, flipud, coeffs, partner, partner_coeffs, r
+        return k, flip, out, flipud, coeffs, partner, partner_coeffs, r, mosaic
 
     # ---- images (GPU) ----
     def _need_gpu(self):
@@ -401,12 +495,11 @@ class DetectDataset(torch.utils.data.Dataset):
             return self._from_device_decode(indices)
         return self._from_host_decode(indices)
 
-    def _mix_images(self, indices, packed, warps, mixes, out, out_u8, stream):
-        """A batch with at least one mixup hit: every distinct frame of items and partners resized once (yf_augment_u8 with zero
-        parameters, one launch per source size, each into its slice of one u8 scratch), then one yf_augment_mix_u8 into `out`."""
+    def _resize_distinct(self, distinct, stream):
+        """The distinct frames `distinct` resized (and grayed) once: yf_augment_u8 with zero parameters, one launch per source size, each
+        into its slice of one u8 scratch -> (scratch [len(distinct), H, W, C], item -> its frame in the scratch)."""
         H, W, C = self.input_shape
         dev, lib = self.device, _lib.lib()
-        distinct = list(dict.fromkeys(list(indices) + [m[0] for m in mixes if m is not None]))
         scratch = torch.empty((len(distinct), H, W, C), dtype=torch.uint8, device=dev)
         where, base = {}, 0                                  # item -> its frame in the scratch
         for stack, slots, pos in self._groups(distinct):
@@ -420,6 +513,15 @@ class DetectDataset(torch.utils.data.Dataset):
             for j, p in enumerate(pos):
                 where[distinct[p]] = base + j
             base += len(pos)
+        return scratch, where
+
+    def _mix_images(self, indices, packed, warps, mixes, out, out_u8, stream):
+        """A batch with at least one mixup hit: every distinct frame of items and partners resized once (_resize_distinct), then one
+        yf_augment_mix_u8 into `out`."""
+        H, W, C = self.input_shape
+        dev, lib = self.device, _lib.lib()
+        distinct = list(dict.fromkeys(list(indices) + [m[0] for m in mixes if m is not None]))
+        scratch, where = self._resize_distinct(distinct, stream)
         neutral = [1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0]
         first = torch.tensor([where[i] for i in indices], dtype=torch.int32).to(dev)
         second = torch.tensor([-1 if m is None else where[m[0]] for m in mixes], dtype=torch.int32).to(dev)
@@ -432,11 +534,30 @@ class DetectDataset(torch.utils.data.Dataset):
                                          prm.data_ptr(), warp.data_ptr(), ratio.data_ptr(), out.data_ptr() if out_u8 else None,
                                          None if out_u8 else out.data_ptr(), ctypes.c_void_p(stream)))
 
+    def _mosaic_images(self, indices, packed, warps, mosaics, out, out_u8, stream):
+        """A batch with at least one mosaic: every distinct frame of items and tiles resized once (_resize_distinct), then one
+        yf_augment_mosaic_u8 into `out`; an item that is no mosaic is its own frame with tile slots 1 .. 3 at -1 (the warp call's bytes)."""
+        H, W, C = self.input_shape
+        dev, lib = self.device, _lib.lib()
+        distinct = list(dict.fromkeys(list(indices) + [int(t) for m in mosaics if m is not None for t in m[2]]))
+        scratch, where = self._resize_distinct(distinct, stream)
+        neutral = [1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0]
+        tiles = torch.tensor([[where[i], -1, -1, -1] if m is None else [where[int(t)] for t in m[2]] for i, m in zip(indices, mosaics)],
+                             dtype=torch.int32).to(dev)
+        centre = torch.tensor([[0, 0] if m is None else [int(m[0]), int(m[1])] for m in mosaics], dtype=torch.int32).to(dev)
+        prm = torch.tensor(packed, dtype=torch.int32).to(dev)
+        warp = torch.tensor([neutral if w is None else [float(v) for v in w] for w in warps], dtype=torch.float64).to(dev)
+        _lib.check(lib.yf_augment_mosaic_u8(dev.index, scratch.data_ptr(), len(distinct), len(indices), H, W, C, tiles.data_ptr(),
+                                            centre.data_ptr(), prm.data_ptr(), warp.data_ptr(), out.data_ptr() if out_u8 else None,
+                                            None if out_u8 else out.data_ptr(), ctypes.c_void_p(stream)))
+
     def augment_images(self, indices, params, out_u8=False):
         """The frames `indices` with per-frame `params` -- (k, flip), (k, flip, flipud, coeffs), draw_ex's values, or those extended by
         draw_mix's (partner, partner_coeffs, r) -- through yf_augment_u8, one launch per source size; a size group with a warped or
         flipud frame goes through yf_augment_warp_u8 (two).  With at least one partner: the distinct frames of items and partners resized
         by yf_augment_u8 (one launch per source size) into one u8 scratch, then ONE yf_augment_mix_u8 for the whole batch.
+        Extended once more by draw_mosaic's ninth value (None, or (xc, yc, tiles, coeffs)): with at least one mosaic, the distinct
+        frames of items and tiles resized the same way, then ONE yf_augment_mosaic_u8 for the whole batch.
         -> float32 device [N, C, H, W] ((v - 128) / 255), or uint8 device [N, H, W, C] with out_u8."""
         self._need_gpu()
         H, W, C = self.input_shape
@@ -444,15 +565,25 @@ class DetectDataset(torch.utils.data.Dataset):
         dev = self.device
         stream = torch.cuda.current_stream(dev).cuda_stream
         out = torch.empty((N, H, W, C) if out_u8 else (N, C, H, W), dtype=torch.uint8 if out_u8 else torch.float32, device=dev)
-        packed, warps, mixes = [], [], []
+        packed, warps, mixes, mosaics = [], [], [], []
         for k, f, *rest in params:
-            ud, coeffs, partner, pcoeffs, r = (tuple(rest) + (None, None, None))[:5] if rest else (False, None, None, None, None)
+            ud, coeffs, partner, pcoeffs, r, mosaic = (tuple(rest) + (None, None, None, None))[:6] if rest else (False, None, None, None, None, None)
+            if mosaic is not None:
+                if partner is not None:
+                    raise ValueError("a frame cannot be a mosaic and have a mixup partner: the two are not combined")
+                coeffs = mosaic[3]                              # the canvas's coefficients take the frame's slot
+            mosaics.append(mosaic)
             warps.append(coeffs)
             mixes.append(None if partner is None else (int(partner), pcoeffs, float(r)))
             packed.append(int(k) | (int(bool(f)) << 8) | (int(bool(ud)) << 9) |
                           (0 if coeffs is None else (1 << 10) | (int(coeffs[6] != 0 or coeffs[7] != 0) << 11)) |
                           (0 if partner is None or pcoeffs is None else (1 << 12) | (int(pcoeffs[6] != 0 or pcoeffs[7] != 0) << 13)))
         lib = _lib.lib()
+        if any(m is not None for m in mosaics):
+            if any(m is not None for m in mixes):
+                raise ValueError("a batch cannot hold mosaics and mixup partners: the two are not combined")
+            self._mosaic_images(indices, packed, warps, mosaics, out, out_u8, stream)
+            return out
         if any(m is not None for m in mixes):
             self._mix_images(indices, packed, warps, mixes, out, out_u8, stream)
             return out
@@ -481,8 +612,8 @@ class DetectDataset(torch.utils.data.Dataset):
     def __getitem__(self, index):
         """The reference's item: (float64 [H, W, C] image u8 - 128.0, float64 [max_boxes, 6] boxes)."""
         self._need_gpu()
-        k, flip, boxes, flipud, coeffs, partner, partner_coeffs, r = self.draw_mix(index)
-        u8 = self.augment_images([index], [(k, flip, flipud, coeffs, partner, partner_coeffs, r)], out_u8=True)[0].cpu().numpy()
+        k, flip, boxes, flipud, coeffs, partner, partner_coeffs, r, mosaic = self.draw_mosaic(index)
+        u8 = self.augment_images([index], [(k, flip, flipud, coeffs, partner, partner_coeffs, r, mosaic)], out_u8=True)[0].cpu().numpy()
         img = u8 - 128.0
         return np.ascontiguousarray(img), boxes
 
@@ -491,8 +622,9 @@ class DetectDataset(torch.utils.data.Dataset):
         -> DetectBatch(float32 device [N, C, H, W], float64 host [N, max_boxes, 6]); collate_fn passes it through."""
         self._need_gpu()
         indices = [int(i) for i in indices]
-        draws = [self.draw_mix(i) for i in indices]
-        imgs = self.augment_images(indices, [(k, f, ud, coeffs) + tuple(mix) for k, f, _, ud, coeffs, *mix in draws])
+        draws = [self.draw_mosaic(i) for i in indices]
+        tail = 4 if self.augment and self.mosaic > 0 else 3      # the mosaic value travels only where one can occur
+        imgs = self.augment_images(indices, [(k, f, ud, coeffs) + tuple(mix[:tail]) for k, f, _, ud, coeffs, *mix in draws])
         targets = torch.from_numpy(np.stack([d[2] for d in draws])) if draws else torch.zeros((0, self.max_boxes, 6), dtype=torch.float64)
         return DetectBatch(imgs, targets)
 
