@@ -283,6 +283,35 @@ int yf_train_opt_multi_pinned(int device, int kind, int ntensors, void *const *d
                               const long *sizes, const int *group_of, const int *first, int ngroups, const yf_opt_group *groups, void *d_table,
                               size_t table_bytes, void *h_table_pinned, int upload, void *stream);
 
+/* yf_train_opt_multi_pinned with yolov5's ModelEMA kept inside the same launch (training.ModelEMA; step(ema=...)): after tensor t's
+ * update the kernel goes on with the value it just stored in p, every scalar rounded once from double to float:
+ *                    d_f = (float)d;  omd_f = (float)(1.0 - d)
+ *                    a = round(e * d_f)                                      (e: the element of d_ema[t])
+ *                    b = round(omd_f * p)                                    (p: the element of d_p[t] as just written)
+ *                    e = round(a + b)
+ * three separately rounded fp32 operations, never a fused multiply-add: torch's `v *= d; v += (1 - d) * p` on float32 tensors.
+ * d_ema: HOST array of `ntensors` device pointers, one per optimised tensor.  The `n_extra` tensors behind them are EMA-only --
+ * d_extra_src[t] is read, d_extra_ema[t] gets the three lines above, no gradient and no optimizer arithmetic (BatchNorm running
+ * statistics, parameters without a gradient); n_extra == 0 allows the three arrays to be NULL.  d: this update's decay, e.g.
+ * decay * (1 - exp(-updates / tau)); d_f and omd_f travel as kernel arguments, so a call that differs only in d passes upload == 0.
+ * d_table / h_table_pinned / upload as in yf_train_opt_multi_pinned with YF_OPT_EMA_TABLE_ENTRY_BYTES per tensor, ntensors + n_extra
+ * of them; upload != 0 too when an EMA or EMA-only pointer changed.  Stream-ordered, capturable, no allocation, no synchronisation.
+ * YF_E_INVALID before the GPU is touched for everything yf_train_opt_multi_pinned refuses, and for: d outside [0, 1] or not finite,
+ * n_extra < 0, a null EMA / source pointer, an EMA-only size <= 0, an EMA pointer equal to its source, a table that is too small. */
+#define YF_OPT_EMA_TABLE_ENTRY_BYTES 64
+int yf_train_opt_ema_multi_pinned(int device, int kind, int ntensors, void *const *d_p, const void *const *d_g, void *const *d_s1,
+                                  void *const *d_s2, const long *sizes, const int *group_of, const int *first, int ngroups,
+                                  const yf_opt_group *groups, void *const *d_ema, int n_extra, const void *const *d_extra_src,
+                                  void *const *d_extra_ema, const long *extra_sizes, double d, void *d_table, size_t table_bytes,
+                                  void *h_table_pinned, int upload, void *stream);
+/* The average alone, ONE launch for `ntensors` (d_src[t], d_ema[t], sizes[t]) triples (training.ModelEMA.update beside any optimizer):
+ *                    e = round(round(e * d_f) + round(omd_f * s))            (s: the element of d_src[t]; d_f, omd_f as above)
+ * The table takes YF_EMA_TABLE_ENTRY_BYTES per tensor; d_table / h_table_pinned / upload, the stream ordering and the refusals (null
+ * pointer, size <= 0, d outside [0, 1] or not finite, d_ema[t] == d_src[t], table too small) as above. */
+#define YF_EMA_TABLE_ENTRY_BYTES 32
+int yf_train_ema_multi_pinned(int device, int ntensors, const void *const *d_src, void *const *d_ema, const long *sizes, double d,
+                              void *d_table, size_t table_bytes, void *h_table_pinned, int upload, void *stream);
+
 /* The same training forward / backward as ONE call each: the whole graph of yolo_fastest.py:150-218 in train mode (what
  * `pred = model(imgs)` and `loss.backward()` run, train.py:114, :131), launched from C++ into a caller-owned workspace.
  *   d_params / d_grads: HOST arrays of yf_trainer_num_params() device pointers in `model.parameters()` order (per conv block: conv

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Training-step throughput (train.py:111-132: zero_grad, train-mode forward, two-head loss, backward, Adam) on synthetic frames.
-GPU box: python tools/train_bench.py [--batch 16] [--steps 20] [--optimizer reference|adam|sgd] [--cpu]   (--cpu also times oracle/ on the host cores: the baseline)"""
+GPU box: python tools/train_bench.py [--batch 16] [--steps 20] [--optimizer reference|adam|sgd] [--ema off|fused|loop] [--cpu]   (--cpu also times oracle/ on the host cores: the baseline)"""
 import argparse
 import os
 import sys
@@ -23,6 +23,9 @@ ap.add_argument("--optimizer", choices=["reference", "adam", "sgd"], default="re
                 help="reference: train.py:84's Adam on one group; adam / sgd: what training.train(optimizer=...) builds, three groups")
 ap.add_argument("--branch-weight", type=float, nargs=2, default=None, metavar=("LARGE", "SMALL"),
                 help="train_step(branch_weight=...): factors other than 1 take one backward per head")
+ap.add_argument("--ema", choices=["off", "fused", "loop"], default="off",
+                help="yolov5's ModelEMA behind every step: fused = training.ModelEMA inside the optimizer's launch (train_step(ema=...)); "
+                     "loop = yolov5's own update(), a Python loop over the state dict on torch kernels")
 ap.add_argument("--cpu", action="store_true")
 ap.add_argument("--json", action="store_true", help="also print one JSON line (metric, value, ms per iteration, cpu baseline)")
 a = ap.parse_args()
@@ -51,19 +54,42 @@ elif a.optimizer == "adam":                  # train(optimizer="adam"): yolov5's
 else:                                        # train(optimizer="sgd")
     opt = training.SGD(training.param_groups(m, tp["weight_decay"]), lr=0.001, momentum=tp["momentum"], nesterov=True)
 xd, td = x.to(dev), tt.to(dev)
+ema = training.ModelEMA(m) if a.ema != "off" else None
+
+
+def loop_update():
+    """yolov5's ModelEMA.update (utils/torch_utils.py), on the same EMA network"""
+    ema.updates += 1
+    d = ema.decay(ema.updates)
+    msd = m.state_dict()
+    with torch.no_grad():
+        for k, v in ema.ema.state_dict().items():
+            if v.dtype.is_floating_point:
+                v *= d
+                v += (1 - d) * msd[k].detach()
+
+
+def iteration():
+    if a.ema == "loop":
+        out = training.train_step(m, crit, opt, xd, td, a.branch_weight)
+        loop_update()
+        return out
+    return training.train_step(m, crit, opt, xd, td, a.branch_weight, ema=ema)
+
+
 for _ in range(a.warmup):
-    training.train_step(m, crit, opt, xd, td, a.branch_weight)
+    iteration()
 torch.cuda.synchronize()
 t0 = time.perf_counter()
 for _ in range(a.steps):
-    loss = training.train_step(m, crit, opt, xd, td, a.branch_weight)[0]
+    loss = iteration()[0]
 torch.cuda.synchronize()
 dt = (time.perf_counter() - t0) / a.steps
 print("GPU  batch %d %dx%d: %.2f ms / iteration, %.0f examples/s, loss %.4f" % (a.batch, H, W, dt * 1e3, a.batch / dt, float(loss.detach())))
 line = {"metric": "training_examples_per_second", "value": round(a.batch / dt, 1), "unit": "examples/s", "ms_per_iteration": round(dt * 1e3, 3),
         "steps": a.steps, "warmup": a.warmup, "dtype": "f32", "data": "synthetic",
         "config": {"workload": "train.py:111-132 iteration (zero_grad, train-mode forward, two-head loss, backward, Adam)", "batch": a.batch,
-                   "input": [H, W], "optimizer": a.optimizer}, "cpu_baseline": None}
+                   "input": [H, W], "optimizer": a.optimizer, "ema": a.ema}, "cpu_baseline": None}
 if a.cpu:
     from oracle import backbone_oracle as bo, loss_oracle as lo
     sd = bo.training_state(sd0)

@@ -16,6 +16,7 @@ YF_OK, YF_E_INVALID, YF_E_BLOB, YF_E_HIP, YF_E_WORKSPACE, YF_E_NOPROBE = 0, -1, 
 _c = ctypes
 
 YF_OPT_ADAM, YF_OPT_SGD, YF_OPT_MAX_GROUPS, YF_OPT_TABLE_ENTRY_BYTES = 0, 1, 8, 56     # yf_train_opt_multi_pinned
+YF_OPT_EMA_TABLE_ENTRY_BYTES, YF_EMA_TABLE_ENTRY_BYTES = 64, 32                        # yf_train_opt_ema_multi_pinned, yf_train_ema_multi_pinned
 
 
 class OptGroup(_c.Structure):
@@ -101,6 +102,11 @@ _SIGS = {
                                               _c.c_double, _c.c_double, _c.c_double, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_int,
                                               _c.c_void_p]),
     "yf_train_opt_multi_pinned": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int] + [_c.c_void_p] * 7 + [_c.c_int, _c.c_void_p, _c.c_void_p, _c.c_size_t,
+                                             _c.c_void_p, _c.c_int, _c.c_void_p]),
+    "yf_train_opt_ema_multi_pinned": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int] + [_c.c_void_p] * 7 + [_c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int,
+                                                 _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_double, _c.c_void_p, _c.c_size_t, _c.c_void_p,
+                                                 _c.c_int, _c.c_void_p]),       # ... groups, d_ema, n_extra, extra src / ema / sizes, d, table ...
+    "yf_train_ema_multi_pinned": (_c.c_int, [_c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_double, _c.c_void_p, _c.c_size_t,
                                              _c.c_void_p, _c.c_int, _c.c_void_p]),
     "yf_train_channel_sum": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_long, _c.c_void_p]),
     "yf_train_channel_sum_split": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_long, _c.c_void_p, _c.c_void_p]),

@@ -384,6 +384,14 @@ struct TOptGroup { double lr, wd, mom, b1, b2, eps; int nesterov, step; };
 int launch_topt_multi(int kind, int nt, float* const* p, const float* const* g, float* const* s1, float* const* s2, const long* sizes,
                       const int* group_of, const int* first, int ngroups, const TOptGroup* groups, void* d_table, void* h_table, int upload,
                       hipStream_t s);
+// ... with yolov5's ModelEMA behind every update, plus n_extra EMA-only tensors (64-byte table entries, nt + n_extra of them), and the
+// average alone over (src, ema, size) triples (32-byte entries); d: the step's decay, rounded once to float as d and as 1 - d
+int launch_topt_ema_multi(int kind, int nt, float* const* p, const float* const* g, float* const* s1, float* const* s2, const long* sizes,
+                          const int* group_of, const int* first, int ngroups, const TOptGroup* groups, float* const* ema, int n_extra,
+                          const float* const* xsrc, float* const* xema, const long* xsizes, double d, void* d_table, void* h_table, int upload,
+                          hipStream_t s);
+int launch_tema_multi(int nt, const float* const* src, float* const* ema, const long* sizes, double d, void* d_table, void* h_table, int upload,
+                      hipStream_t s);
 void launch_tchan_sum(const float* dy, float* out, int N, int C, long HW, hipStream_t s, void* scratch = nullptr /* >= 64 C doubles */);
 void launch_tadd(const float* a, const float* b, float* out, long total, hipStream_t s);
 void launch_tslice(const float* src, float* dst, int N, int C, long HW, int Cs, int sc0, int Cd, int dc0, hipStream_t s);

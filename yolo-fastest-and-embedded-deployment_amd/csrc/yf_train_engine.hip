@@ -369,42 +369,108 @@ int yf_train_adam_multi_pinned(int device, int ntensors, void* const* d_p, const
     HIP_OK(hipGetLastError());
     return YF_OK;
 }
+// the argument checks yf_train_opt_multi_pinned and yf_train_opt_ema_multi_pinned share (`who` names the entry in the message); fills gs,
+// adds the tensors' workgroups to *blocks.  `entries` table entries of `entry_bytes` must fit.
+static int opt_multi_check(const char* who, int kind, int ntensors, void* const* d_p, const void* const* d_g, void* const* d_s1, void* const* d_s2,
+                           const long* sizes, const int* group_of, int ngroups, const yf_opt_group* groups, void* d_table, size_t table_bytes,
+                           long entries, size_t entry_bytes, yf::TOptGroup* gs, long* blocks)
+{
+    if (kind != YF_OPT_ADAM && kind != YF_OPT_SGD) return fail(YF_E_INVALID, "%s: unknown kind %d", who, kind);
+    if (!d_p || !d_g || !sizes || !group_of || !groups || !d_table || ntensors <= 0 || entries < ntensors || table_bytes < (size_t)entries * entry_bytes)
+        return fail(YF_E_INVALID, "%s: bad argument", who);
+    if (ngroups < 1 || ngroups > YF_OPT_MAX_GROUPS) return fail(YF_E_INVALID, "%s: %d groups (1 .. %d)", who, ngroups, YF_OPT_MAX_GROUPS);
+    if (kind == YF_OPT_ADAM && (!d_s1 || !d_s2)) return fail(YF_E_INVALID, "%s: Adam needs both state arrays", who);
+    for (int i = 0; i < ngroups; ++i) {
+        const yf_opt_group& q = groups[i];
+        if (q.maximize) return fail(YF_E_INVALID, "%s: group %d: maximize is not implemented", who, i);
+        if (kind == YF_OPT_SGD) {
+            if (q.dampening != 0) return fail(YF_E_INVALID, "%s: group %d: dampening is not implemented", who, i);
+            if (!(q.momentum >= 0)) return fail(YF_E_INVALID, "%s: group %d: negative momentum", who, i);
+            if (q.nesterov && q.momentum == 0) return fail(YF_E_INVALID, "%s: group %d: nesterov needs a momentum", who, i);
+        } else if (q.step < 1) {
+            return fail(YF_E_INVALID, "%s: group %d: step %d (counts from 1)", who, i, q.step);
+        }
+        gs[i] = yf::TOptGroup{q.lr, q.weight_decay, q.momentum, q.beta1, q.beta2, q.eps, q.nesterov, q.step};
+    }
+    for (int t = 0; t < ntensors; ++t) {
+        if (group_of[t] < 0 || group_of[t] >= ngroups) return fail(YF_E_INVALID, "%s: tensor %d: group %d of %d", who, t, group_of[t], ngroups);
+        const bool need1 = kind == YF_OPT_ADAM || gs[group_of[t]].mom != 0;
+        if (!d_p[t] || !d_g[t] || sizes[t] <= 0 || (need1 && (!d_s1 || !d_s1[t])) || (kind == YF_OPT_ADAM && !d_s2[t]))
+            return fail(YF_E_INVALID, "%s: tensor %d: null pointer or empty", who, t);
+        *blocks += (sizes[t] + 255) / 256;
+        if (*blocks > 0x7fffffffL) return fail(YF_E_INVALID, "%s: more than 2^31 workgroups", who);
+    }
+    return YF_OK;
+}
 int yf_train_opt_multi_pinned(int device, int kind, int ntensors, void* const* d_p, const void* const* d_g, void* const* d_s1, void* const* d_s2,
                               const long* sizes, const int* group_of, const int* first, int ngroups, const yf_opt_group* groups, void* d_table,
                               size_t table_bytes, void* h_table_pinned, int upload, void* stream)
 {
     static_assert(YF_OPT_MAX_GROUPS == 8 && YF_OPT_TABLE_ENTRY_BYTES == 56, "the kernels' group array and table entry (yf_train_opt_kernels.h)");
-    if (kind != YF_OPT_ADAM && kind != YF_OPT_SGD) return fail(YF_E_INVALID, "yf_train_opt_multi: unknown kind %d", kind);
-    if (!d_p || !d_g || !sizes || !group_of || !groups || !d_table || ntensors <= 0 || table_bytes < (size_t)ntensors * YF_OPT_TABLE_ENTRY_BYTES)
-        return fail(YF_E_INVALID, "yf_train_opt_multi: bad argument");
-    if (ngroups < 1 || ngroups > YF_OPT_MAX_GROUPS) return fail(YF_E_INVALID, "yf_train_opt_multi: %d groups (1 .. %d)", ngroups, YF_OPT_MAX_GROUPS);
-    if (kind == YF_OPT_ADAM && (!d_s1 || !d_s2)) return fail(YF_E_INVALID, "yf_train_opt_multi: Adam needs both state arrays");
     yf::TOptGroup gs[YF_OPT_MAX_GROUPS];
-    for (int i = 0; i < ngroups; ++i) {
-        const yf_opt_group& q = groups[i];
-        if (q.maximize) return fail(YF_E_INVALID, "yf_train_opt_multi: group %d: maximize is not implemented", i);
-        if (kind == YF_OPT_SGD) {
-            if (q.dampening != 0) return fail(YF_E_INVALID, "yf_train_opt_multi: group %d: dampening is not implemented", i);
-            if (!(q.momentum >= 0)) return fail(YF_E_INVALID, "yf_train_opt_multi: group %d: negative momentum", i);
-            if (q.nesterov && q.momentum == 0) return fail(YF_E_INVALID, "yf_train_opt_multi: group %d: nesterov needs a momentum", i);
-        } else if (q.step < 1) {
-            return fail(YF_E_INVALID, "yf_train_opt_multi: group %d: step %d (counts from 1)", i, q.step);
-        }
-        gs[i] = yf::TOptGroup{q.lr, q.weight_decay, q.momentum, q.beta1, q.beta2, q.eps, q.nesterov, q.step};
-    }
     long blocks = 0;
-    for (int t = 0; t < ntensors; ++t) {
-        if (group_of[t] < 0 || group_of[t] >= ngroups) return fail(YF_E_INVALID, "yf_train_opt_multi: tensor %d: group %d of %d", t, group_of[t], ngroups);
-        const bool need1 = kind == YF_OPT_ADAM || gs[group_of[t]].mom != 0;
-        if (!d_p[t] || !d_g[t] || sizes[t] <= 0 || (need1 && (!d_s1 || !d_s1[t])) || (kind == YF_OPT_ADAM && !d_s2[t]))
-            return fail(YF_E_INVALID, "yf_train_opt_multi: tensor %d: null pointer or empty", t);
-        blocks += (sizes[t] + 255) / 256;
-        if (blocks > 0x7fffffffL) return fail(YF_E_INVALID, "yf_train_opt_multi: more than 2^31 workgroups");
-    }
+    if (const int rc = opt_multi_check("yf_train_opt_multi", kind, ntensors, d_p, d_g, d_s1, d_s2, sizes, group_of, ngroups, groups, d_table,
+                                       table_bytes, ntensors, YF_OPT_TABLE_ENTRY_BYTES, gs, &blocks))
+        return rc;
     HIP_OK(hipSetDevice(device));
     if (yf::launch_topt_multi(kind, ntensors, (float* const*)d_p, (const float* const*)d_g, (float* const*)d_s1, (float* const*)d_s2, sizes, group_of,
                               first, ngroups, gs, d_table, h_table_pinned, upload, (hipStream_t)stream))
         return fail(YF_E_HIP, "yf_train_opt_multi: the upload of the pointer table failed");
+    HIP_OK(hipGetLastError());
+    return YF_OK;
+}
+// the decay of one EMA update: a finite number in [0, 1]
+static bool ema_decay_ok(double d) { return d >= 0.0 && d <= 1.0; }        // (false for NaN)
+
+int yf_train_opt_ema_multi_pinned(int device, int kind, int ntensors, void* const* d_p, const void* const* d_g, void* const* d_s1,
+                                  void* const* d_s2, const long* sizes, const int* group_of, const int* first, int ngroups,
+                                  const yf_opt_group* groups, void* const* d_ema, int n_extra, const void* const* d_extra_src,
+                                  void* const* d_extra_ema, const long* extra_sizes, double d, void* d_table, size_t table_bytes,
+                                  void* h_table_pinned, int upload, void* stream)
+{
+    static_assert(YF_OPT_EMA_TABLE_ENTRY_BYTES == 64, "the kernels' table entry (yf_train_opt_kernels.h)");
+    const char* who = "yf_train_opt_ema_multi";
+    if (n_extra < 0 || (n_extra > 0 && (!d_extra_src || !d_extra_ema || !extra_sizes)) || !d_ema) return fail(YF_E_INVALID, "%s: bad argument", who);
+    if (!ema_decay_ok(d)) return fail(YF_E_INVALID, "%s: d = %g is not in [0, 1]", who, d);
+    yf::TOptGroup gs[YF_OPT_MAX_GROUPS];
+    long blocks = 0;
+    if (const int rc = opt_multi_check(who, kind, ntensors, d_p, d_g, d_s1, d_s2, sizes, group_of, ngroups, groups, d_table, table_bytes,
+                                       (long)ntensors + n_extra, YF_OPT_EMA_TABLE_ENTRY_BYTES, gs, &blocks))
+        return rc;
+    for (int t = 0; t < ntensors; ++t)
+        if (!d_ema[t] || d_ema[t] == d_p[t]) return fail(YF_E_INVALID, "%s: tensor %d: the EMA pointer is null or the parameter's own", who, t);
+    for (int t = 0; t < n_extra; ++t) {
+        if (!d_extra_src[t] || !d_extra_ema[t] || extra_sizes[t] <= 0 || d_extra_ema[t] == d_extra_src[t])
+            return fail(YF_E_INVALID, "%s: EMA-only tensor %d: null pointer, empty, or the EMA pointer is the source's own", who, t);
+        blocks += (extra_sizes[t] + 255) / 256;
+        if (blocks > 0x7fffffffL) return fail(YF_E_INVALID, "%s: more than 2^31 workgroups", who);
+    }
+    HIP_OK(hipSetDevice(device));
+    if (yf::launch_topt_ema_multi(kind, ntensors, (float* const*)d_p, (const float* const*)d_g, (float* const*)d_s1, (float* const*)d_s2, sizes,
+                                  group_of, first, ngroups, gs, (float* const*)d_ema, n_extra, (const float* const*)d_extra_src,
+                                  (float* const*)d_extra_ema, extra_sizes, d, d_table, h_table_pinned, upload, (hipStream_t)stream))
+        return fail(YF_E_HIP, "%s: the upload of the pointer table failed", who);
+    HIP_OK(hipGetLastError());
+    return YF_OK;
+}
+int yf_train_ema_multi_pinned(int device, int ntensors, const void* const* d_src, void* const* d_ema, const long* sizes, double d, void* d_table,
+                              size_t table_bytes, void* h_table_pinned, int upload, void* stream)
+{
+    static_assert(YF_EMA_TABLE_ENTRY_BYTES == 32, "the kernel's table entry (yf_train_opt_kernels.h)");
+    const char* who = "yf_train_ema_multi";
+    if (!d_src || !d_ema || !sizes || !d_table || ntensors <= 0 || table_bytes < (size_t)ntensors * YF_EMA_TABLE_ENTRY_BYTES)
+        return fail(YF_E_INVALID, "%s: bad argument", who);
+    if (!ema_decay_ok(d)) return fail(YF_E_INVALID, "%s: d = %g is not in [0, 1]", who, d);
+    long blocks = 0;
+    for (int t = 0; t < ntensors; ++t) {
+        if (!d_src[t] || !d_ema[t] || sizes[t] <= 0 || d_ema[t] == d_src[t])
+            return fail(YF_E_INVALID, "%s: tensor %d: null pointer, empty, or the EMA pointer is the source's own", who, t);
+        blocks += (sizes[t] + 255) / 256;
+        if (blocks > 0x7fffffffL) return fail(YF_E_INVALID, "%s: more than 2^31 workgroups", who);
+    }
+    HIP_OK(hipSetDevice(device));
+    if (yf::launch_tema_multi(ntensors, (const float* const*)d_src, (float* const*)d_ema, sizes, d, d_table, h_table_pinned, upload, (hipStream_t)stream))
+        return fail(YF_E_HIP, "%s: the upload of the pointer table failed", who);
     HIP_OK(hipGetLastError());
     return YF_OK;
 }

@@ -589,6 +589,28 @@ int launch_tadam_multi(int nt, float* const* p, const float* const* g, float* co
     return 0;
 }
 
+// the param groups' scalars as the kernels take them: formed in double, rounded once to float like torch's Python-double scalars
+static TSgdGroups sgd_groups(int ngroups, const TOptGroup* groups)
+{
+    TSgdGroups gs = {};
+    for (int i = 0; i < ngroups; ++i) {
+        const TOptGroup& q = groups[i];
+        gs.g[i] = TSgdGroup{(float)q.wd, (float)q.mom, (float)-q.lr,
+                            (q.nesterov ? TOPT_NESTEROV : 0) | (q.wd != 0 ? TOPT_DECAY : 0) | (q.mom != 0 ? TOPT_MOMENTUM : 0)};
+    }
+    return gs;
+}
+static TAdamGroups adam_groups(int ngroups, const TOptGroup* groups)
+{
+    TAdamGroups gs = {};
+    for (int i = 0; i < ngroups; ++i) {
+        const TOptGroup& q = groups[i];
+        const double bc1 = 1.0 - pow(q.b1, (double)q.step), bc2 = 1.0 - pow(q.b2, (double)q.step);
+        gs.g[i] = TAdamGroup{(float)q.wd, (float)(1.0 - q.b1), (float)q.b2, (float)(1.0 - q.b2), (float)q.eps, (float)(q.lr / bc1),
+                             (float)sqrt(bc2), q.wd != 0 ? TOPT_DECAY : 0};
+    }
+    return gs;
+}
 // The same scheme for every tensor of every param group (kind 0 = Adam, 1 = SGD): the table entry names its group and carries the
 // first-step mark; the groups' scalars, formed in double and rounded once to float like torch's Python-double scalars, are kernel
 // arguments.  h_table null: staged from pageable memory on every call, as above.  The caller has checked every argument.
@@ -606,24 +628,62 @@ int launch_topt_multi(int kind, int nt, float* const* p, const float* const* g, 
         blocks += (sizes[t] + 255) / 256;
     }
     if (upload && hipMemcpyAsync(d_table, host, (size_t)nt * sizeof(TOptEntry), hipMemcpyHostToDevice, s) != hipSuccess) return -1;
-    if (kind == 1) {
-        TSgdGroups gs = {};
-        for (int i = 0; i < ngroups; ++i) {
-            const TOptGroup& q = groups[i];
-            gs.g[i] = TSgdGroup{(float)q.wd, (float)q.mom, (float)-q.lr,
-                                (q.nesterov ? TOPT_NESTEROV : 0) | (q.wd != 0 ? TOPT_DECAY : 0) | (q.mom != 0 ? TOPT_MOMENTUM : 0)};
-        }
-        hipLaunchKernelGGL(tsgd_group_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const TOptEntry*)d_table, nt, gs);
-    } else {
-        TAdamGroups gs = {};
-        for (int i = 0; i < ngroups; ++i) {
-            const TOptGroup& q = groups[i];
-            const double bc1 = 1.0 - pow(q.b1, (double)q.step), bc2 = 1.0 - pow(q.b2, (double)q.step);
-            gs.g[i] = TAdamGroup{(float)q.wd, (float)(1.0 - q.b1), (float)q.b2, (float)(1.0 - q.b2), (float)q.eps, (float)(q.lr / bc1),
-                                 (float)sqrt(bc2), q.wd != 0 ? TOPT_DECAY : 0};
-        }
-        hipLaunchKernelGGL(tadam_group_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const TOptEntry*)d_table, nt, gs);
+    if (kind == 1)
+        hipLaunchKernelGGL(tsgd_group_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const TOptEntry*)d_table, nt, sgd_groups(ngroups, groups));
+    else
+        hipLaunchKernelGGL(tadam_group_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const TOptEntry*)d_table, nt, adam_groups(ngroups, groups));
+    return 0;
+}
+
+// launch_topt_multi with yolov5's ModelEMA behind every update (tsgd_group_ema_kernel / tadam_group_ema_kernel): entry t < nt carries
+// ema[t]; the n_extra entries behind them are EMA-only (xsrc -> xema, no gradient).  d = the step's decay, in double; it and 1 - d are
+// rounded once each and are kernel arguments like the groups' scalars.  Table entries are 64 bytes, nt + n_extra of them.
+int launch_topt_ema_multi(int kind, int nt, float* const* p, const float* const* g, float* const* s1, float* const* s2, const long* sizes,
+                          const int* group_of, const int* first, int ngroups, const TOptGroup* groups, float* const* ema, int n_extra,
+                          const float* const* xsrc, float* const* xema, const long* xsizes, double d, void* d_table, void* h_table, int upload,
+                          hipStream_t s)
+{
+    static_assert(sizeof(TOptEmaEntry) == 64, "YF_OPT_EMA_TABLE_ENTRY_BYTES");
+    static thread_local std::vector<TOptEmaEntry> tab;
+    const int total = nt + n_extra;
+    TOptEmaEntry* host = static_cast<TOptEmaEntry*>(h_table);
+    if (!host) { tab.resize(total); host = tab.data(); upload = 1; }
+    long blocks = 0;
+    for (int t = 0; t < nt; ++t) {
+        if (upload)
+            host[t] = TOptEmaEntry{p[t], g[t], s1 ? s1[t] : nullptr, s2 ? s2[t] : nullptr, ema[t], blocks, sizes[t], group_of[t], first ? first[t] : 0};
+        blocks += (sizes[t] + 255) / 256;
     }
+    for (int t = 0; t < n_extra; ++t) {
+        if (upload) host[nt + t] = TOptEmaEntry{const_cast<float*>(xsrc[t]), nullptr, nullptr, nullptr, xema[t], blocks, xsizes[t], 0, 0};
+        blocks += (xsizes[t] + 255) / 256;
+    }
+    if (upload && hipMemcpyAsync(d_table, host, (size_t)total * sizeof(TOptEmaEntry), hipMemcpyHostToDevice, s) != hipSuccess) return -1;
+    const float d_f = (float)d, omd_f = (float)(1.0 - d);
+    if (kind == 1)
+        hipLaunchKernelGGL(tsgd_group_ema_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const TOptEmaEntry*)d_table, total,
+                           sgd_groups(ngroups, groups), d_f, omd_f);
+    else
+        hipLaunchKernelGGL(tadam_group_ema_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const TOptEmaEntry*)d_table, total,
+                           adam_groups(ngroups, groups), d_f, omd_f);
+    return 0;
+}
+
+// the average alone: ema[t] = ema[t] d + (1 - d) src[t] for nt tensors in one launch; 32-byte table entries, the same upload scheme
+int launch_tema_multi(int nt, const float* const* src, float* const* ema, const long* sizes, double d, void* d_table, void* h_table, int upload,
+                      hipStream_t s)
+{
+    static_assert(sizeof(TEmaEntry) == 32, "YF_EMA_TABLE_ENTRY_BYTES");
+    static thread_local std::vector<TEmaEntry> tab;
+    TEmaEntry* host = static_cast<TEmaEntry*>(h_table);
+    if (!host) { tab.resize(nt); host = tab.data(); upload = 1; }
+    long blocks = 0;
+    for (int t = 0; t < nt; ++t) {
+        if (upload) host[t] = TEmaEntry{src[t], ema[t], blocks, sizes[t]};
+        blocks += (sizes[t] + 255) / 256;
+    }
+    if (upload && hipMemcpyAsync(d_table, host, (size_t)nt * sizeof(TEmaEntry), hipMemcpyHostToDevice, s) != hipSuccess) return -1;
+    hipLaunchKernelGGL(tema_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const TEmaEntry*)d_table, nt, (float)d, (float)(1.0 - d));
     return 0;
 }
 

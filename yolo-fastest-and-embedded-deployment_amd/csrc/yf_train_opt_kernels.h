@@ -1,4 +1,4 @@
-// yf_train_opt_kernels.h -- sums of split partial results, channel sums (bias gradients), add / slice, Adam, SGD
+// yf_train_opt_kernels.h -- sums of split partial results, channel sums (bias gradients), add / slice, Adam, SGD, ModelEMA
 // Part of the training-step operators: yf_train_kernels.hip includes the family headers into ONE translation unit, INSIDE namespace yf, so the
 // kernels keep their internal linkage and the launchers in that file see all of them.  Device code: include from there only.
 #pragma once
@@ -126,7 +126,7 @@ struct TSgdGroups { TSgdGroup g[TOPT_MAX_GROUPS]; };
 struct TAdamGroup { float wd, w1, b2, w2, eps, step_size, bc2_sqrt; int flags; };
 struct TAdamGroups { TAdamGroup g[TOPT_MAX_GROUPS]; };
 
-__device__ __forceinline__ TOptEntry topt_entry(const TOptEntry* __restrict__ tab, int nt)
+template <class E> __device__ __forceinline__ E topt_entry(const E* __restrict__ tab, int nt)
 {
     int lo = 0, hi = nt - 1;                                   // the tensor this workgroup belongs to
     while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (tab[mid].block0 <= (long)blockIdx.x) lo = mid; else hi = mid - 1; }
@@ -137,12 +137,9 @@ __device__ __forceinline__ TOptEntry topt_entry(const TOptEntry* __restrict__ ta
 // `add(x, alpha=a)` one fused multiply-add, `buf.mul_(momentum)` a rounded product of its own):
 //   d = g + wd p;  buf = mom buf + d (first step: buf = d);  d = nesterov ? d + mom buf : buf;  p += -lr d
 // The wd == 0 and first-step branches keep signed zeros: fma(0, p, -0.0) and 0 * mom + (-0.0) are +0.0 where torch keeps -0.0.
-__global__ void __launch_bounds__(256) tsgd_group_kernel(const TOptEntry* __restrict__ tab, int nt, TSgdGroups gs)
+// Returns the parameter value it stored (the EMA form below goes on with it).
+template <class E> __device__ __forceinline__ float tsgd_update(const E& e, const TSgdGroup& s, long idx)
 {
-    const TOptEntry e = topt_entry(tab, nt);
-    const long idx = ((long)blockIdx.x - e.block0) * 256 + threadIdx.x;
-    if (idx >= e.n) return;
-    const TSgdGroup s = gs.g[__builtin_amdgcn_readfirstlane(e.group) & (TOPT_MAX_GROUPS - 1)];
     const float pi = e.p[idx];
     float d = e.g[idx];
     if (s.flags & TOPT_DECAY) d = __fmaf_rn(s.wd, pi, d);
@@ -152,21 +149,71 @@ __global__ void __launch_bounds__(256) tsgd_group_kernel(const TOptEntry* __rest
         e.s1[idx] = buf;
         d = (s.flags & TOPT_NESTEROV) ? __fmaf_rn(s.mom, buf, d) : buf;
     }
-    e.p[idx] = __fmaf_rn(s.neg_lr, d, pi);
+    const float pn = __fmaf_rn(s.neg_lr, d, pi);
+    e.p[idx] = pn;
+    return pn;
 }
-
-// torch.optim.Adam with weight_decay (L2: the gradient becomes g + wd p, one fused multiply-add), then tadam_multi_kernel's sequence
-// unchanged -- with wd == 0 its bits.
-__global__ void __launch_bounds__(256) tadam_group_kernel(const TOptEntry* __restrict__ tab, int nt, TAdamGroups gs)
+__global__ void __launch_bounds__(256) tsgd_group_kernel(const TOptEntry* __restrict__ tab, int nt, TSgdGroups gs)
 {
     const TOptEntry e = topt_entry(tab, nt);
     const long idx = ((long)blockIdx.x - e.block0) * 256 + threadIdx.x;
     if (idx >= e.n) return;
-    const TAdamGroup s = gs.g[__builtin_amdgcn_readfirstlane(e.group) & (TOPT_MAX_GROUPS - 1)];
+    tsgd_update(e, gs.g[__builtin_amdgcn_readfirstlane(e.group) & (TOPT_MAX_GROUPS - 1)], idx);
+}
+
+// torch.optim.Adam with weight_decay (L2: the gradient becomes g + wd p, one fused multiply-add), then tadam_multi_kernel's sequence
+// unchanged -- with wd == 0 its bits.  Returns the parameter value it stored.
+template <class E> __device__ __forceinline__ float tadam_update(const E& e, const TAdamGroup& s, long idx)
+{
     float gi = e.g[idx];
     if (s.flags & TOPT_DECAY) gi = __fmaf_rn(s.wd, e.p[idx], gi);
     const float mi = e.s1[idx] + s.w1 * (gi - e.s1[idx]);
     const float vi = e.s2[idx] * s.b2 + (s.w2 * gi) * gi;
     e.s1[idx] = mi; e.s2[idx] = vi;
-    e.p[idx] += -s.step_size * (mi / (sqrtf(vi) / s.bc2_sqrt + s.eps));
+    const float pn = e.p[idx] + -s.step_size * (mi / (sqrtf(vi) / s.bc2_sqrt + s.eps));
+    e.p[idx] = pn;
+    return pn;
+}
+__global__ void __launch_bounds__(256) tadam_group_kernel(const TOptEntry* __restrict__ tab, int nt, TAdamGroups gs)
+{
+    const TOptEntry e = topt_entry(tab, nt);
+    const long idx = ((long)blockIdx.x - e.block0) * 256 + threadIdx.x;
+    if (idx >= e.n) return;
+    tadam_update(e, gs.g[__builtin_amdgcn_readfirstlane(e.group) & (TOPT_MAX_GROUPS - 1)], idx);
+}
+
+// ---- yolov5's ModelEMA (training.ModelEMA): e = e d + (1 - d) p, torch's `v *= d; v += (1 - d) * p` on float32 tensors ----
+// Three separately rounded operations, never contracted into a fused multiply-add (the intrinsics hold that whatever the build's
+// -ffp-contract says); d and 1 - d are formed in double on the host and rounded once each, and travel as kernel arguments.
+__device__ __forceinline__ float tema_update(float e, float p, float d, float omd) { return __fadd_rn(__fmul_rn(e, d), __fmul_rn(omd, p)); }
+
+// The optimizer kernels with the average behind them: the entry gains the EMA pointer, and the value just stored in p goes into it from
+// the register.  An entry without a gradient (g null; wave-uniform, a workgroup lies inside one tensor) is EMA-only: no optimizer
+// arithmetic, p is only read -- the BatchNorm running statistics and parameters without .grad ride along in the same launch.
+struct TOptEmaEntry { float* p; const float* g; float* s1; float* s2; float* ema; long block0; long n; int group; int first; };
+__global__ void __launch_bounds__(256) tsgd_group_ema_kernel(const TOptEmaEntry* __restrict__ tab, int nt, TSgdGroups gs, float d, float omd)
+{
+    const TOptEmaEntry e = topt_entry(tab, nt);
+    const long idx = ((long)blockIdx.x - e.block0) * 256 + threadIdx.x;
+    if (idx >= e.n) return;
+    const float pn = e.g ? tsgd_update(e, gs.g[__builtin_amdgcn_readfirstlane(e.group) & (TOPT_MAX_GROUPS - 1)], idx) : e.p[idx];
+    e.ema[idx] = tema_update(e.ema[idx], pn, d, omd);
+}
+__global__ void __launch_bounds__(256) tadam_group_ema_kernel(const TOptEmaEntry* __restrict__ tab, int nt, TAdamGroups gs, float d, float omd)
+{
+    const TOptEmaEntry e = topt_entry(tab, nt);
+    const long idx = ((long)blockIdx.x - e.block0) * 256 + threadIdx.x;
+    if (idx >= e.n) return;
+    const float pn = e.g ? tadam_update(e, gs.g[__builtin_amdgcn_readfirstlane(e.group) & (TOPT_MAX_GROUPS - 1)], idx) : e.p[idx];
+    e.ema[idx] = tema_update(e.ema[idx], pn, d, omd);
+}
+
+// the average alone, any number of (src, ema, n) tensors in one launch (ModelEMA.update beside a torch.optim optimizer)
+struct TEmaEntry { const float* src; float* ema; long block0; long n; };
+__global__ void __launch_bounds__(256) tema_multi_kernel(const TEmaEntry* __restrict__ tab, int nt, float d, float omd)
+{
+    const TEmaEntry e = topt_entry(tab, nt);
+    const long idx = ((long)blockIdx.x - e.block0) * 256 + threadIdx.x;
+    if (idx >= e.n) return;
+    e.ema[idx] = tema_update(e.ema[idx], e.src[idx], d, omd);
 }

@@ -6,6 +6,7 @@
     loss = sum(model_loss[i](pred[i], targets)[0] ...)   # validation.YOLOLossV3 (yf_train_loss)
     loss.backward()                                      # backward of every layer -> param.grad
     optimizer.step()                                     # training.Adam / training.SGD (yf_train_opt_multi_pinned) -- or any torch optimizer
+    ema.update(model)                                    # opt-in, yolov5's: training.ModelEMA, inside the optimizer's launch (step(ema=...))
 
 `YoloFastest.forward` routes here when the module is in train mode.  Forward and backward of the whole network are ONE C call each
 (`yf_trainer_forward` / `yf_trainer_backward`: the graph walked in C++ over a workspace that is the pass's tape); `model.train_impl =
@@ -443,9 +444,15 @@ class _MultiTensorOptimizer(torch.optim.Optimizer):
         return None
 
     @torch.no_grad()
-    def step(self, closure=None):
+    def step(self, closure=None, ema=None):
+        """`ema` (a ModelEMA; its model: the one it was built from or last updated with): the average is kept inside this step's launch
+        -- ONE yf_train_opt_ema_multi_pinned call in which every optimised tensor carries its EMA pointer and every other floating
+        state-dict entry of the model (BatchNorm running statistics, parameters without .grad) rides along as an EMA-only entry.  A step
+        that needs several launches (mixed devices, Adam step counts) runs them as without `ema` and then `ema.update(model)`, a launch
+        of its own.  Either way every EMA entry moves exactly once, to the bits of `step(); ema.update(model)`."""
         if closure is not None:
             raise NotImplementedError("closure")
+        ema_model = ema._bound_model() if ema is not None else None
         lib = _lib.lib()
         f32 = torch.float32
         name = type(self).__name__
@@ -459,6 +466,8 @@ class _MultiTensorOptimizer(torch.optim.Optimizer):
                 if g is not None:
                     ps.append(p); gs.append(g); gof.append(gi)
         if not ps:
+            if ema is not None:
+                ema.update(ema_model)
             return
         # cached while the same Parameter objects take part: the state tensors, their pointers, the ctypes arrays of everything that does
         # not change between steps (at batch 16 the host, not the GPU, was the slower side of an iteration)
@@ -498,6 +507,12 @@ class _MultiTensorOptimizer(torch.optim.Optimizer):
                 parts.setdefault((q.device, klist[i] if klist else 0), []).append(i)
             launches = [(d, k, idx) for (d, k), idx in parts.items()]
         ng = len(groups)
+        fe = None
+        if ema is not None and launches[0][2] is None:       # the EMA's side of the one launch, kept while neither side's pointers move
+            fe = c.get("ema")
+            if fe is None or fe["pp"] is not c["pp"] or not ema._holds(fe):
+                plan = ema._plan(ema_model)
+                fe = c["ema"] = _ema_fusion(ema, plan, ps, c["pp"]) if plan["device"] == device else None
         for device, step, idx in launches:
             og = (_lib.OptGroup * ng)()                      # per launch: lr is edited between steps, Adam's step differs per launch
             for gi, group in enumerate(groups):
@@ -517,19 +532,30 @@ class _MultiTensorOptimizer(torch.optim.Optimizer):
             # caching allocator hands back every iteration; SGD's first-step marks fall after the first step) -- so a step is normally
             # ONE asynchronous launch and the host runs ahead.
             cache = self.__dict__.setdefault("_tables", {})
-            ent = cache.get((device, m))
+            if fe is not None:
+                ptrs = ptrs + (fe["key"],)
+            tkey = (device, m) if fe is None else ("ema", device, m + fe["nx"])
+            ent = cache.get(tkey)
             if ent is None:
-                nb = _lib.YF_OPT_TABLE_ENTRY_BYTES * m
-                ent = cache[(device, m)] = dict(dev=torch.empty(nb, dtype=torch.uint8, device=device),
-                                                host=torch.empty(nb, dtype=torch.uint8).pin_memory(), key=None, event=None)
+                nb = _lib.YF_OPT_TABLE_ENTRY_BYTES * m if fe is None else _lib.YF_OPT_EMA_TABLE_ENTRY_BYTES * (m + fe["nx"])
+                ent = cache[tkey] = dict(dev=torch.empty(nb, dtype=torch.uint8, device=device),
+                                         host=torch.empty(nb, dtype=torch.uint8).pin_memory(), key=None, event=None)
             upload = ent["key"] != ptrs
             if upload and ent["event"] is not None:
                 ent["event"].synchronize()                   # the previous upload has left the pinned buffer
             dev = device.index if device.index is not None else torch.cuda.current_device()
             stream = torch.cuda.current_stream(device)
-            _lib.check(lib.yf_train_opt_multi_pinned(dev, self._kind, m, arrs[0], arrs[1], arrs[2], arrs[3], arrs[4], arrs[5], arrs[6], ng, og,
-                                                     ent["dev"].data_ptr(), ent["dev"].numel(), ent["host"].data_ptr(), int(upload),
-                                                     ctypes.c_void_p(stream.cuda_stream)))
+            if fe is None:
+                _lib.check(lib.yf_train_opt_multi_pinned(dev, self._kind, m, arrs[0], arrs[1], arrs[2], arrs[3], arrs[4], arrs[5], arrs[6], ng, og,
+                                                         ent["dev"].data_ptr(), ent["dev"].numel(), ent["host"].data_ptr(), int(upload),
+                                                         ctypes.c_void_p(stream.cuda_stream)))
+            else:
+                ema.updates += 1
+                _lib.check(lib.yf_train_opt_ema_multi_pinned(dev, self._kind, m, arrs[0], arrs[1], arrs[2], arrs[3], arrs[4], arrs[5], arrs[6], ng,
+                                                             og, fe["ea"], fe["nx"], fe["xs"], fe["xe"], fe["xn"], ema.decay(ema.updates),
+                                                             ent["dev"].data_ptr(), ent["dev"].numel(), ent["host"].data_ptr(), int(upload),
+                                                             ctypes.c_void_p(stream.cuda_stream)))
+                ema.ema._weights_dirty = True                # the engine folds BatchNorm into a packed blob once: re-pack at the next eval forward
             if upload:
                 ent["key"] = ptrs
                 ent["event"] = torch.cuda.Event()
@@ -537,6 +563,8 @@ class _MultiTensorOptimizer(torch.optim.Optimizer):
         if any(first):
             c["first"] = [0] * n
         self._keep = gs                          # alive until the next step: the launch is asynchronous
+        if ema is not None and fe is None:
+            ema.update(ema_model)
 
 
 class Adam(_MultiTensorOptimizer):
@@ -596,6 +624,192 @@ class SGD(_MultiTensorOptimizer):
             raise ValueError("training.SGD: dampening, maximize and nesterov without momentum are not implemented")
 
 
+def _state_slots(module):
+    """[(state-dict key, the owning module's _parameters / _buffers dict, name)] in state_dict() order.  The dicts, not the tensors, so a
+    replaced tensor (.to(), load_state_dict of a buffer) is still picked up; the module SET is taken to be fixed, as in _structure()."""
+    out = []
+    for prefix, mod in module.named_modules():
+        pre = prefix + "." if prefix else ""
+        out += [(pre + k, mod._parameters, k) for k, v in mod._parameters.items() if v is not None]
+        out += [(pre + k, mod._buffers, k) for k, v in mod._buffers.items() if v is not None and k not in mod._non_persistent_buffers_set]
+    return out
+
+
+def _ema_fusion(ema, plan, ps, pp):
+    """The EMA's part of one fused optimizer launch: the EMA pointer of every optimised tensor `ps`, and the model's remaining floating
+    entries as EMA-only (source, EMA, size) triples -- ctypes arrays, built once per (plan, tensor set) and kept while ModelEMA._holds."""
+    where = {id(t): i for i, t in enumerate(plan["src"])}
+    try:
+        at = [where[id(q)] for q in ps]
+    except KeyError:
+        raise ValueError("step(ema=...): an optimised tensor is no floating state-dict entry of the EMA's model") from None
+    taken = set(at)
+    rest = [i for i in range(len(plan["src"])) if i not in taken]
+    sp, ep, sizes, slots = plan["sp"], plan["ep"], plan["sizes"], plan["slots"]
+    nx = len(rest)
+    key = (tuple(ep[i] for i in at), tuple(sp[i] for i in rest), tuple(ep[i] for i in rest))
+    return dict(of=ema, plan=plan, pp=pp, key=key, nx=nx, rest=[slots[i][1:] for i in rest], ea=(ctypes.c_void_p * len(at))(*key[0]),
+                xs=(ctypes.c_void_p * max(nx, 1))(*key[1]), xe=(ctypes.c_void_p * max(nx, 1))(*key[2]),
+                xn=(ctypes.c_long * max(nx, 1))(*[sizes[i] for i in rest]))
+
+
+class ModelEMA:
+    """yolov5's `ModelEMA(model, decay=0.9999, tau=2000, updates=0)`: an exponential moving average of every floating-point
+    state-dict entry (this network: 256 parameters and 168 BatchNorm running statistics of 508 keys), updated after each optimizer step,
+
+        d = decay * (1 - exp(-updates / tau));   v *= d;   v += (1 - d) * model_value          (float32, three rounded operations)
+
+    Validation and the deployed checkpoint use the average.  `.ema` is a YoloFastest in eval mode holding it (parameters without
+    gradient), built from the model's io_params and state_dict() (of any other module: a deepcopy); `.updates` counts the updates, `.decay(x)` is the ramp.  Integer
+    entries (num_batches_tracked) keep the value they had at construction, as in yolov5.  `update(model)` is ONE launch over all
+    floating entries (yf_train_ema_multi_pinned) where yolov5's loop takes three torch launches per entry; `optimizer.step(ema=...)` of
+    training.SGD / training.Adam keeps it inside the optimizer's own launch.  No CPU path for update()."""
+
+    _KNOBS = ("chunk", "fusion", "lanes", "branches", "split_sums", "post_split", "storage_dtype", "precision")
+
+    def __init__(self, model, decay=0.9999, tau=2000, updates=0):
+        from .model import YoloFastest
+        if not (0.0 <= float(decay) <= 1.0) or not float(tau) > 0 or int(updates) < 0:
+            raise ValueError("ModelEMA: decay in [0, 1], tau > 0 and updates >= 0 (got %r, %r, %r)" % (decay, tau, updates))
+        if isinstance(model, YoloFastest):                   # a new network from the io_params: the model owns engine handles, no deepcopy
+            # its layers draw initial values (overwritten below); the caller's random stream stays where a run without EMA has it, so
+            # train(ema=True) shuffles and augments exactly as train(ema=False) does
+            with torch.random.fork_rng(devices=[]):
+                net = YoloFastest(dict(num_cls=model.num_cls, input_channel=model.input_channel, num_anchors=model.num_anchors,
+                                       gray_bits=model.gray_bits))
+            for k in self._KNOBS:
+                setattr(net, k, getattr(model, k))
+            first = next(model.parameters())
+            net = net.to(device=first.device, dtype=first.dtype)
+        else:                                                # any other module, as yolov5's class does it
+            import copy
+            net = copy.deepcopy(model)
+        self._slots = [(k, d, n) for k, d, n in _state_slots(net) if d[n].is_floating_point()]
+        self._model = self._cache = None
+        self._tables = {}
+        self._bind(model)
+        net.load_state_dict(model.state_dict())
+        for p in net.parameters():
+            p.requires_grad_(False)
+        self.ema = net.eval()
+        self.updates, self._decay, self.tau = int(updates), float(decay), float(tau)
+
+    def decay(self, x):
+        """the decay of update number x: it ramps from 0 to `decay`, so the early averages follow the model"""
+        import math
+        return self._decay * (1 - math.exp(-x / self.tau))
+
+    # -- which model -----------------------------------------------------------------------------
+    def _bind(self, model):
+        """`model` becomes the one update() and step(ema=...) read: its floating state-dict entries must be the EMA's, key for key and
+        shape for shape (checked once per model)."""
+        import weakref
+        slots = model.__dict__.get("_yf_ema_slots")
+        if slots is None:
+            slots = [(k, d, n) for k, d, n in _state_slots(model) if d[n].is_floating_point()]
+        mine = self._slots
+        theirs = {k: tuple(d[n].shape) for k, d, n in slots}
+        if [k for k, _, _ in slots] != [k for k, _, _ in mine]:
+            odd = sorted(set(theirs) ^ {k for k, _, _ in mine})
+            raise ValueError("ModelEMA: the model's floating state-dict keys are not the EMA's (%d against %d; e.g. %s)"
+                             % (len(slots), len(mine), ", ".join(odd[:3]) or "another order"))
+        for k, d, n in mine:
+            if tuple(d[n].shape) != theirs[k]:
+                raise ValueError("ModelEMA: %s is %s in the model and %s in the EMA" % (k, theirs[k], tuple(d[n].shape)))
+        model.__dict__["_yf_ema_slots"] = slots
+        self._model, self._cache = weakref.ref(model), None
+
+    def _bound_model(self):
+        m = self._model() if self._model is not None else None
+        if m is None:
+            raise RuntimeError("ModelEMA: the model it was built from is gone; call update(model) once, or train_step(..., ema=ema)")
+        return m
+
+    def _plan(self, model):
+        """The pointers, sizes and ctypes arrays of one update, cached the way _MultiTensorOptimizer caches its own: rebuilt (a new dict)
+        only when a tensor of either side moved."""
+        if self._model is None or self._model() is not model:
+            self._bind(model)
+        slots = model.__dict__["_yf_ema_slots"]
+        src = [d[n] for _, d, n in slots]
+        sp = tuple(map(torch.Tensor.data_ptr, src))
+        c = self._cache
+        if c is None or c["sp"] != sp or self._moved(c):
+            dst = [d[n] for _, d, n in self._slots]
+            ep = tuple(map(torch.Tensor.data_ptr, dst))
+            f32, device = torch.float32, dst[0].device
+            for t in src + dst:
+                if not t.is_cuda or t.dtype is not f32 or not t.is_contiguous() or t.device != device:
+                    raise RuntimeError("ModelEMA.update (HIP) has no CPU path: contiguous float32 tensors of the model and the EMA on one GPU")
+            n = len(src)
+            sizes = [t.numel() for t in dst]
+            c = self._cache = dict(sp=sp, ep=ep, src=src, dst=dst, slots=slots, sizes=sizes, device=device, n=n, sa=(ctypes.c_void_p * n)(*sp),
+                                   ea=(ctypes.c_void_p * n)(*ep), na=(ctypes.c_long * n)(*sizes))
+        return c
+
+    def _moved(self, c):
+        """Whether `.ema`'s tensors have left the addresses of plan `c`.  `.ema` is this object's own network and its tensors move only all
+        at once (.to(), .half(); load_state_dict copies in place), so the first and the last entry stand for all 424: at batch 16 the
+        host is the slower side of an iteration, and reading every pointer of both networks in every step showed in its time."""
+        (_, d0, n0), (_, d1, n1) = self._slots[0], self._slots[-1]
+        return d0[n0].data_ptr() != c["ep"][0] or d1[n1].data_ptr() != c["ep"][-1]
+
+    def _holds(self, fe):
+        """Whether the fused-launch arrays `fe` (_ema_fusion) still describe this EMA and its model: the plan is the current one, `.ema` has
+        not moved, and the model's EMA-only tensors -- the optimizer has compared the pointers of its own -- are where they were."""
+        return (fe["of"] is self and fe["plan"] is self._cache and not self._moved(fe["plan"])
+                and tuple(map(torch.Tensor.data_ptr, [d[n] for d, n in fe["rest"]])) == fe["key"][1])
+
+    # -- the update ------------------------------------------------------------------------------
+    @torch.no_grad()
+    def update(self, model):
+        """yolov5's `update(model)`: `updates` += 1, then every floating entry in one launch."""
+        c = self._plan(model)
+        device, n = c["device"], c["n"]
+        ent = self._tables.get((device, n))
+        if ent is None:
+            nb = _lib.YF_EMA_TABLE_ENTRY_BYTES * n
+            ent = self._tables[(device, n)] = dict(dev=torch.empty(nb, dtype=torch.uint8, device=device),
+                                                   host=torch.empty(nb, dtype=torch.uint8).pin_memory(), key=None, event=None)
+        key = (c["sp"], c["ep"])
+        upload = ent["key"] != key
+        if upload and ent["event"] is not None:
+            ent["event"].synchronize()                       # the previous upload has left the pinned buffer
+        self.updates += 1
+        stream = torch.cuda.current_stream(device)
+        _lib.check(_lib.lib().yf_train_ema_multi_pinned(device.index if device.index is not None else torch.cuda.current_device(), n, c["sa"],
+                                                        c["ea"], c["na"], self.decay(self.updates), ent["dev"].data_ptr(), ent["dev"].numel(),
+                                                        ent["host"].data_ptr(), int(upload), ctypes.c_void_p(stream.cuda_stream)))
+        if upload:
+            ent["key"] = key
+            ent["event"] = torch.cuda.Event()
+            ent["event"].record(stream)
+        # the easy bug: the engine folds BatchNorm into a packed blob once, and the kernel has just changed the tensors behind its back
+        self.ema._weights_dirty = True
+
+    # -- resuming --------------------------------------------------------------------------------
+    def state_dict(self):
+        """the EMA network's state-dict (508 keys here) plus `updates`"""
+        sd = self.ema.state_dict()
+        sd["updates"] = self.updates
+        return sd
+
+    def load_state_dict(self, state_dict):
+        sd = dict(state_dict)
+        if "updates" not in sd:
+            raise ValueError("ModelEMA.load_state_dict: no 'updates' entry")
+        updates = int(sd.pop("updates"))
+        own = self.ema.state_dict()
+        if set(sd) != set(own):
+            odd = sorted(set(sd) ^ set(own))
+            raise ValueError("ModelEMA.load_state_dict: %d keys against the EMA's %d (e.g. %s)" % (len(sd), len(own), ", ".join(odd[:3])))
+        for k, v in own.items():
+            if tuple(sd[k].shape) != tuple(v.shape):
+                raise ValueError("ModelEMA.load_state_dict: %s is %s, the EMA's is %s" % (k, tuple(sd[k].shape), tuple(v.shape)))
+        self.ema.load_state_dict(sd)                         # (in place, and it drops the packed weights)
+        self.updates = updates
+
+
 def param_groups(model, weight_decay):
     """yolov5's three optimizer groups (its train.py), by module type over named_modules(), in yolov5's order: BatchNorm2d weights (no
     decay), every other module's .weight (Conv2d, ConvTranspose2d; `weight_decay`), every .bias (BatchNorm2d's included; no decay)."""
@@ -614,14 +828,16 @@ def param_groups(model, weight_decay):
     return [{"params": bn}, {"params": w, "weight_decay": weight_decay}, {"params": b}]
 
 
-def train_step(model, model_loss, optimizer, imgs, targets, branch_weight=None):
+def train_step(model, model_loss, optimizer, imgs, targets, branch_weight=None, ema=None):
     """One iteration of train.py:111-132: returns the summed losses [total, x, y, w, h, conf, cls] (total a 0-dim tensor).
     `branch_weight` (a sequence, one factor per head; the reference sums the heads unweighted, :129-130): head i's seven values are
     multiplied by branch_weight[i] before the sum, so the backward reaches head i scaled by it.  With factors other than 1 the heads
     are taken back one at a time over the same tape and `p.grad` accumulates: every gradient is sum_i round(branch_weight[i] * g_i), g_i
     head i's own gradient, added once -- the fp32 backward of a sum of head gradients is not the sum of their backwards (it rounds at
     every accumulation), and only this form is linear in the heads to the last bit.  It costs one backward per head.  None and all-ones
-    are the reference's single backward, bit for bit."""
+    are the reference's single backward, bit for bit.
+    `ema` (a ModelEMA of `model`): updated once behind the optimizer step, yolov5's `optimizer.step(); ema.update(model)` -- inside the
+    optimizer's launch with training.SGD / training.Adam (`optimizer.step(ema=ema)`), as a launch of its own with any other optimizer."""
     optimizer.zero_grad()
     pred = model(imgs)
     if branch_weight is not None and len(branch_weight) != len(pred):
@@ -644,7 +860,15 @@ def train_step(model, model_loss, optimizer, imgs, targets, branch_weight=None):
         finally:
             _KEEP_TAPE[0] -= 1
         heads[-1].backward()                                 # the last one frees the tape
-    optimizer.step()
+    if ema is None:
+        optimizer.step()
+    elif isinstance(optimizer, _MultiTensorOptimizer):
+        if ema._model is None or ema._model() is not model:
+            ema._bind(model)
+        optimizer.step(ema=ema)
+    else:
+        optimizer.step()
+        ema.update(model)
     return losses
 
 
@@ -655,7 +879,7 @@ def cosine_factor(epoch, total_epochs):
 
 
 def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, logger=None, val_match="host", optimizer=None,
-          branch_weight=False):
+          branch_weight=False, ema=False):
     """The reference's `train(params, device, tbwriter)` (train.py:44-160) with the iteration on the GPU kernels of this package.
     Same control flow and arithmetic: one YOLOLossV3 per stride (:50-53), the model from `pretrained_pth` or initialize_weights()
     (:58-65), DataLoader(batch_size, drop_last, shuffle) (:71-73), Adam(lr0, betas (0.9, 0.999), eps 1e-8) (:84), the cosine
@@ -673,6 +897,12 @@ def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, l
     `branch_weight=True` weights the heads' losses by train_params["branch_weight"] (train_step).  The defaults (None, False) read none of
     the three: the reference's Adam on one group, the heads summed unweighted.  The warm-up and the cosine schedule are the reference's in
     every case (yolov5's momentum / bias-lr warm-up is not part of this).
+    `ema=True`, opt-in like these: yolov5's ModelEMA(model), built once the weights are loaded or initialised and updated by every
+    train_step (inside the optimizer's launch); from epoch 5 on validation runs on `ema.ema`, as yolov5 validates its average, and a
+    `YOLO-Fastest_epoch_N_ema.pth` with the average's state-dict (loadable like the other) is written beside each
+    `YOLO-Fastest_epoch_N.pth`, which stays the raw model's.  With several ranks sync_buffers runs on `ema.ema` too -- the gradients are
+    averaged, so the ranks' parameter averages agree, but their running statistics do not; that path needs more than one GPU and has
+    not been run.  With ema=False nothing of this is constructed or read.
     Returns the trained model."""
     import logging
     import os
@@ -715,6 +945,7 @@ def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, l
         from torch.utils.data.distributed import DistributedSampler
         sampler = DistributedSampler(train_dataset, num_replicas=world, rank=rank, shuffle=True, drop_last=True)
         data_parallel(model)
+    model_ema = ModelEMA(model) if ema else None             # (behind data_parallel's broadcast: every rank averages rank 0's start)
     dataloader = DataLoader(train_dataset, batch_size=batch_size, num_workers=0, drop_last=True, pin_memory=True, shuffle=sampler is None,
                             sampler=sampler, collate_fn=validation.collate_fn)
     val = validation.Validation(params=params, logger=logger, dataset=val_dataset, device=device, model_loss=model_loss,
@@ -749,7 +980,9 @@ def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, l
             if iteration <= num_warm:
                 for x in optimizer.param_groups:
                     x["lr"] = np.interp(iteration, [0, num_warm], [0.0, x["initial_lr"] * lf(epoch)])
-            if head_weights is None:
+            if model_ema is not None:
+                losses = train_step(model, model_loss, optimizer, imgs, targets, head_weights, ema=model_ema)
+            elif head_weights is None:
                 losses = train_step(model, model_loss, optimizer, imgs, targets)
             else:
                 losses = train_step(model, model_loss, optimizer, imgs, targets, head_weights)
@@ -772,8 +1005,13 @@ def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, l
         scheduler.step()
         if world > 1:
             sync_buffers(model)                      # validation and the checkpoint see rank 0's running statistics on every rank
+            if model_ema is not None:
+                sync_buffers(model_ema.ema)
+                model_ema.ema._weights_dirty = True
         if epoch > 4 and val is not None:
-            val.get_mAP(epoch=epoch, model=model)
+            val.get_mAP(epoch=epoch, model=model if model_ema is None else model_ema.ema)
         if rank == 0:
             torch.save(model.state_dict(), os.path.join(save_path, "YOLO-Fastest_epoch_{}.pth".format(str(epoch))))
+            if model_ema is not None:
+                torch.save(model_ema.ema.state_dict(), os.path.join(save_path, "YOLO-Fastest_epoch_{}_ema.pth".format(str(epoch))))
     return model
