@@ -191,6 +191,48 @@ int yf_train_head_loss_ex(int device, int H, int W, const float *d_head, int N, 
                           int num_classes, const float *d_targets, int T, double ignore_thres, void *d_work, size_t work_bytes,
                           float *d_losses, float *d_grad_head, void *stream);
 
+/* The same loss with the box regressed as ONE IoU-family term per positive cell in place of the reference's four coordinate terms
+ * (opt-in; darknet's and yolov5's formulation).  yf_train_head_loss_ex's arguments, then box_kind and lambda_box.
+ *   box_kind YF_BOX_REF runs the reference's terms: d_losses, the gradient and the first 6 + C planes are those of
+ *   yf_train_head_loss_ex.  YF_BOX_GIOU / _DIOU / _CIOU, per positive cell (mask == 1 after get_target, which is unchanged: same best
+ *   anchor, same ignore marks, the last target written to a cell wins), in feature-map units relative to the cell's corner, from the
+ *   cell's float32 logits t0..t3 and its float32 anchor (aw, ah), everything widened to double:
+ *     predicted box   px = sigmoid(t0), py = sigmoid(t1), pw = exp(clamp(t2, -C, C)) * aw, ph = exp(clamp(t3, -C, C)) * ah with
+ *                     C = YF_BOX_WH_CLAMP -- a guard, not a tuning knob (exp(1000) is infinite and the term NaN without it); its
+ *                     derivative is 1 on [-C, C] inclusive and 0 outside
+ *     target box      tx, ty (the float32 planes), gw = float32(w * fw), gh = float32(h * fh) of the target that wrote tx
+ *     with eps = 1e-7, corners b?x1 = x - w / 2 and so on, 1 = predicted, 2 = target:
+ *     inter = max(min(b1x2,b2x2) - max(b1x1,b2x1), 0) * max(min(b1y2,b2y2) - max(b1y1,b2y1), 0)
+ *     union = pw*ph + gw*gh - inter + eps              iou = inter / union
+ *     cw = max(b1x2,b2x2) - min(b1x1,b2x1)             ch likewise
+ *     giou = iou - (cw*ch + eps - union) / (cw*ch + eps)
+ *     c2 = cw^2 + ch^2 + eps    rho2 = ((b2x1+b2x2-b1x1-b1x2)^2 + (b2y1+b2y2-b1y1-b1y2)^2) / 4
+ *     diou = iou - rho2 / c2
+ *     v = 4/pi^2 * (atan(gw/(gh+eps)) - atan(pw/(ph+eps)))^2
+ *     alpha = v / (v - iou + 1 + eps), a CONSTANT in the backward (yolov5's no_grad)     ciou = iou - (rho2/c2 + v*alpha)
+ *   box = (1 / E) * sum over the positive cells of (1 - value), E = N*A*fh*fw: the normalisation of the reference's four terms (means
+ *   over all cells of masked values), so the balance against the confidence term stays where it is; 0 without a positive cell.
+ *   total = lambda_box * box + conf + cls, conf and cls exactly those of yf_train_head_loss_ex (cls and total NaN without a positive
+ *   cell, as there).  lambda_box = 5.0 is the sum of the reference's weights on x, y (2.5) and w, h (2.5); nobody has trained with it.
+ *   The term and its derivative are evaluated in double per positive cell and rounded to float32 once, at the gradient store: in
+ *   float32 GIoU's enclosing-area term cancels catastrophically for a clamped, huge box.  Non-positive cells get an exact 0 in channels
+ *   0..3; channels 4.. are yf_train_head_loss_ex's arithmetic, bit for bit.  No atomic feeds the gradient; five launches, as there.
+ *   d_losses float32 [8] = total, box, 0, 0, 0, conf, cls, and in [7] the count of targets the reference cannot index (as above).
+ *   d_work: yf_train_head_loss_box_workspace_bytes bytes, 8-byte aligned: double[16] -- [0] the sum of (1 - value), [1..3] zero,
+ *   [4..8] as above (YF_BOX_REF: all as above) -- then float32 [8 + C][E]: the 6 + C planes above, bit for bit, then gw and gh (written
+ *   for every box_kind, zero at non-positive cells); up to 64 bytes behind them are reserved and not written.
+ *   YF_E_INVALID before any launch for everything yf_train_head_loss_ex refuses, a box_kind outside 0..3 and a lambda_box that is
+ *   negative or not finite; YF_E_WORKSPACE for a workspace smaller than reported. */
+#define YF_BOX_REF 0
+#define YF_BOX_GIOU 1
+#define YF_BOX_DIOU 2
+#define YF_BOX_CIOU 3
+#define YF_BOX_WH_CLAMP 10.0
+int yf_train_head_loss_box_workspace_bytes(int N, int fh, int fw, int num_anchors, int num_classes, size_t *out);
+int yf_train_head_loss_box(int device, int H, int W, const float *d_head, int N, int fh, int fw, const double *anchors, int num_anchors,
+                           int num_classes, const float *d_targets, int T, double ignore_thres, void *d_work, size_t work_bytes,
+                           float *d_losses, float *d_grad_head, void *stream, int box_kind, double lambda_box);
+
 /* Operators of the reference's TRAINING step (second slice): every layer type of YoloFastest in train mode, forward
  * and backward, on NCHW float32 device tensors like the reference's (src/model_training/model/yolo_fastest.py:16-66, train.py:98-160).
  * Per-layer kernels (MFMA GEMMs for the pointwise / dense convs, split reductions added in a fixed order: DESIGN.md section 4) -- not the

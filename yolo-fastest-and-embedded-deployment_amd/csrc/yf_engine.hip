@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/yolo_fastest_hip.h"
+#include "yf_box_term.h"
 #include "yf_kernels.h"
 #include "yf_layers.h"
 
@@ -1354,6 +1355,39 @@ int yf_train_head_loss_ex(int device, int H, int W, const float* d_head, int N, 
     for (int a = 0; a < num_anchors; ++a) { anc[2 * a] = (float)(anchors[2 * a] / stride_w); anc[2 * a + 1] = (float)(anchors[2 * a + 1] / stride_h); }
     yf::launch_train_loss(d_head, N, fh, fw, anc, num_anchors, num_classes, d_targets, T, (float)ignore_thres, d_work, d_losses, d_grad_head,
                           (hipStream_t)stream);
+    HIP_OK(hipGetLastError());
+    return YF_OK;
+}
+
+// The same with the box regressed as one IoU-family term (yolo_fastest_hip.h); box_kind 0 runs the reference's terms.
+int yf_train_head_loss_box_workspace_bytes(int N, int fh, int fw, int num_anchors, int num_classes, size_t* out)
+{
+    if (!out || N <= 0 || fh <= 0 || fw <= 0 || num_anchors < 1 || num_anchors > yf::POST_MAX_ANCHORS || num_classes < 1)
+        return fail(YF_E_INVALID, "yf_train_head_loss_box_workspace_bytes: bad argument");
+    *out = yf::train_loss_box_workspace_bytes(N, fh, fw, num_anchors, num_classes);
+    return YF_OK;
+}
+
+int yf_train_head_loss_box(int device, int H, int W, const float* d_head, int N, int fh, int fw, const double* anchors, int num_anchors,
+                           int num_classes, const float* d_targets, int T, double ignore_thres, void* d_work, size_t work_bytes, float* d_losses,
+                           float* d_grad_head, void* stream, int box_kind, double lambda_box)
+{
+    if (!d_head || !anchors || !d_targets || !d_work || !d_losses || N <= 0 || fh <= 0 || fw <= 0 || T <= 0 || H <= 0 || W <= 0 ||
+        num_anchors < 1 || num_anchors > yf::POST_MAX_ANCHORS || num_classes < 1)
+        return fail(YF_E_INVALID, "yf_train_head_loss_box: bad argument");
+    static_assert((int)yf::BOX_REF == YF_BOX_REF && (int)yf::BOX_GIOU == YF_BOX_GIOU && (int)yf::BOX_DIOU == YF_BOX_DIOU &&
+                  (int)yf::BOX_CIOU == YF_BOX_CIOU && yf::BOX_WH_CLAMP == YF_BOX_WH_CLAMP, "yf_box_term.h and the header agree");
+    if (box_kind < YF_BOX_REF || box_kind > YF_BOX_CIOU) return fail(YF_E_INVALID, "yf_train_head_loss_box: box_kind must be 0 .. 3");
+    if (!(lambda_box >= 0.0 && lambda_box < HUGE_VAL)) return fail(YF_E_INVALID, "yf_train_head_loss_box: lambda_box must be finite and >= 0");
+    if (work_bytes < yf::train_loss_box_workspace_bytes(N, fh, fw, num_anchors, num_classes))
+        return fail(YF_E_WORKSPACE, "yf_train_head_loss_box: workspace too small");
+    if (reinterpret_cast<uintptr_t>(d_work) & 7) return fail(YF_E_INVALID, "yf_train_head_loss_box: workspace must be 8-byte aligned");
+    HIP_OK(hipSetDevice(device));
+    const double stride_h = (double)H / fh, stride_w = (double)W / fw;      // as in yf_train_head_loss_ex
+    float anc[2 * yf::POST_MAX_ANCHORS];
+    for (int a = 0; a < num_anchors; ++a) { anc[2 * a] = (float)(anchors[2 * a] / stride_w); anc[2 * a + 1] = (float)(anchors[2 * a + 1] / stride_h); }
+    yf::launch_train_loss_box(d_head, N, fh, fw, anc, num_anchors, num_classes, d_targets, T, (float)ignore_thres, d_work, d_losses, d_grad_head,
+                              box_kind, lambda_box, (hipStream_t)stream);
     HIP_OK(hipGetLastError());
     return YF_OK;
 }

@@ -340,6 +340,10 @@ void launch_val_match(const float* det, const int32_t* counts, int N, int kmax, 
 size_t train_loss_workspace_bytes(int N, int fh, int fw, int na = 3, int nc = 3);
 void launch_train_loss(const float* head, int N, int fh, int fw, const float* anc, int na, int nc, const float* targets, int T, float ignore_thres,
                        void* work, float* losses, float* grad, hipStream_t s);
+// the same with an IoU-family box term (box_kind: yf_box_term.h's BOX_*; 0 = the reference's terms in the box entry's workspace)
+size_t train_loss_box_workspace_bytes(int N, int fh, int fw, int na, int nc);
+void launch_train_loss_box(const float* head, int N, int fh, int fw, const float* anc, int na, int nc, const float* targets, int T,
+                           float ignore_thres, void* work, float* losses, float* grad, int box_kind, double lambda_box, hipStream_t s);
 // training-step operators (yf_train_kernels.hip): NCHW fp32, correctness-first
 // BatchNorm's partial sums out of the conv's epilogue (the large maps): the caller sets part / cap_bytes (a region no concurrent kernel
 // uses: behind BatchNorm's own megabyte of the scratch), the conv launcher sets count (> 0: it left count pairs per channel in

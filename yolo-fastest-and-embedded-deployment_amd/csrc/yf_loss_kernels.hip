@@ -7,15 +7,20 @@
 // targets IN ORDER (the reference's loop has sequential semantics: a later target overwrites an earlier one in the same cell),
 // and one pass over all cells that accumulates the seven sums in double (block reduction + one atomicAdd per block) and
 // writes the gradient.  The backward of the layers themselves is not part of this slice.
+//
+// yf_train_head_loss_box (opt-in) regresses the box as ONE IoU-family term per positive cell in place of the reference's four
+// (yf_box_term.h): two more target planes, loss_cells_kernel<GRAD, true> and loss_final_box_kernel, the same five launches.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
+#include "yf_box_term.h"
 #include "yf_kernels.h"
 
 namespace yf {
 
 // dense target arrays, per (n, anchor, row, col): mask, noobj, tx, ty, tw, th, tcls0..nc-1   (6 + num_classes planes)
+// yf_train_head_loss_box: two more behind the class planes, gw and gh of the target that wrote tx (feature-map units)
 enum { LT_MASK = 0, LT_NOOBJ, LT_TX, LT_TY, LT_TW, LT_TH, LT_C0 };
 enum { LOSS_MAX_ANCHORS = 8 };
 struct LossAnchors { float w[LOSS_MAX_ANCHORS], h[LOSS_MAX_ANCHORS]; };
@@ -33,7 +38,7 @@ __global__ void loss_init_kernel(float* __restrict__ dense, long E, int planes, 
 // outside the map, or a class outside 0 .. nc-1 (:195 raises IndexError).  Such a target is skipped whole.  (A NEGATIVE index wraps
 // round in the reference; that is not reproduced: it is counted like any other index outside the range.)
 __global__ void loss_targets_kernel(const float* __restrict__ targets, int T, float* __restrict__ dense, long E, int N, int fh, int fw,
-                                    LossAnchors anc, int na, int nc, float ignore_thres, double* __restrict__ acc)
+                                    LossAnchors anc, int na, int nc, float ignore_thres, double* __restrict__ acc, int size_planes)
 {
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= N) return;
@@ -66,6 +71,10 @@ __global__ void loss_targets_kernel(const float* __restrict__ targets, int T, fl
         dense[LT_TW * E + e] = (float)log((double)(gw / aw[best] + 1e-16f));   // :190-191 math.log of the float32 quotient, in double
         dense[LT_TH * E + e] = (float)log((double)(gh / ah[best] + 1e-16f));
         dense[(LT_C0 + c) * E + e] = 1.f;                              // :195 one-hot (accumulates over targets sharing the cell)
+        if (size_planes) {                                             // the box loss's target size: the last target's, like tx
+            dense[(LT_C0 + nc) * E + e] = gw;
+            dense[(LT_C0 + nc + 1) * E + e] = gh;
+        }
     }
 }
 
@@ -75,10 +84,16 @@ __device__ __forceinline__ float bce(float p, float t) { return -(t * fmaxf(logf
 __device__ __forceinline__ float dbce(float p, float t) { return (p - t) / fmaxf((1.f - p) * p, 1e-12f); }
 __device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
 
+// what loss_cells_kernel<GRAD, true> needs on top: the anchors the targets were matched with, which IoU-family term, and its weight
+struct LossBox { LossAnchors anc; int na, kind; double lambda; };
+
 // acc: [0] sum bce x, [1] y, [2] sum (w)^2, [3] h, [4] conf obj, [5] conf noobj, [6] cls, [7] n_pos
-template <bool GRAD>
+// BOX: [0] sum over the positive cells of 1 - value (yf_box_term.h, evaluated in double per positive cell: a float32 evaluation
+// cancels in GIoU's enclosing-area term for a clamped, huge box), [1..3] zero; channels 0..3 of the gradient are lambda / E times
+// its derivative, rounded to float32 once at the store, an exact 0 at every other cell.  Channels 4.. as without BOX.
+template <bool GRAD, bool BOX>
 __global__ void __launch_bounds__(256) loss_cells_kernel(const float* __restrict__ head, const float* __restrict__ dense, long E, int fh, int fw,
-                                                         int nc, double* __restrict__ acc, float* __restrict__ grad)
+                                                         int nc, double* __restrict__ acc, float* __restrict__ grad, LossBox box)
 {
     const int attrs = 5 + nc;
     __shared__ double red[8][4];
@@ -91,11 +106,21 @@ __global__ void __launch_bounds__(256) loss_cells_kernel(const float* __restrict
         const float m = dense[LT_MASK * E + e], nm = dense[LT_NOOBJ * E + e];
         const float px = sigm(t[0]), py = sigm(t[hw]), w = t[2 * hw], h = t[3 * hw], pc = sigm(t[4 * hw]);
         const float tx = dense[LT_TX * E + e], ty = dense[LT_TY * E + e], tw = dense[LT_TW * E + e], th = dense[LT_TH * E + e];
-        s[0] = bce(px * m, tx * m);                          // yolo_loss.py:78-79
-        s[1] = bce(py * m, ty * m);
         const float dw = w * m - tw * m, dh = h * m - th * m;
-        s[2] = dw * dw;                                      // :80-81
-        s[3] = dh * dh;
+        double dbox[4] = {0, 0, 0, 0};                       // BOX: d value / d logit of this cell
+        if constexpr (BOX) {
+            if (m == 1.f) {
+                const int a = (int)(na % box.na);
+                const double tl[4] = {(double)t[0], (double)t[hw], (double)w, (double)h};
+                s[0] = 1.0 - box_term(box.kind, tl, (double)box.anc.w[a], (double)box.anc.h[a], (double)tx, (double)ty,
+                                      (double)dense[(LT_C0 + nc) * E + e], (double)dense[(LT_C0 + nc + 1) * E + e], GRAD ? dbox : nullptr);
+            }
+        } else {
+            s[0] = bce(px * m, tx * m);                      // yolo_loss.py:78-79
+            s[1] = bce(py * m, ty * m);
+            s[2] = dw * dw;                                  // :80-81
+            s[3] = dh * dh;
+        }
         s[4] = bce(pc * m, m);                               // :84
         s[5] = bce(pc * nm, nm * 0.f);
         if (m == 1.f) {                                      // :87 pred_cls[mask == 1]
@@ -106,10 +131,15 @@ __global__ void __launch_bounds__(256) loss_cells_kernel(const float* __restrict
             // acc[7] already holds n_pos (the forward pass ran first); d(total)/d(logit), total = 2.5 (x + y + w + h) + conf + cls
             const float inv = 1.f / (float)E, npos = (float)acc[7];
             float* g = grad + na * attrs * hw + cell;
-            g[0] = 2.5f * inv * dbce(px * m, tx * m) * m * (1.f - px) * px;
-            g[hw] = 2.5f * inv * dbce(py * m, ty * m) * m * (1.f - py) * py;
-            g[2 * hw] = 2.5f * inv * 2.f * dw * m;
-            g[3 * hw] = 2.5f * inv * 2.f * dh * m;
+            if constexpr (BOX) {
+                const double k = -box.lambda / (double)E;    // total = lambda * (1 / E) sum (1 - value) + conf + cls
+                for (int c = 0; c < 4; ++c) g[c * hw] = m == 1.f ? (float)(k * dbox[c]) : 0.f;
+            } else {
+                g[0] = 2.5f * inv * dbce(px * m, tx * m) * m * (1.f - px) * px;
+                g[hw] = 2.5f * inv * dbce(py * m, ty * m) * m * (1.f - py) * py;
+                g[2 * hw] = 2.5f * inv * 2.f * dw * m;
+                g[3 * hw] = 2.5f * inv * 2.f * dh * m;
+            }
             g[4 * hw] = inv * (dbce(pc * m, m) * m + 0.5f * dbce(pc * nm, 0.f) * nm) * (1.f - pc) * pc;
             for (int k = 0; k < nc; ++k) {
                 float gk = 0.f;
@@ -145,26 +175,62 @@ __global__ void loss_final_kernel(const double* __restrict__ acc, long E, int nc
     losses[7] = (float)acc[8];
 }
 
+// losses[0..7] = total, box, 0, 0, 0, conf, cls, targets skipped; total = lambda * box + conf + cls in float32, left to right
+__global__ void loss_final_box_kernel(const double* __restrict__ acc, long E, int nc, float lambda, float* __restrict__ losses)
+{
+    const float lbox = (float)(acc[0] / (double)E);
+    const float lconf = (float)(acc[4] / (double)E) + 0.5f * (float)(acc[5] / (double)E);
+    const float lcls = (float)(acc[6] / ((double)nc * acc[7]));     // no positive cell: nan, as in loss_final_kernel
+    losses[0] = lambda * lbox + lconf * 1.0f + lcls * 1.0f;
+    losses[1] = lbox; losses[2] = 0.f; losses[3] = 0.f; losses[4] = 0.f; losses[5] = lconf; losses[6] = lcls;
+    losses[7] = (float)acc[8];
+}
+
+size_t train_loss_box_workspace_bytes(int N, int fh, int fw, int na, int nc) { return train_loss_workspace_bytes(N, fh, fw, na, nc + 2); }
+
 size_t train_loss_workspace_bytes(int N, int fh, int fw, int na, int nc)
 {
     return ((size_t)(LT_C0 + nc) * N * na * fh * fw) * sizeof(float) + 16 * sizeof(double) + 64;
 }
 
-void launch_train_loss(const float* head, int N, int fh, int fw, const float* anc, int na, int nc, const float* targets, int T, float ignore_thres,
-                       void* work, float* losses, float* grad, hipStream_t s)
+// box_kind < 0: the reference's loss in its own workspace (6 + nc planes).  0 .. 3: the box entry's workspace (8 + nc planes, gw and
+// gh written); 0 still runs the reference's terms, 1 .. 3 the IoU-family one.
+static void launch_loss(const float* head, int N, int fh, int fw, const float* anc, int na, int nc, const float* targets, int T, float ignore_thres,
+                        void* work, float* losses, float* grad, int box_kind, double lambda_box, hipStream_t s)
 {
     const long E = (long)N * na * fh * fw;
-    LossAnchors la{};
+    LossBox lb{};
+    LossAnchors& la = lb.anc;
     for (int a = 0; a < na && a < LOSS_MAX_ANCHORS; ++a) { la.w[a] = anc[2 * a]; la.h[a] = anc[2 * a + 1]; }
+    lb.na = na; lb.kind = box_kind; lb.lambda = lambda_box;
     double* acc = reinterpret_cast<double*>(work);                       // 16 doubles first (8-byte aligned), the dense planes behind
     float* dense = reinterpret_cast<float*>(static_cast<char*>(work) + 16 * sizeof(double));
     const unsigned nb = (unsigned)((E + 255) / 256);
-    hipLaunchKernelGGL(loss_init_kernel, dim3(nb), dim3(256), 0, s, dense, E, LT_C0 + nc, acc);
+    const int sizes = box_kind >= 0;
+    hipLaunchKernelGGL(loss_init_kernel, dim3(nb), dim3(256), 0, s, dense, E, LT_C0 + nc + 2 * sizes, acc);
     hipLaunchKernelGGL(loss_targets_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, s, targets, T, dense, E, N, fh, fw, la, na, nc,
-                       ignore_thres, acc);
-    hipLaunchKernelGGL(loss_cells_kernel<false>, dim3(nb), dim3(256), 0, s, head, dense, E, fh, fw, nc, acc, (float*)nullptr);
-    if (grad) hipLaunchKernelGGL(loss_cells_kernel<true>, dim3(nb), dim3(256), 0, s, head, dense, E, fh, fw, nc, acc, grad);
-    hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(1), 0, s, acc, E, nc, losses);
+                       ignore_thres, acc, sizes);
+    if (box_kind > 0) {
+        hipLaunchKernelGGL((loss_cells_kernel<false, true>), dim3(nb), dim3(256), 0, s, head, dense, E, fh, fw, nc, acc, (float*)nullptr, lb);
+        if (grad) hipLaunchKernelGGL((loss_cells_kernel<true, true>), dim3(nb), dim3(256), 0, s, head, dense, E, fh, fw, nc, acc, grad, lb);
+        hipLaunchKernelGGL(loss_final_box_kernel, dim3(1), dim3(1), 0, s, acc, E, nc, (float)lambda_box, losses);
+    } else {
+        hipLaunchKernelGGL((loss_cells_kernel<false, false>), dim3(nb), dim3(256), 0, s, head, dense, E, fh, fw, nc, acc, (float*)nullptr, lb);
+        if (grad) hipLaunchKernelGGL((loss_cells_kernel<true, false>), dim3(nb), dim3(256), 0, s, head, dense, E, fh, fw, nc, acc, grad, lb);
+        hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(1), 0, s, acc, E, nc, losses);
+    }
+}
+
+void launch_train_loss(const float* head, int N, int fh, int fw, const float* anc, int na, int nc, const float* targets, int T, float ignore_thres,
+                       void* work, float* losses, float* grad, hipStream_t s)
+{
+    launch_loss(head, N, fh, fw, anc, na, nc, targets, T, ignore_thres, work, losses, grad, -1, 0.0, s);
+}
+
+void launch_train_loss_box(const float* head, int N, int fh, int fw, const float* anc, int na, int nc, const float* targets, int T,
+                           float ignore_thres, void* work, float* losses, float* grad, int box_kind, double lambda_box, hipStream_t s)
+{
+    launch_loss(head, N, fh, fw, anc, na, nc, targets, T, ignore_thres, work, losses, grad, box_kind, lambda_box, s);
 }
 
 }  // namespace yf

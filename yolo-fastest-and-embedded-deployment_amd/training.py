@@ -879,7 +879,7 @@ def cosine_factor(epoch, total_epochs):
 
 
 def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, logger=None, val_match="host", optimizer=None,
-          branch_weight=False, ema=False):
+          branch_weight=False, ema=False, box_loss=None, lambda_box=5.0):
     """The reference's `train(params, device, tbwriter)` (train.py:44-160) with the iteration on the GPU kernels of this package.
     Same control flow and arithmetic: one YOLOLossV3 per stride (:50-53), the model from `pretrained_pth` or initialize_weights()
     (:58-65), DataLoader(batch_size, drop_last, shuffle) (:71-73), Adam(lr0, betas (0.9, 0.999), eps 1e-8) (:84), the cosine
@@ -903,6 +903,11 @@ def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, l
     `YOLO-Fastest_epoch_N.pth`, which stays the raw model's.  With several ranks sync_buffers runs on `ema.ema` too -- the gradients are
     averaged, so the ranks' parameter averages agree, but their running statistics do not; that path needs more than one GPU and has
     not been run.  With ema=False nothing of this is constructed or read.
+    `box_loss="giou" | "diou" | "ciou"`, opt-in like these: both heads regress the box of a positive cell as one IoU-family term in place
+    of the reference's four coordinate terms, total = lambda_box * box + conf + cls (validation.YOLOLossV3; yf_train_head_loss_box).
+    lambda_box = 5.0 is the sum of the reference's weights on x, y and on w, h; nobody has trained with it.  tbwriter then gets the
+    scalar `box` in place of `x`, and no `y`, `w`, `h`.  It composes with branch_weight and ema (train_step is unchanged).  The decode
+    stays the reference's, so the checkpoints load into detect.py as before.
     Returns the trained model."""
     import logging
     import os
@@ -928,7 +933,7 @@ def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, l
     total_epochs, batch_size = tp["total_epochs"], tp["batch_size"]
     model = YoloFastest(io).to(device)
     model_loss = [validation.YOLOLossV3(anchors=io["anchors"][i], num_classes=io["num_cls"], input_shape=io["input_shape"], device=device,
-                                        model=model) for i in range(len(io["strides"]))]
+                                        model=model, box_loss=box_loss, lambda_box=lambda_box) for i in range(len(io["strides"]))]
     for ml in model_loss:
         ml.ignore_threshold = tp.get("IOU_loss_thre", 0.5)
     if tp.get("pretrained_pth") and os.path.exists(tp["pretrained_pth"]):
@@ -968,6 +973,8 @@ def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, l
     step_count = 0
     logger.info("Start training.")
     losses_name = ["total_loss", "x", "y", "w", "h", "conf", "cls"]
+    if box_loss is not None:
+        losses_name = ["total_loss", "box", None, None, None, "conf", "cls"]     # [2..4] are zeros then
     for epoch in range(start_epoch, total_epochs):
         model.train()
         if sampler is not None:
@@ -1001,6 +1008,8 @@ def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, l
                     tbwriter.add_scalar("lr", lr, step_count)
                     tbwriter.add_scalar("example/sec", example_per_second, step_count)
                     for i, name in enumerate(losses_name):
+                        if name is None:
+                            continue
                         tbwriter.add_scalar(name, _loss if i == 0 else losses[i], step_count)
         scheduler.step()
         if world > 1:

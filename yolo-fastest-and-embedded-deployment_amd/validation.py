@@ -33,8 +33,15 @@ def _engine(t, H, W, model=None):
     return _model(model).engine(H, W, t.shape[0], t.device)
 
 
+BOX_KINDS = {"giou": 1, "diou": 2, "ciou": 3}        # YF_BOX_GIOU, YF_BOX_DIOU, YF_BOX_CIOU
+
+
 class YOLOLossV3(torch.nn.Module):
-    def __init__(self, anchors, num_classes, input_shape, device, model=None):
+    def __init__(self, anchors, num_classes, input_shape, device, model=None, box_loss=None, lambda_box=5.0):
+        """`box_loss` (opt-in; None = the reference's four coordinate terms, exactly as before): "giou", "diou" or "ciou" regresses the box
+        of a positive cell as one IoU-family term (yf_train_head_loss_box; include/yolo_fastest_hip.h states the definition), and the
+        training loss is lambda_box * box + conf + cls.  lambda_box = 5.0 is the sum of the reference's weights on x, y and on w, h;
+        nobody has trained with it.  The decode (no targets) is the reference's either way."""
         super().__init__()
         # the YoloFastest whose heads this decodes (None: validation.bind's default).  NOT registered as a submodule: the loss object's
         # .train() / .eval() / .to() / state_dict() must not reach into the network (the reference's YOLOLossV3 does not hold the model)
@@ -48,6 +55,12 @@ class YOLOLossV3(torch.nn.Module):
         self.ignore_threshold = 0.5    # config_params["train_params"]["IOU_loss_thre"] (_config.py:45)
         if not (1 <= self.num_anchors <= 8) or int(num_classes) < 1:
             raise ValueError("1..8 anchors and at least one class")
+        if box_loss is not None and box_loss not in BOX_KINDS:
+            raise ValueError("box_loss must be None, \"giou\", \"diou\" or \"ciou\", got %r" % (box_loss,))
+        if not (0.0 <= float(lambda_box) < math.inf):
+            raise ValueError("lambda_box must be finite and >= 0, got %r" % (lambda_box,))
+        self.box_loss = box_loss
+        self.lambda_box = float(lambda_box)
 
     def forward(self, input, targets=None):
         if targets is not None:
@@ -82,15 +95,24 @@ class _TrainLossFn(torch.autograd.Function):
         dev_index = x.device.index if x.device.index is not None else torch.cuda.current_device()
         need = ctypes.c_size_t()
         na, nc = loss_mod.num_anchors, loss_mod.num_classes
-        _lib.check(lib.yf_train_head_loss_workspace_bytes_ex(bs, fh, fw, na, nc, ctypes.byref(need)))
+        box = loss_mod.box_loss
+        if box is None:
+            _lib.check(lib.yf_train_head_loss_workspace_bytes_ex(bs, fh, fw, na, nc, ctypes.byref(need)))
+        else:
+            _lib.check(lib.yf_train_head_loss_box_workspace_bytes(bs, fh, fw, na, nc, ctypes.byref(need)))
         work = torch.empty((need.value + 7) // 8, dtype=torch.float64, device=x.device)     # 8-byte aligned scratch
         losses = torch.empty(8, dtype=torch.float32, device=x.device)
         grad = torch.empty_like(x)
         anc = (ctypes.c_double * (2 * na))(*[float(v) for a in loss_mod.anchors for v in a[:2]])
         stream = torch.cuda.current_stream(x.device).cuda_stream
-        _lib.check(lib.yf_train_head_loss_ex(dev_index, H, W, x.data_ptr(), bs, fh, fw, anc, na, nc, targets.data_ptr(), targets.shape[1],
-                                             float(loss_mod.ignore_threshold), work.data_ptr(), work.numel() * 8, losses.data_ptr(),
-                                             grad.data_ptr(), ctypes.c_void_p(stream)))
+        if box is None:
+            _lib.check(lib.yf_train_head_loss_ex(dev_index, H, W, x.data_ptr(), bs, fh, fw, anc, na, nc, targets.data_ptr(), targets.shape[1],
+                                                 float(loss_mod.ignore_threshold), work.data_ptr(), work.numel() * 8, losses.data_ptr(),
+                                                 grad.data_ptr(), ctypes.c_void_p(stream)))
+        else:
+            _lib.check(lib.yf_train_head_loss_box(dev_index, H, W, x.data_ptr(), bs, fh, fw, anc, na, nc, targets.data_ptr(), targets.shape[1],
+                                                  float(loss_mod.ignore_threshold), work.data_ptr(), work.numel() * 8, losses.data_ptr(),
+                                                  grad.data_ptr(), ctypes.c_void_p(stream), BOX_KINDS[box], loss_mod.lambda_box))
         ctx.save_for_backward(grad)
         ctx.mark_non_differentiable(losses)
         return losses[0].clone(), losses
@@ -103,7 +125,7 @@ class _TrainLossFn(torch.autograd.Function):
 
 def _train_loss(self, input, targets):
     """yolo_loss.py:70-97 with targets: (loss, x, y, w, h, conf, cls) -- loss a 0-dim tensor whose backward() fills input.grad, the rest
-    Python floats like the reference's .item() values.  A target whose cell lies outside the feature map or whose class lies outside
+    Python floats like the reference's .item() values; with `box_loss`: (loss, box, 0.0, 0.0, 0.0, conf, cls).  A target whose cell lies outside the feature map or whose class lies outside
     0 .. num_classes-1 raises IndexError like the reference's indexing (a negative index wraps round there; here it raises too)."""
     if input.dim() != 4 or input.shape[1] != self.num_anchors * self.bbox_attrs:
         raise RuntimeError("input must be [batch, %d x (5 + %d), h, w]" % (self.num_anchors, self.num_classes))   # yolo_loss.py:58's view
