@@ -385,15 +385,13 @@ int launch_tadam_multi(int nt, float* const* p, const float* const* g, float* co
                        double b2, double eps, int step, void* d_table, void* h_table, int upload, hipStream_t s);
 // one param group of launch_topt_multi (the C ABI's yf_opt_group, checked); kind: 0 Adam, 1 SGD; table entries are 56 bytes
 struct TOptGroup { double lr, wd, mom, b1, b2, eps; int nesterov, step; };
+// ... with `ema`: yolov5's ModelEMA behind every update, plus n_extra EMA-only tensors (64-byte table entries, nt + n_extra of them);
+// d: the step's decay, rounded once to float as d and as 1 - d
+struct TOptEma { float* const* ema; int n_extra; const float* const* xsrc; float* const* xema; const long* xsizes; double d; };
 int launch_topt_multi(int kind, int nt, float* const* p, const float* const* g, float* const* s1, float* const* s2, const long* sizes,
-                      const int* group_of, const int* first, int ngroups, const TOptGroup* groups, void* d_table, void* h_table, int upload,
-                      hipStream_t s);
-// ... with yolov5's ModelEMA behind every update, plus n_extra EMA-only tensors (64-byte table entries, nt + n_extra of them), and the
-// average alone over (src, ema, size) triples (32-byte entries); d: the step's decay, rounded once to float as d and as 1 - d
-int launch_topt_ema_multi(int kind, int nt, float* const* p, const float* const* g, float* const* s1, float* const* s2, const long* sizes,
-                          const int* group_of, const int* first, int ngroups, const TOptGroup* groups, float* const* ema, int n_extra,
-                          const float* const* xsrc, float* const* xema, const long* xsizes, double d, void* d_table, void* h_table, int upload,
-                          hipStream_t s);
+                      const int* group_of, const int* first, int ngroups, const TOptGroup* groups, const TOptEma* ema, void* d_table, void* h_table,
+                      int upload, hipStream_t s);
+// the average alone over (src, ema, size) triples (32-byte entries)
 int launch_tema_multi(int nt, const float* const* src, float* const* ema, const long* sizes, double d, void* d_table, void* h_table, int upload,
                       hipStream_t s);
 void launch_tchan_sum(const float* dy, float* out, int N, int C, long HW, hipStream_t s, void* scratch = nullptr /* >= 64 C doubles */);

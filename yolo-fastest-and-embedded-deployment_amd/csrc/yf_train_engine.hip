@@ -348,6 +348,25 @@ int yf_train_unit_backward(int device, int deconv, const float* d_x, const float
     HIP_OK(hipGetLastError());
     return YF_OK;
 }
+// ---- the multi-tensor entries (Adam, SGD, ModelEMA).  What they share; `who` names the entry in the message ----
+// a tensor's workgroups added to *blocks: a launch has fewer than 2^31
+static int add_blocks(const char* who, long size, long* blocks)
+{
+    *blocks += (size + 255) / 256;
+    return *blocks > 0x7fffffffL ? fail(YF_E_INVALID, "%s: more than 2^31 workgroups", who) : YF_OK;
+}
+// an average and the tensor it follows: both there, and not the same one
+static bool ema_pair_ok(const void* src, const void* ema) { return src && ema && ema != src; }
+// the decay of one EMA update: a finite number in [0, 1]
+static bool ema_decay_ok(double d) { return d >= 0.0 && d <= 1.0; }        // (false for NaN)
+// the end of every entry, after all its refusals and hipSetDevice.  launch_rc != 0: the table did not reach the device
+static int table_launched(const char* who, int launch_rc)
+{
+    if (launch_rc) return fail(YF_E_HIP, "%s: the upload of the pointer table failed", who);
+    HIP_OK(hipGetLastError());
+    return YF_OK;
+}
+
 int yf_train_adam_multi(int device, int ntensors, void* const* d_p, const void* const* d_g, void* const* d_m, void* const* d_v, const long* sizes,
                         double lr, double beta1, double beta2, double eps, int step, void* d_table, size_t table_bytes, void* stream)
 {
@@ -363,14 +382,12 @@ int yf_train_adam_multi_pinned(int device, int ntensors, void* const* d_p, const
     for (int t = 0; t < ntensors; ++t)
         if (!d_p[t] || !d_g[t] || !d_m[t] || !d_v[t] || sizes[t] <= 0) return fail(YF_E_INVALID, "yf_train_adam_multi: tensor %d: null pointer or empty", t);
     HIP_OK(hipSetDevice(device));
-    if (yf::launch_tadam_multi(ntensors, (float* const*)d_p, (const float* const*)d_g, (float* const*)d_m, (float* const*)d_v, sizes, lr, beta1, beta2,
-                               eps, step, d_table, h_table_pinned, upload, (hipStream_t)stream))
-        return fail(YF_E_HIP, "yf_train_adam_multi: the upload of the pointer table failed");
-    HIP_OK(hipGetLastError());
-    return YF_OK;
+    return table_launched("yf_train_adam_multi", yf::launch_tadam_multi(ntensors, (float* const*)d_p, (const float* const*)d_g, (float* const*)d_m,
+                                                                        (float* const*)d_v, sizes, lr, beta1, beta2, eps, step, d_table,
+                                                                        h_table_pinned, upload, (hipStream_t)stream));
 }
-// the argument checks yf_train_opt_multi_pinned and yf_train_opt_ema_multi_pinned share (`who` names the entry in the message); fills gs,
-// adds the tensors' workgroups to *blocks.  `entries` table entries of `entry_bytes` must fit.
+// the argument checks yf_train_opt_multi_pinned and yf_train_opt_ema_multi_pinned share; fills gs, adds the tensors' workgroups to
+// *blocks.  `entries` table entries of `entry_bytes` must fit.
 static int opt_multi_check(const char* who, int kind, int ntensors, void* const* d_p, const void* const* d_g, void* const* d_s1, void* const* d_s2,
                            const long* sizes, const int* group_of, int ngroups, const yf_opt_group* groups, void* d_table, size_t table_bytes,
                            long entries, size_t entry_bytes, yf::TOptGroup* gs, long* blocks)
@@ -397,8 +414,7 @@ static int opt_multi_check(const char* who, int kind, int ntensors, void* const*
         const bool need1 = kind == YF_OPT_ADAM || gs[group_of[t]].mom != 0;
         if (!d_p[t] || !d_g[t] || sizes[t] <= 0 || (need1 && (!d_s1 || !d_s1[t])) || (kind == YF_OPT_ADAM && !d_s2[t]))
             return fail(YF_E_INVALID, "%s: tensor %d: null pointer or empty", who, t);
-        *blocks += (sizes[t] + 255) / 256;
-        if (*blocks > 0x7fffffffL) return fail(YF_E_INVALID, "%s: more than 2^31 workgroups", who);
+        if (const int rc = add_blocks(who, sizes[t], blocks)) return rc;
     }
     return YF_OK;
 }
@@ -407,21 +423,17 @@ int yf_train_opt_multi_pinned(int device, int kind, int ntensors, void* const* d
                               size_t table_bytes, void* h_table_pinned, int upload, void* stream)
 {
     static_assert(YF_OPT_MAX_GROUPS == 8 && YF_OPT_TABLE_ENTRY_BYTES == 56, "the kernels' group array and table entry (yf_train_opt_kernels.h)");
+    const char* who = "yf_train_opt_multi";
     yf::TOptGroup gs[YF_OPT_MAX_GROUPS];
     long blocks = 0;
-    if (const int rc = opt_multi_check("yf_train_opt_multi", kind, ntensors, d_p, d_g, d_s1, d_s2, sizes, group_of, ngroups, groups, d_table,
-                                       table_bytes, ntensors, YF_OPT_TABLE_ENTRY_BYTES, gs, &blocks))
+    if (const int rc = opt_multi_check(who, kind, ntensors, d_p, d_g, d_s1, d_s2, sizes, group_of, ngroups, groups, d_table, table_bytes, ntensors,
+                                       YF_OPT_TABLE_ENTRY_BYTES, gs, &blocks))
         return rc;
     HIP_OK(hipSetDevice(device));
-    if (yf::launch_topt_multi(kind, ntensors, (float* const*)d_p, (const float* const*)d_g, (float* const*)d_s1, (float* const*)d_s2, sizes, group_of,
-                              first, ngroups, gs, d_table, h_table_pinned, upload, (hipStream_t)stream))
-        return fail(YF_E_HIP, "yf_train_opt_multi: the upload of the pointer table failed");
-    HIP_OK(hipGetLastError());
-    return YF_OK;
+    return table_launched(who, yf::launch_topt_multi(kind, ntensors, (float* const*)d_p, (const float* const*)d_g, (float* const*)d_s1,
+                                                     (float* const*)d_s2, sizes, group_of, first, ngroups, gs, nullptr, d_table, h_table_pinned,
+                                                     upload, (hipStream_t)stream));
 }
-// the decay of one EMA update: a finite number in [0, 1]
-static bool ema_decay_ok(double d) { return d >= 0.0 && d <= 1.0; }        // (false for NaN)
-
 int yf_train_opt_ema_multi_pinned(int device, int kind, int ntensors, void* const* d_p, const void* const* d_g, void* const* d_s1,
                                   void* const* d_s2, const long* sizes, const int* group_of, const int* first, int ngroups,
                                   const yf_opt_group* groups, void* const* d_ema, int n_extra, const void* const* d_extra_src,
@@ -438,20 +450,17 @@ int yf_train_opt_ema_multi_pinned(int device, int kind, int ntensors, void* cons
                                        (long)ntensors + n_extra, YF_OPT_EMA_TABLE_ENTRY_BYTES, gs, &blocks))
         return rc;
     for (int t = 0; t < ntensors; ++t)
-        if (!d_ema[t] || d_ema[t] == d_p[t]) return fail(YF_E_INVALID, "%s: tensor %d: the EMA pointer is null or the parameter's own", who, t);
+        if (!ema_pair_ok(d_p[t], d_ema[t])) return fail(YF_E_INVALID, "%s: tensor %d: the EMA pointer is null or the parameter's own", who, t);
     for (int t = 0; t < n_extra; ++t) {
-        if (!d_extra_src[t] || !d_extra_ema[t] || extra_sizes[t] <= 0 || d_extra_ema[t] == d_extra_src[t])
+        if (!ema_pair_ok(d_extra_src[t], d_extra_ema[t]) || extra_sizes[t] <= 0)
             return fail(YF_E_INVALID, "%s: EMA-only tensor %d: null pointer, empty, or the EMA pointer is the source's own", who, t);
-        blocks += (extra_sizes[t] + 255) / 256;
-        if (blocks > 0x7fffffffL) return fail(YF_E_INVALID, "%s: more than 2^31 workgroups", who);
+        if (const int rc = add_blocks(who, extra_sizes[t], &blocks)) return rc;
     }
+    const yf::TOptEma ema{(float* const*)d_ema, n_extra, (const float* const*)d_extra_src, (float* const*)d_extra_ema, extra_sizes, d};
     HIP_OK(hipSetDevice(device));
-    if (yf::launch_topt_ema_multi(kind, ntensors, (float* const*)d_p, (const float* const*)d_g, (float* const*)d_s1, (float* const*)d_s2, sizes,
-                                  group_of, first, ngroups, gs, (float* const*)d_ema, n_extra, (const float* const*)d_extra_src,
-                                  (float* const*)d_extra_ema, extra_sizes, d, d_table, h_table_pinned, upload, (hipStream_t)stream))
-        return fail(YF_E_HIP, "%s: the upload of the pointer table failed", who);
-    HIP_OK(hipGetLastError());
-    return YF_OK;
+    return table_launched(who, yf::launch_topt_multi(kind, ntensors, (float* const*)d_p, (const float* const*)d_g, (float* const*)d_s1,
+                                                     (float* const*)d_s2, sizes, group_of, first, ngroups, gs, &ema, d_table, h_table_pinned,
+                                                     upload, (hipStream_t)stream));
 }
 int yf_train_ema_multi_pinned(int device, int ntensors, const void* const* d_src, void* const* d_ema, const long* sizes, double d, void* d_table,
                               size_t table_bytes, void* h_table_pinned, int upload, void* stream)
@@ -463,16 +472,13 @@ int yf_train_ema_multi_pinned(int device, int ntensors, const void* const* d_src
     if (!ema_decay_ok(d)) return fail(YF_E_INVALID, "%s: d = %g is not in [0, 1]", who, d);
     long blocks = 0;
     for (int t = 0; t < ntensors; ++t) {
-        if (!d_src[t] || !d_ema[t] || sizes[t] <= 0 || d_ema[t] == d_src[t])
+        if (!ema_pair_ok(d_src[t], d_ema[t]) || sizes[t] <= 0)
             return fail(YF_E_INVALID, "%s: tensor %d: null pointer, empty, or the EMA pointer is the source's own", who, t);
-        blocks += (sizes[t] + 255) / 256;
-        if (blocks > 0x7fffffffL) return fail(YF_E_INVALID, "%s: more than 2^31 workgroups", who);
+        if (const int rc = add_blocks(who, sizes[t], &blocks)) return rc;
     }
     HIP_OK(hipSetDevice(device));
-    if (yf::launch_tema_multi(ntensors, (const float* const*)d_src, (float* const*)d_ema, sizes, d, d_table, h_table_pinned, upload, (hipStream_t)stream))
-        return fail(YF_E_HIP, "%s: the upload of the pointer table failed", who);
-    HIP_OK(hipGetLastError());
-    return YF_OK;
+    return table_launched(who, yf::launch_tema_multi(ntensors, (const float* const*)d_src, (float* const*)d_ema, sizes, d, d_table, h_table_pinned,
+                                                     upload, (hipStream_t)stream));
 }
 // ---- the trainer: forward and backward of the whole network as one call each ----
 int yf_trainer_create(int H, int W, int device, yf_trainer* out) { return yf_trainer_create_ex(H, W, device, 1, 24, out); }

@@ -558,35 +558,38 @@ void launch_tslice(const float* src, float* dst, int N, int C, long HW, int Cs, 
 {
     hipLaunchKernelGGL(tslice_kernel, dim3(nblk((long)N * C * HW)), dim3(256), 0, s, src, dst, N, C, HW, Cs, sc0, Cd, dc0);
 }
-void launch_tadam(float* p, const float* g, float* m, float* v, long total, double lr, double b1, double b2, double eps, int step, hipStream_t s)
+
+// ---- the multi-tensor launches: host arrays of device pointers -> (one table upload +) one launch ----
+// d_table: device memory for the entries.  h_table: as many bytes of PINNED host memory owned by the caller (one per optimizer), or null.
+// With it the table is written there and uploaded with a truly asynchronous copy, and only when `upload` is set -- the caller sets it
+// when the pointer set changed (p and the state tensors are stable; g is too when the flat gradient buffer is reused) and must not call
+// again with upload = 1 before the previous upload has executed (training.Adam waits on an event).  Without it (null) the table is
+// staged from pageable memory on every call, which the runtime completes before returning -- correct, but it can hold the host until
+// the stream has drained.
+// That staging buffer, one per thread for all launchers.  stage_table fetches it on EVERY call, on purpose: a thread that never touches
+// this library's thread-local block pays for it in every other library's (profiles/opt_table_refactor.txt, section 3).
+static std::vector<char>& pageable_table()
 {
-    const double bc1 = 1.0 - pow(b1, (double)step), bc2 = 1.0 - pow(b2, (double)step);
-    hipLaunchKernelGGL(tadam_kernel, dim3(nblk(total)), dim3(256), 0, s, p, g, m, v, total, (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)eps,
-                       (float)(lr / bc1), (float)sqrt(bc2));
+    static thread_local std::vector<char> tab;
+    return tab;
 }
 
-// host arrays of device pointers -> (one table upload +) one launch.  d_table: at least nt * 48 bytes of device memory.
-// h_table: nt * 48 bytes of PINNED host memory owned by the caller (one per optimizer), or null.  With it the table is written there and
-// uploaded with a truly asynchronous copy, and only when `upload` is set -- the caller sets it when the pointer set changed (p, m, v are
-// stable; g is too when the flat gradient buffer is reused) and must not call again with upload = 1 before the previous upload has
-// executed (training.Adam waits on an event).  Without it (null) the table is staged from pageable memory on every call, which the
-// runtime completes before returning -- correct, but it can hold the host until the stream has drained.
-int launch_tadam_multi(int nt, float* const* p, const float* const* g, float* const* m, float* const* v, const long* sizes, double lr, double b1,
-                       double b2, double eps, int step, void* d_table, void* h_table, int upload, hipStream_t s)
+// Stages n entries of type E: make(t) gives entry t without its first workgroup (the running sum, set here).  -> the launch's
+// workgroups, or -1 when the upload failed.  make(t) runs on every call; without an upload only the entry's size is used.
+template <class E, class F> static long stage_table(int n, F make, void* d_table, void* h_table, int upload, hipStream_t s)
 {
-    static thread_local std::vector<TAdamEntry> tab;
-    TAdamEntry* host = static_cast<TAdamEntry*>(h_table);
-    if (!host) { tab.resize(nt); host = tab.data(); upload = 1; }
+    std::vector<char>& pageable = pageable_table();
+    E* host = static_cast<E*>(h_table);
+    if (!host) { pageable.resize((size_t)n * sizeof(E)); host = reinterpret_cast<E*>(pageable.data()); upload = 1; }
     long blocks = 0;
-    for (int t = 0; t < nt; ++t) {
-        if (upload) host[t] = TAdamEntry{p[t], g[t], m[t], v[t], blocks, sizes[t]};
-        blocks += (sizes[t] + 255) / 256;
+    for (int t = 0; t < n; ++t) {
+        E e = make(t);
+        e.block0 = blocks;
+        if (upload) host[t] = e;
+        blocks += (e.n + 255) / 256;
     }
-    if (upload && hipMemcpyAsync(d_table, host, (size_t)nt * sizeof(TAdamEntry), hipMemcpyHostToDevice, s) != hipSuccess) return -1;
-    const double bc1 = 1.0 - pow(b1, (double)step), bc2 = 1.0 - pow(b2, (double)step);
-    hipLaunchKernelGGL(tadam_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const TAdamEntry*)d_table, nt, (float)(1.0 - b1), (float)b2,
-                       (float)(1.0 - b2), (float)eps, (float)(lr / bc1), (float)sqrt(bc2));
-    return 0;
+    if (upload && hipMemcpyAsync(d_table, host, (size_t)n * sizeof(E), hipMemcpyHostToDevice, s) != hipSuccess) return -1;
+    return blocks;
 }
 
 // the param groups' scalars as the kernels take them: formed in double, rounded once to float like torch's Python-double scalars
@@ -611,78 +614,71 @@ static TAdamGroups adam_groups(int ngroups, const TOptGroup* groups)
     }
     return gs;
 }
-// The same scheme for every tensor of every param group (kind 0 = Adam, 1 = SGD): the table entry names its group and carries the
-// first-step mark; the groups' scalars, formed in double and rounded once to float like torch's Python-double scalars, are kernel
-// arguments.  h_table null: staged from pageable memory on every call, as above.  The caller has checked every argument.
+
+// the older Adam entries (yf_train_adam_step, yf_train_adam_multi*): one group without decay; 48-byte table entries
+static TAdamGroup adam_group(double lr, double b1, double b2, double eps, int step)
+{
+    const TOptGroup q{lr, 0.0, 0.0, b1, b2, eps, 0, step};
+    return adam_groups(1, &q).g[0];
+}
+void launch_tadam(float* p, const float* g, float* m, float* v, long total, double lr, double b1, double b2, double eps, int step, hipStream_t s)
+{
+    hipLaunchKernelGGL(tadam_kernel, dim3(nblk(total)), dim3(256), 0, s, TAdamEntry{p, g, m, v, 0, total}, adam_group(lr, b1, b2, eps, step));
+}
+int launch_tadam_multi(int nt, float* const* p, const float* const* g, float* const* m, float* const* v, const long* sizes, double lr, double b1,
+                       double b2, double eps, int step, void* d_table, void* h_table, int upload, hipStream_t s)
+{
+    static_assert(sizeof(TAdamEntry) == 48, "the table entry of yf_train_adam_multi");
+    const long blocks = stage_table<TAdamEntry>(nt, [&](int t) { return TAdamEntry{p[t], g[t], m[t], v[t], 0, sizes[t]}; }, d_table, h_table, upload, s);
+    if (blocks < 0) return -1;
+    hipLaunchKernelGGL(tadam_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const TAdamEntry*)d_table, nt, adam_group(lr, b1, b2, eps, step));
+    return 0;
+}
+
+// Every tensor of every param group (kind 0 = Adam, 1 = SGD): the table entry names its group and carries the first-step mark; the
+// groups' scalars are kernel arguments.  With `ema` yolov5's ModelEMA follows every update in the same launch: entry t < nt carries
+// ema->ema[t], the ema->n_extra entries behind them are EMA-only (xsrc -> xema, no gradient), and ema->d, the step's decay, and 1 - d are
+// rounded once each and are kernel arguments like the groups' scalars.  The caller has checked every argument.
 int launch_topt_multi(int kind, int nt, float* const* p, const float* const* g, float* const* s1, float* const* s2, const long* sizes,
-                      const int* group_of, const int* first, int ngroups, const TOptGroup* groups, void* d_table, void* h_table, int upload,
-                      hipStream_t s)
+                      const int* group_of, const int* first, int ngroups, const TOptGroup* groups, const TOptEma* ema, void* d_table, void* h_table,
+                      int upload, hipStream_t s)
 {
-    static_assert(sizeof(TOptEntry) == 56, "YF_OPT_TABLE_ENTRY_BYTES");
-    static thread_local std::vector<TOptEntry> tab;
-    TOptEntry* host = static_cast<TOptEntry*>(h_table);
-    if (!host) { tab.resize(nt); host = tab.data(); upload = 1; }
-    long blocks = 0;
-    for (int t = 0; t < nt; ++t) {
-        if (upload) host[t] = TOptEntry{p[t], g[t], s1 ? s1[t] : nullptr, s2 ? s2[t] : nullptr, blocks, sizes[t], group_of[t], first ? first[t] : 0};
-        blocks += (sizes[t] + 255) / 256;
+    static_assert(sizeof(TOptEntry) == 56 && sizeof(TOptEmaEntry) == 64, "YF_OPT_TABLE_ENTRY_BYTES, YF_OPT_EMA_TABLE_ENTRY_BYTES");
+    const dim3 wg(256);
+    if (!ema) {
+        const long blocks = stage_table<TOptEntry>(nt, [&](int t) {
+            return TOptEntry{p[t], g[t], s1 ? s1[t] : nullptr, s2 ? s2[t] : nullptr, 0, sizes[t], group_of[t], first ? first[t] : 0};
+        }, d_table, h_table, upload, s);
+        if (blocks < 0) return -1;
+        if (kind == 1)
+            hipLaunchKernelGGL(tsgd_group_kernel, dim3((unsigned)blocks), wg, 0, s, (const TOptEntry*)d_table, nt, sgd_groups(ngroups, groups));
+        else
+            hipLaunchKernelGGL(tadam_group_kernel, dim3((unsigned)blocks), wg, 0, s, (const TOptEntry*)d_table, nt, adam_groups(ngroups, groups));
+        return 0;
     }
-    if (upload && hipMemcpyAsync(d_table, host, (size_t)nt * sizeof(TOptEntry), hipMemcpyHostToDevice, s) != hipSuccess) return -1;
+    const int total = nt + ema->n_extra;
+    const long blocks = stage_table<TOptEmaEntry>(total, [&](int t) {
+        if (t >= nt) return TOptEmaEntry{const_cast<float*>(ema->xsrc[t - nt]), nullptr, nullptr, nullptr, ema->xema[t - nt], 0, ema->xsizes[t - nt], 0, 0};
+        return TOptEmaEntry{p[t], g[t], s1 ? s1[t] : nullptr, s2 ? s2[t] : nullptr, ema->ema[t], 0, sizes[t], group_of[t], first ? first[t] : 0};
+    }, d_table, h_table, upload, s);
+    if (blocks < 0) return -1;
+    const float d_f = (float)ema->d, omd_f = (float)(1.0 - ema->d);
     if (kind == 1)
-        hipLaunchKernelGGL(tsgd_group_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const TOptEntry*)d_table, nt, sgd_groups(ngroups, groups));
+        hipLaunchKernelGGL(tsgd_group_ema_kernel, dim3((unsigned)blocks), wg, 0, s, (const TOptEmaEntry*)d_table, total, sgd_groups(ngroups, groups),
+                           d_f, omd_f);
     else
-        hipLaunchKernelGGL(tadam_group_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const TOptEntry*)d_table, nt, adam_groups(ngroups, groups));
+        hipLaunchKernelGGL(tadam_group_ema_kernel, dim3((unsigned)blocks), wg, 0, s, (const TOptEmaEntry*)d_table, total, adam_groups(ngroups, groups),
+                           d_f, omd_f);
     return 0;
 }
 
-// launch_topt_multi with yolov5's ModelEMA behind every update (tsgd_group_ema_kernel / tadam_group_ema_kernel): entry t < nt carries
-// ema[t]; the n_extra entries behind them are EMA-only (xsrc -> xema, no gradient).  d = the step's decay, in double; it and 1 - d are
-// rounded once each and are kernel arguments like the groups' scalars.  Table entries are 64 bytes, nt + n_extra of them.
-int launch_topt_ema_multi(int kind, int nt, float* const* p, const float* const* g, float* const* s1, float* const* s2, const long* sizes,
-                          const int* group_of, const int* first, int ngroups, const TOptGroup* groups, float* const* ema, int n_extra,
-                          const float* const* xsrc, float* const* xema, const long* xsizes, double d, void* d_table, void* h_table, int upload,
-                          hipStream_t s)
-{
-    static_assert(sizeof(TOptEmaEntry) == 64, "YF_OPT_EMA_TABLE_ENTRY_BYTES");
-    static thread_local std::vector<TOptEmaEntry> tab;
-    const int total = nt + n_extra;
-    TOptEmaEntry* host = static_cast<TOptEmaEntry*>(h_table);
-    if (!host) { tab.resize(total); host = tab.data(); upload = 1; }
-    long blocks = 0;
-    for (int t = 0; t < nt; ++t) {
-        if (upload)
-            host[t] = TOptEmaEntry{p[t], g[t], s1 ? s1[t] : nullptr, s2 ? s2[t] : nullptr, ema[t], blocks, sizes[t], group_of[t], first ? first[t] : 0};
-        blocks += (sizes[t] + 255) / 256;
-    }
-    for (int t = 0; t < n_extra; ++t) {
-        if (upload) host[nt + t] = TOptEmaEntry{const_cast<float*>(xsrc[t]), nullptr, nullptr, nullptr, xema[t], blocks, xsizes[t], 0, 0};
-        blocks += (xsizes[t] + 255) / 256;
-    }
-    if (upload && hipMemcpyAsync(d_table, host, (size_t)total * sizeof(TOptEmaEntry), hipMemcpyHostToDevice, s) != hipSuccess) return -1;
-    const float d_f = (float)d, omd_f = (float)(1.0 - d);
-    if (kind == 1)
-        hipLaunchKernelGGL(tsgd_group_ema_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const TOptEmaEntry*)d_table, total,
-                           sgd_groups(ngroups, groups), d_f, omd_f);
-    else
-        hipLaunchKernelGGL(tadam_group_ema_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const TOptEmaEntry*)d_table, total,
-                           adam_groups(ngroups, groups), d_f, omd_f);
-    return 0;
-}
-
-// the average alone: ema[t] = ema[t] d + (1 - d) src[t] for nt tensors in one launch; 32-byte table entries, the same upload scheme
+// the average alone: ema[t] = ema[t] d + (1 - d) src[t] for nt tensors in one launch; 32-byte table entries
 int launch_tema_multi(int nt, const float* const* src, float* const* ema, const long* sizes, double d, void* d_table, void* h_table, int upload,
                       hipStream_t s)
 {
     static_assert(sizeof(TEmaEntry) == 32, "YF_EMA_TABLE_ENTRY_BYTES");
-    static thread_local std::vector<TEmaEntry> tab;
-    TEmaEntry* host = static_cast<TEmaEntry*>(h_table);
-    if (!host) { tab.resize(nt); host = tab.data(); upload = 1; }
-    long blocks = 0;
-    for (int t = 0; t < nt; ++t) {
-        if (upload) host[t] = TEmaEntry{src[t], ema[t], blocks, sizes[t]};
-        blocks += (sizes[t] + 255) / 256;
-    }
-    if (upload && hipMemcpyAsync(d_table, host, (size_t)nt * sizeof(TEmaEntry), hipMemcpyHostToDevice, s) != hipSuccess) return -1;
+    const long blocks = stage_table<TEmaEntry>(nt, [&](int t) { return TEmaEntry{src[t], ema[t], 0, sizes[t]}; }, d_table, h_table, upload, s);
+    if (blocks < 0) return -1;
     hipLaunchKernelGGL(tema_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const TEmaEntry*)d_table, nt, (float)d, (float)(1.0 - d));
     return 0;
 }

@@ -84,60 +84,39 @@ __global__ void __launch_bounds__(256) tslice_kernel(const float* __restrict__ s
     dst[(n * Cd + dc0 + c) * HW + i] = src[(n * Cs + sc0 + c) * HW + i];
 }
 
-// torch.optim.Adam (no weight decay, no amsgrad), in the operation order of torch's single-tensor implementation:
-//   m += (1 - b1) (g - m);  v = v b2 + (1 - b2) g g;  p += -(lr / (1 - b1^t)) * (m / (sqrt(v) / sqrt(1 - b2^t) + eps))
-// the scalars are formed in double on the host and rounded once to float, like torch's Python-double scalars.
-__global__ void __launch_bounds__(256) tadam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                                    long total, float w1, float b2, float w2, float eps, float step_size, float bc2_sqrt)
-{
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= total) return;
-    const float gi = g[idx];
-    const float mi = m[idx] + w1 * (gi - m[idx]);
-    const float vi = v[idx] * b2 + (w2 * gi) * gi;
-    m[idx] = mi; v[idx] = vi;
-    p[idx] += -step_size * (mi / (sqrtf(vi) / bc2_sqrt + eps));
-}
+// ---- the multi-tensor launches: training.SGD, training.Adam, training.ModelEMA and the older yf_train_adam_* entries ----
+// Every tensor of a launch is one entry of a pointer table in device memory; a workgroup lies inside one tensor and finds it by bisection
+// over the entries' first workgroup.  The four entry forms differ in what a tensor carries, and each size is part of the C ABI (callers
+// allocate the table by it): state 1 / state 2 are Adam's exp_avg / exp_avg_sq, or SGD's momentum buffer and nothing.
+struct TAdamEntry { float* p; const float* g; float* s1; float* s2; long block0; long n; };                                    // 48: yf_train_adam_multi*
+struct TOptEntry { float* p; const float* g; float* s1; float* s2; long block0; long n; int group; int first; };               // 56: + param group, first step
+struct TOptEmaEntry { float* p; const float* g; float* s1; float* s2; float* ema; long block0; long n; int group; int first; };    // 64: + the EMA pointer
+struct TEmaEntry { const float* src; float* ema; long block0; long n; };                                                       // 32: the average alone
 
-// every parameter tensor in one launch: tab[t] = {p, g, m, v, first block, elements}
-struct TAdamEntry { float* p; const float* g; float* m; float* v; long block0; long n; };
-__global__ void __launch_bounds__(256) tadam_multi_kernel(const TAdamEntry* __restrict__ tab, int nt, float w1, float b2, float w2, float eps,
-                                                          float step_size, float bc2_sqrt)
-{
-    int lo = 0, hi = nt - 1;                                   // the tensor this workgroup belongs to
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (tab[mid].block0 <= (long)blockIdx.x) lo = mid; else hi = mid - 1; }
-    const TAdamEntry e = tab[lo];
-    const long idx = ((long)blockIdx.x - e.block0) * 256 + threadIdx.x;
-    if (idx >= e.n) return;
-    const float gi = e.g[idx];
-    const float mi = e.m[idx] + w1 * (gi - e.m[idx]);
-    const float vi = e.v[idx] * b2 + (w2 * gi) * gi;
-    e.m[idx] = mi; e.v[idx] = vi;
-    e.p[idx] += -step_size * (mi / (sqrtf(vi) / bc2_sqrt + eps));
-}
-
-// ---- every tensor of every param group of an optimizer in one launch (training.SGD, training.Adam) ----
-// tab[t] = {p, g, state 1, state 2, first block, elements, param group, first step}; the groups' scalars are kernel arguments, indexed by
-// the entry's group (wave-uniform: a workgroup lies inside one tensor), so an lr edit between two steps changes no device memory.
-struct TOptEntry { float* p; const float* g; float* s1; float* s2; long block0; long n; int group; int first; };
+// The groups' scalars are kernel arguments, indexed by the entry's group (wave-uniform), so an lr edit between two steps changes no
+// device memory.
 enum { TOPT_MAX_GROUPS = 8, TOPT_NESTEROV = 1, TOPT_DECAY = 2, TOPT_MOMENTUM = 4 };
 struct TSgdGroup { float wd, mom, neg_lr; int flags; };
 struct TSgdGroups { TSgdGroup g[TOPT_MAX_GROUPS]; };
 struct TAdamGroup { float wd, w1, b2, w2, eps, step_size, bc2_sqrt; int flags; };
 struct TAdamGroups { TAdamGroup g[TOPT_MAX_GROUPS]; };
 
-template <class E> __device__ __forceinline__ E topt_entry(const E* __restrict__ tab, int nt)
+// What every multi-tensor kernel starts with: the tensor this workgroup belongs to, its element, the guard of the tensor's last
+// workgroup; then f(entry, element).
+template <class E, class F> __device__ __forceinline__ void tmulti_each(const E* __restrict__ tab, int nt, F f)
 {
-    int lo = 0, hi = nt - 1;                                   // the tensor this workgroup belongs to
+    int lo = 0, hi = nt - 1;
     while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (tab[mid].block0 <= (long)blockIdx.x) lo = mid; else hi = mid - 1; }
-    return tab[lo];
+    const E e = tab[lo];
+    const long idx = ((long)blockIdx.x - e.block0) * 256 + threadIdx.x;
+    if (idx < e.n) f(e, idx);
 }
 
 // torch.optim.SGD(momentum, weight_decay, nesterov; dampening 0), bit for bit (the operations of torch's _single_tensor_sgd, each
 // `add(x, alpha=a)` one fused multiply-add, `buf.mul_(momentum)` a rounded product of its own):
 //   d = g + wd p;  buf = mom buf + d (first step: buf = d);  d = nesterov ? d + mom buf : buf;  p += -lr d
 // The wd == 0 and first-step branches keep signed zeros: fma(0, p, -0.0) and 0 * mom + (-0.0) are +0.0 where torch keeps -0.0.
-// Returns the parameter value it stored (the EMA form below goes on with it).
+// Returns the parameter value it stored (the EMA goes on with it).
 template <class E> __device__ __forceinline__ float tsgd_update(const E& e, const TSgdGroup& s, long idx)
 {
     const float pi = e.p[idx];
@@ -153,16 +132,12 @@ template <class E> __device__ __forceinline__ float tsgd_update(const E& e, cons
     e.p[idx] = pn;
     return pn;
 }
-__global__ void __launch_bounds__(256) tsgd_group_kernel(const TOptEntry* __restrict__ tab, int nt, TSgdGroups gs)
-{
-    const TOptEntry e = topt_entry(tab, nt);
-    const long idx = ((long)blockIdx.x - e.block0) * 256 + threadIdx.x;
-    if (idx >= e.n) return;
-    tsgd_update(e, gs.g[__builtin_amdgcn_readfirstlane(e.group) & (TOPT_MAX_GROUPS - 1)], idx);
-}
 
-// torch.optim.Adam with weight_decay (L2: the gradient becomes g + wd p, one fused multiply-add), then tadam_multi_kernel's sequence
-// unchanged -- with wd == 0 its bits.  Returns the parameter value it stored.
+// torch.optim.Adam (no amsgrad), in the operation order of torch's single-tensor implementation:
+//   m += (1 - b1) (g - m);  v = v b2 + (1 - b2) g g;  p += -(lr / (1 - b1^t)) * (m / (sqrt(v) / sqrt(1 - b2^t) + eps))
+// with weight_decay (L2, not AdamW) the gradient first becomes g + wd p, one fused multiply-add.  The scalars are formed in double on the
+// host and rounded once to float, like torch's Python-double scalars (yf_train_kernels.hip: adam_groups).  The only place Adam's
+// arithmetic is written: every entry point's kernel calls it.  Returns the parameter value it stored.
 template <class E> __device__ __forceinline__ float tadam_update(const E& e, const TAdamGroup& s, long idx)
 {
     float gi = e.g[idx];
@@ -174,46 +149,55 @@ template <class E> __device__ __forceinline__ float tadam_update(const E& e, con
     e.p[idx] = pn;
     return pn;
 }
-__global__ void __launch_bounds__(256) tadam_group_kernel(const TOptEntry* __restrict__ tab, int nt, TAdamGroups gs)
-{
-    const TOptEntry e = topt_entry(tab, nt);
-    const long idx = ((long)blockIdx.x - e.block0) * 256 + threadIdx.x;
-    if (idx >= e.n) return;
-    tadam_update(e, gs.g[__builtin_amdgcn_readfirstlane(e.group) & (TOPT_MAX_GROUPS - 1)], idx);
-}
 
-// ---- yolov5's ModelEMA (training.ModelEMA): e = e d + (1 - d) p, torch's `v *= d; v += (1 - d) * p` on float32 tensors ----
-// Three separately rounded operations, never contracted into a fused multiply-add (the intrinsics hold that whatever the build's
-// -ffp-contract says); d and 1 - d are formed in double on the host and rounded once each, and travel as kernel arguments.
+// yolov5's ModelEMA (training.ModelEMA): e = e d + (1 - d) p, torch's `v *= d; v += (1 - d) * p` on float32 tensors.  Three separately
+// rounded operations, never contracted into a fused multiply-add (the intrinsics hold that whatever the build's -ffp-contract says);
+// d and 1 - d are formed in double on the host and rounded once each, and travel as kernel arguments.
 __device__ __forceinline__ float tema_update(float e, float p, float d, float omd) { return __fadd_rn(__fmul_rn(e, d), __fmul_rn(omd, p)); }
 
-// The optimizer kernels with the average behind them: the entry gains the EMA pointer, and the value just stored in p goes into it from
-// the register.  An entry without a gradient (g null; wave-uniform, a workgroup lies inside one tensor) is EMA-only: no optimizer
-// arithmetic, p is only read -- the BatchNorm running statistics and parameters without .grad ride along in the same launch.
-struct TOptEmaEntry { float* p; const float* g; float* s1; float* s2; float* ema; long block0; long n; int group; int first; };
+// One launch for every tensor of every param group: the update the group type names (TSgdGroups: tsgd_update, TAdamGroups: tadam_update)
+// with the scalars of the entry's group.  EMA: the entry carries the EMA pointer, and the value just stored in p goes into the average
+// from the register.  There an entry without a gradient (g null; wave-uniform) is EMA-only: no optimizer arithmetic, p is only read --
+// the BatchNorm running statistics and parameters without .grad ride along in the same launch.
+template <class E> __device__ __forceinline__ float topt_update(const E& e, const TSgdGroup& s, long idx) { return tsgd_update(e, s, idx); }
+template <class E> __device__ __forceinline__ float topt_update(const E& e, const TAdamGroup& s, long idx) { return tadam_update(e, s, idx); }
+template <bool EMA, class E, class GS>
+__device__ __forceinline__ void topt_multi(const E* __restrict__ tab, int nt, const GS& gs, float d = 0.f, float omd = 0.f)
+{
+    tmulti_each(tab, nt, [&](const E& e, long idx) {
+        const auto& s = gs.g[__builtin_amdgcn_readfirstlane(e.group) & (TOPT_MAX_GROUPS - 1)];
+        if constexpr (EMA) {
+            const float pn = e.g ? topt_update(e, s, idx) : e.p[idx];
+            e.ema[idx] = tema_update(e.ema[idx], pn, d, omd);
+        } else {
+            topt_update(e, s, idx);
+        }
+    });
+}
+__global__ void __launch_bounds__(256) tsgd_group_kernel(const TOptEntry* __restrict__ tab, int nt, TSgdGroups gs) { topt_multi<false>(tab, nt, gs); }
+__global__ void __launch_bounds__(256) tadam_group_kernel(const TOptEntry* __restrict__ tab, int nt, TAdamGroups gs) { topt_multi<false>(tab, nt, gs); }
 __global__ void __launch_bounds__(256) tsgd_group_ema_kernel(const TOptEmaEntry* __restrict__ tab, int nt, TSgdGroups gs, float d, float omd)
 {
-    const TOptEmaEntry e = topt_entry(tab, nt);
-    const long idx = ((long)blockIdx.x - e.block0) * 256 + threadIdx.x;
-    if (idx >= e.n) return;
-    const float pn = e.g ? tsgd_update(e, gs.g[__builtin_amdgcn_readfirstlane(e.group) & (TOPT_MAX_GROUPS - 1)], idx) : e.p[idx];
-    e.ema[idx] = tema_update(e.ema[idx], pn, d, omd);
+    topt_multi<true>(tab, nt, gs, d, omd);
 }
 __global__ void __launch_bounds__(256) tadam_group_ema_kernel(const TOptEmaEntry* __restrict__ tab, int nt, TAdamGroups gs, float d, float omd)
 {
-    const TOptEmaEntry e = topt_entry(tab, nt);
-    const long idx = ((long)blockIdx.x - e.block0) * 256 + threadIdx.x;
-    if (idx >= e.n) return;
-    const float pn = e.g ? tadam_update(e, gs.g[__builtin_amdgcn_readfirstlane(e.group) & (TOPT_MAX_GROUPS - 1)], idx) : e.p[idx];
-    e.ema[idx] = tema_update(e.ema[idx], pn, d, omd);
+    topt_multi<true>(tab, nt, gs, d, omd);
+}
+
+// the older entries: one tensor per launch (yf_train_adam_step; `e.n` elements from workgroup 0), and every tensor of one group
+__global__ void __launch_bounds__(256) tadam_kernel(TAdamEntry e, TAdamGroup s)
+{
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx < e.n) tadam_update(e, s, idx);
+}
+__global__ void __launch_bounds__(256) tadam_multi_kernel(const TAdamEntry* __restrict__ tab, int nt, TAdamGroup s)
+{
+    tmulti_each(tab, nt, [&](const TAdamEntry& e, long idx) { tadam_update(e, s, idx); });
 }
 
 // the average alone, any number of (src, ema, n) tensors in one launch (ModelEMA.update beside a torch.optim optimizer)
-struct TEmaEntry { const float* src; float* ema; long block0; long n; };
 __global__ void __launch_bounds__(256) tema_multi_kernel(const TEmaEntry* __restrict__ tab, int nt, float d, float omd)
 {
-    const TEmaEntry e = topt_entry(tab, nt);
-    const long idx = ((long)blockIdx.x - e.block0) * 256 + threadIdx.x;
-    if (idx >= e.n) return;
-    e.ema[idx] = tema_update(e.ema[idx], e.src[idx], d, omd);
+    tmulti_each(tab, nt, [&](const TEmaEntry& e, long idx) { e.ema[idx] = tema_update(e.ema[idx], e.src[idx], d, omd); });
 }

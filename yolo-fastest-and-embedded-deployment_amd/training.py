@@ -38,7 +38,7 @@ class _Ops:
     def __init__(self, device):
         self.lib = _lib.lib()
         self.device = device
-        self.dev = device.index if device.index is not None else torch.cuda.current_device()
+        self.dev = _device_index(device)
         self.stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
         sc = _scratch(self.lib, device)
         self.scratch, self.scratch_bytes = sc.data_ptr(), sc.numel()
@@ -58,12 +58,16 @@ _SCRATCH = {}
 
 def _scratch(lib, device):
     """The scratch of the split reductions (include/yolo_fastest_hip.h: yf_train_scratch_bytes), one per (device, stream)."""
-    key = (device.index if device.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(device).cuda_stream)
+    key = (_device_index(device), torch.cuda.current_stream(device).cuda_stream)
     if key not in _SCRATCH:
         n = ctypes.c_size_t()
         _lib.check(lib.yf_train_scratch_bytes(ctypes.byref(n)))
         _SCRATCH[key] = torch.empty(n.value, dtype=torch.uint8, device=device)
     return _SCRATCH[key]
+
+
+def _device_index(device):
+    return device.index if device.index is not None else torch.cuda.current_device()
 
 
 def _ptr(t):
@@ -223,7 +227,7 @@ class _Trainer:
 
     def __init__(self, H, W, device, input_channel=1, num_out=24):
         self.lib = _lib.lib()
-        self.dev = device.index if device.index is not None else torch.cuda.current_device()
+        self.dev = _device_index(device)
         self.handle = ctypes.c_void_p()
         _lib.check(self.lib.yf_trainer_create_ex(H, W, self.dev, int(input_channel), int(num_out), ctypes.byref(self.handle)))
         n, nb = ctypes.c_int(), ctypes.c_int()
@@ -259,7 +263,7 @@ class _Trainer:
 
 
 def _trainer(model, H, W, device):
-    key = (H, W, device.index if device.index is not None else torch.cuda.current_device())
+    key = (H, W, _device_index(device))
     cache = model.__dict__.setdefault("_trainers", {})
     if key not in cache:
         cache[key] = _Trainer(H, W, device, model.input_channel, model.num_out)
@@ -420,6 +424,31 @@ def sync_buffers(model, process_group=None):
     return model
 
 
+class _PinnedTable:
+    """The pointer table of one multi-tensor launch: device memory, the pinned host copy the C entry fills and uploads from, the key (the
+    pointers) of the last upload and that upload's event.  A class because the order matters: the C entry rewrites the pinned copy only
+    when told to upload, and may do so only after the previous upload has left it."""
+
+    def __init__(self, nbytes, device):
+        self.dev = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        self.host = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+        self.args = (self.dev.data_ptr(), nbytes, self.host.data_ptr())      # d_table, table_bytes, h_table_pinned of the C entries
+        self.key = self.event = None
+
+    def needs_upload(self, key):
+        """Whether the table on the device is not `key`'s; if so, waits until the previous upload has left the pinned copy."""
+        if self.key == key:
+            return False
+        if self.event is not None:
+            self.event.synchronize()
+        return True
+
+    def uploaded(self, key, stream):
+        """The call on `stream` has uploaded `key`'s table."""
+        self.key, self.event = key, torch.cuda.Event()
+        self.event.record(stream)
+
+
 class _MultiTensorOptimizer(torch.optim.Optimizer):
     """What training.Adam and training.SGD share: `step()` is ONE launch (yf_train_opt_multi_pinned) for every tensor of every param
     group -- the table entry of a tensor names its group, the groups' scalars (lr, weight_decay, ...) travel as kernel arguments -- when
@@ -453,118 +482,111 @@ class _MultiTensorOptimizer(torch.optim.Optimizer):
         if closure is not None:
             raise NotImplementedError("closure")
         ema_model = ema._bound_model() if ema is not None else None
-        lib = _lib.lib()
-        f32 = torch.float32
-        name = type(self).__name__
-        groups = self.param_groups
-        if len(groups) > _lib.YF_OPT_MAX_GROUPS:
-            raise ValueError("training.%s takes up to %d param groups (got %d)" % (name, _lib.YF_OPT_MAX_GROUPS, len(groups)))
-        ps, gs, gof = [], [], []
-        for gi, group in enumerate(groups):
-            for p in group["params"]:
-                g = p.grad
-                if g is not None:
-                    ps.append(p); gs.append(g); gof.append(gi)
+        if len(self.param_groups) > _lib.YF_OPT_MAX_GROUPS:
+            raise ValueError("training.%s takes up to %d param groups (got %d)" % (type(self).__name__, _lib.YF_OPT_MAX_GROUPS, len(self.param_groups)))
+        ps, gs, gof = self._taking_part()
         if not ps:
             if ema is not None:
                 ema.update(ema_model)
             return
-        # cached while the same Parameter objects take part: the state tensors, their pointers, the ctypes arrays of everything that does
-        # not change between steps (at batch 16 the host, not the GPU, was the slower side of an iteration)
-        c = self.__dict__.get("_cache")
-        key = self._shape_key()
-        if c is None or c["gof"] != gof or c["key"] != key or any(a is not b for a, b in zip(c["ps"], ps)):
-            s1, s2, first = [], [], []
-            for q, gi in zip(ps, gof):
-                if not q.is_cuda or q.dtype is not f32 or not q.is_contiguous():
-                    raise RuntimeError("training.%s (HIP) has no CPU path: contiguous float32 GPU parameters only" % name)
-                a, b, f = self._state(q, groups[gi])
-                s1.append(a); s2.append(b); first.append(f)
-            n = len(ps)
-            c = self._cache = dict(ps=list(ps), gof=gof, key=key, sts=[self.state[q] for q in ps], s1=s1, s2=s2, first=first,
-                                   sizes=[q.numel() for q in ps], s1p=tuple(_ptr(t) for t in s1), s2p=tuple(_ptr(t) for t in s2), pp=None)
-            c["full"] = dict(s1a=(ctypes.c_void_p * n)(*c["s1p"]), s2a=(ctypes.c_void_p * n)(*c["s2p"]), sizes=(ctypes.c_long * n)(*c["sizes"]),
-                             gof=(ctypes.c_int * n)(*gof))
-        n = len(ps)
-        pp = tuple(q.data_ptr() for q in ps)
-        if pp != c["pp"]:                                    # (a .to() / .float() of the model moves the parameters)
-            c["pp"], c["full"]["pa"] = pp, (ctypes.c_void_p * n)(*pp)
+        c = self._tensor_set(ps, gof)
         gs = [g if g.is_contiguous() else g.contiguous() for g in gs]
         gp = tuple(g.data_ptr() for g in gs)
-        first = tuple(c["first"])
-        klist = None
-        if self._kind == _lib.YF_OPT_ADAM:
-            klist = []
-            for st in c["sts"]:
-                k = st["step"] = int(st["step"]) + 1         # (a loaded torch.optim.Adam state carries `step` as a tensor)
-                klist.append(k)
-        device = ps[0].device
-        if all(q.device == device for q in ps) and (klist is None or min(klist) == max(klist)):
-            launches = [(device, klist[0] if klist else 0, None)]     # the usual case: one launch for everything
-        else:                                                # mixed devices / step counts: one launch per (device, step)
-            parts = {}
-            for i, q in enumerate(ps):
-                parts.setdefault((q.device, klist[i] if klist else 0), []).append(i)
-            launches = [(d, k, idx) for (d, k), idx in parts.items()]
-        ng = len(groups)
-        fe = None
-        if ema is not None and launches[0][2] is None:       # the EMA's side of the one launch, kept while neither side's pointers move
-            fe = c.get("ema")
-            if fe is None or fe["pp"] is not c["pp"] or not ema._holds(fe):
-                plan = ema._plan(ema_model)
-                fe = c["ema"] = _ema_fusion(ema, plan, ps, c["pp"]) if plan["device"] == device else None
+        launches = self._launches(c, ps)
+        fe = self._ema_side(c, ps, ema, ema_model) if ema is not None and launches[0][2] is None else None
         for device, step, idx in launches:
-            og = (_lib.OptGroup * ng)()                      # per launch: lr is edited between steps, Adam's step differs per launch
-            for gi, group in enumerate(groups):
-                self._scalars(og[gi], group, step)
-            if idx is None:
-                ptrs = (pp, gp, c["s1p"], c["s2p"], first)
-                f = c["full"]
-                arrs = (f["pa"], (ctypes.c_void_p * n)(*gp), f["s1a"], f["s2a"], f["sizes"], f["gof"], (ctypes.c_int * n)(*first))
-                m = n
-            else:
-                m = len(idx)
-                ptrs = tuple(tuple(t[i] for i in idx) for t in (pp, gp, c["s1p"], c["s2p"], first))
-                arrs = tuple((ctypes.c_void_p * m)(*t) for t in ptrs[:4]) + ((ctypes.c_long * m)(*[c["sizes"][i] for i in idx]),
-                                                                             (ctypes.c_int * m)(*[gof[i] for i in idx]), (ctypes.c_int * m)(*ptrs[4]))
-            # The pointer table lives on the device, with a pinned host copy, per (device, tensor count); it is re-uploaded only when
-            # an entry changed (p and the state tensors never do; the gradients are views of the trainer's flat buffer, which the
-            # caching allocator hands back every iteration; SGD's first-step marks fall after the first step) -- so a step is normally
-            # ONE asynchronous launch and the host runs ahead.
-            cache = self.__dict__.setdefault("_tables", {})
-            if fe is not None:
-                ptrs = ptrs + (fe["key"],)
-            tkey = (device, m) if fe is None else ("ema", device, m + fe["nx"])
-            ent = cache.get(tkey)
-            if ent is None:
-                nb = _lib.YF_OPT_TABLE_ENTRY_BYTES * m if fe is None else _lib.YF_OPT_EMA_TABLE_ENTRY_BYTES * (m + fe["nx"])
-                ent = cache[tkey] = dict(dev=torch.empty(nb, dtype=torch.uint8, device=device),
-                                         host=torch.empty(nb, dtype=torch.uint8).pin_memory(), key=None, event=None)
-            upload = ent["key"] != ptrs
-            if upload and ent["event"] is not None:
-                ent["event"].synchronize()                   # the previous upload has left the pinned buffer
-            dev = device.index if device.index is not None else torch.cuda.current_device()
-            stream = torch.cuda.current_stream(device)
-            if fe is None:
-                _lib.check(lib.yf_train_opt_multi_pinned(dev, self._kind, m, arrs[0], arrs[1], arrs[2], arrs[3], arrs[4], arrs[5], arrs[6], ng, og,
-                                                         ent["dev"].data_ptr(), ent["dev"].numel(), ent["host"].data_ptr(), int(upload),
-                                                         ctypes.c_void_p(stream.cuda_stream)))
-            else:
-                ema.updates += 1
-                _lib.check(lib.yf_train_opt_ema_multi_pinned(dev, self._kind, m, arrs[0], arrs[1], arrs[2], arrs[3], arrs[4], arrs[5], arrs[6], ng,
-                                                             og, fe["ea"], fe["nx"], fe["xs"], fe["xe"], fe["xn"], ema.decay(ema.updates),
-                                                             ent["dev"].data_ptr(), ent["dev"].numel(), ent["host"].data_ptr(), int(upload),
-                                                             ctypes.c_void_p(stream.cuda_stream)))
-                ema.ema._weights_dirty = True                # the engine folds BatchNorm into a packed blob once: re-pack at the next eval forward
-            if upload:
-                ent["key"] = ptrs
-                ent["event"] = torch.cuda.Event()
-                ent["event"].record(stream)
-        if any(first):
-            c["first"] = [0] * n
+            self._launch(c, gp, device, step, idx, ema, fe)
+        if any(c["first"]):
+            c["first"] = (0,) * len(ps)
         self._keep = gs                          # alive until the next step: the launch is asynchronous
         if ema is not None and fe is None:
             ema.update(ema_model)
+
+    def _taking_part(self):
+        """-> (parameters with a gradient, their gradients, their group indices), in group order"""
+        ps, gs, gof = [], [], []
+        for gi, group in enumerate(self.param_groups):
+            for p in group["params"]:
+                g = p.grad
+                if g is not None:
+                    ps.append(p); gs.append(g); gof.append(gi)
+        return ps, gs, gof
+
+    def _tensor_set(self, ps, gof):
+        """What does not change between steps while the same Parameter objects take part: the state tensors, their pointers, the ctypes
+        arrays of the one-launch case (at batch 16 the host, not the GPU, was the slower side of an iteration)."""
+        c = self.__dict__.get("_cache")
+        key = self._shape_key()
+        n = len(ps)
+        if c is None or c["gof"] != gof or c["key"] != key or any(a is not b for a, b in zip(c["ps"], ps)):
+            if not all(q.is_cuda and q.dtype is torch.float32 and q.is_contiguous() for q in ps):
+                raise RuntimeError("training.%s (HIP) has no CPU path: contiguous float32 GPU parameters only" % type(self).__name__)
+            s1, s2, first = zip(*[self._state(q, self.param_groups[gi]) for q, gi in zip(ps, gof)])
+            c = self._cache = dict(ps=list(ps), gof=gof, key=key, sts=[self.state[q] for q in ps], s1=s1, s2=s2, first=first,
+                                   sizes=[q.numel() for q in ps], s1p=tuple(_ptr(t) for t in s1), s2p=tuple(_ptr(t) for t in s2), pp=None)
+            c.update(s1a=(ctypes.c_void_p * n)(*c["s1p"]), s2a=(ctypes.c_void_p * n)(*c["s2p"]), na=(ctypes.c_long * n)(*c["sizes"]),
+                     ga=(ctypes.c_int * n)(*gof))
+        pp = tuple(q.data_ptr() for q in ps)
+        if pp != c["pp"]:                                    # (a .to() / .float() of the model moves the parameters)
+            c["pp"], c["pa"] = pp, (ctypes.c_void_p * n)(*pp)
+        return c
+
+    def _launches(self, c, ps):
+        """-> [(device, Adam's step count or 0, the entries' indices or None for all)]; counts Adam's steps"""
+        klist = None
+        if self._kind == _lib.YF_OPT_ADAM:
+            for st in c["sts"]:
+                st["step"] = int(st["step"]) + 1             # (a loaded torch.optim.Adam state carries `step` as a tensor)
+            klist = [st["step"] for st in c["sts"]]
+        device = ps[0].device
+        if all(q.device == device for q in ps) and (klist is None or min(klist) == max(klist)):
+            return [(device, klist[0] if klist else 0, None)]     # the usual case: one launch for everything
+        parts = {}                                           # mixed devices / step counts: one launch per (device, step)
+        for i, q in enumerate(ps):
+            parts.setdefault((q.device, klist[i] if klist else 0), []).append(i)
+        return [(d, k, idx) for (d, k), idx in parts.items()]
+
+    def _ema_side(self, c, ps, ema, ema_model):
+        """The EMA's side of the one launch (_ema_fusion), kept while neither side's pointers move; None when the EMA lives elsewhere"""
+        fe = c.get("ema")
+        if fe is None or fe["pp"] is not c["pp"] or not ema._holds(fe):
+            plan = ema._plan(ema_model)
+            fe = c["ema"] = _ema_fusion(ema, plan, ps, c["pp"]) if plan["device"] == ps[0].device else None
+        return fe
+
+    def _launch(self, c, gp, device, step, idx, ema, fe):
+        """One C call: the entries `idx` (None: all) on `device`, with the EMA's side `fe` behind them"""
+        groups, first, ng = self.param_groups, c["first"], len(self.param_groups)
+        og = (_lib.OptGroup * ng)()                          # per launch: lr is edited between steps, Adam's step differs per launch
+        for gi, group in enumerate(groups):
+            self._scalars(og[gi], group, step)
+        if idx is None:
+            m = len(gp)
+            ptrs = (c["pp"], gp, c["s1p"], c["s2p"], first)
+            arrs = (c["pa"], (ctypes.c_void_p * m)(*gp), c["s1a"], c["s2a"], c["na"], c["ga"], (ctypes.c_int * m)(*first))
+        else:
+            m = len(idx)
+            ptrs = tuple(tuple(t[i] for i in idx) for t in (c["pp"], gp, c["s1p"], c["s2p"], first))
+            arrs = tuple((ctypes.c_void_p * m)(*t) for t in ptrs[:4]) + ((ctypes.c_long * m)(*[c["sizes"][i] for i in idx]),
+                                                                         (ctypes.c_int * m)(*[c["gof"][i] for i in idx]), (ctypes.c_int * m)(*ptrs[4]))
+        # The pointer table lives on the device, with a pinned host copy, per (device, tensor count); it is re-uploaded only when
+        # an entry changed (p and the state tensors never do; the gradients are views of the trainer's flat buffer, which the
+        # caching allocator hands back every iteration; SGD's first-step marks fall after the first step) -- so a step is normally
+        # ONE asynchronous launch and the host runs ahead.
+        tables = self.__dict__.setdefault("_tables", {})
+        fn, mid, tkey, nb = _lib.lib().yf_train_opt_multi_pinned, (), (device, m), _lib.YF_OPT_TABLE_ENTRY_BYTES * m
+        if fe is not None:                                   # the same call with the EMA's arguments in the middle, and its own table
+            ema.updates += 1
+            ptrs, tkey, nb = ptrs + (fe["key"],), ("ema", device, m + fe["nx"]), _lib.YF_OPT_EMA_TABLE_ENTRY_BYTES * (m + fe["nx"])
+            fn, mid = _lib.lib().yf_train_opt_ema_multi_pinned, (fe["ea"], fe["nx"], fe["xs"], fe["xe"], fe["xn"], ema.decay(ema.updates))
+        table = tables.get(tkey) or tables.setdefault(tkey, _PinnedTable(nb, device))
+        upload = table.needs_upload(ptrs)
+        stream = torch.cuda.current_stream(device)
+        _lib.check(fn(_device_index(device), self._kind, m, *arrs, ng, og, *mid, *table.args, int(upload), ctypes.c_void_p(stream.cuda_stream)))
+        if upload:
+            table.uploaded(ptrs, stream)
+        if fe is not None:
+            ema.ema._weights_dirty = True                    # the engine folds BatchNorm into a packed blob once: re-pack at the next eval forward
 
 
 class Adam(_MultiTensorOptimizer):
@@ -766,24 +788,15 @@ class ModelEMA:
         """yolov5's `update(model)`: `updates` += 1, then every floating entry in one launch."""
         c = self._plan(model)
         device, n = c["device"], c["n"]
-        ent = self._tables.get((device, n))
-        if ent is None:
-            nb = _lib.YF_EMA_TABLE_ENTRY_BYTES * n
-            ent = self._tables[(device, n)] = dict(dev=torch.empty(nb, dtype=torch.uint8, device=device),
-                                                   host=torch.empty(nb, dtype=torch.uint8).pin_memory(), key=None, event=None)
+        table = self._tables.get((device, n)) or self._tables.setdefault((device, n), _PinnedTable(_lib.YF_EMA_TABLE_ENTRY_BYTES * n, device))
         key = (c["sp"], c["ep"])
-        upload = ent["key"] != key
-        if upload and ent["event"] is not None:
-            ent["event"].synchronize()                       # the previous upload has left the pinned buffer
+        upload = table.needs_upload(key)
         self.updates += 1
         stream = torch.cuda.current_stream(device)
-        _lib.check(_lib.lib().yf_train_ema_multi_pinned(device.index if device.index is not None else torch.cuda.current_device(), n, c["sa"],
-                                                        c["ea"], c["na"], self.decay(self.updates), ent["dev"].data_ptr(), ent["dev"].numel(),
-                                                        ent["host"].data_ptr(), int(upload), ctypes.c_void_p(stream.cuda_stream)))
+        _lib.check(_lib.lib().yf_train_ema_multi_pinned(_device_index(device), n, c["sa"], c["ea"], c["na"], self.decay(self.updates), *table.args,
+                                                        int(upload), ctypes.c_void_p(stream.cuda_stream)))
         if upload:
-            ent["key"] = key
-            ent["event"] = torch.cuda.Event()
-            ent["event"].record(stream)
+            table.uploaded(key, stream)
         # the easy bug: the engine folds BatchNorm into a packed blob once, and the kernel has just changed the tensors behind its back
         self.ema._weights_dirty = True
 
