@@ -162,6 +162,29 @@ int yf_val_nms_ex(yf_handle h, const float *d_pred, int N, int M, int num_classe
 int yf_val_match(int device, const float *d_det, const int32_t *d_counts, int N, int K_max, const float *d_targets, int T, double iou_thres,
                  const int64_t *d_base, int64_t *d_next, int32_t *d_records, int64_t cap, void *stream);
 
+/* The same detections scored as yolov5 scores them (its val.py process_batch, v6.1 and later, where the second re-sort by IoU is commented
+ * out), at num_thresholds IoU thresholds in one launch per batch.  Not in the reference; yf_val_match above is untouched.
+ *   d_det, d_counts, d_targets, N, K_max, T as for yf_val_match (detections in slot order, a row is a target only with marker > 1), but
+ *       T <= 512: an image's winner table int32 [num_thresholds][T] sits in LDS.
+ *   iou_thresholds: HOST double[num_thresholds], 1 <= num_thresholds <= 16, each cast to float; every one finite, as a float too.
+ *   IoU = yolov5's box_iou in fp32, no +1: iw = clamp0(min(d.x2, t.x2) - max(d.x1, t.x1)), ih likewise, inter = iw * ih,
+ *       iou = inter / ((area_t + area_d) - inter + 1e-7f), area = (x2 - x1) * (y2 - y1); min, max and clamp return NaN as torch does.
+ *   Best target b(k) of detection k: the target of class == class_pred (compared as floats) with the largest non-NaN IoU, the lowest index
+ *       among equals; none if there is no such target.  It does not depend on the threshold.
+ *   At threshold j, k is a candidate if iou(k, b(k)) >= (float)iou_thresholds[j]; among the candidates that share a target the lowest
+ *       slot k wins, the others get no hit at j.  Bit j of a detection's hit mask is set iff it is the winner of its target at j.
+ *       Where no detection has two same-class targets at equal IoU this is process_batch's result exactly; on such ties yolov5's own result
+ *       depends on numpy's unstable default sort, and the lowest-index rule is this library's definition.
+ *   d_records int32 [cap,4]: one record per detection = (obj_conf as float32 bits, class_conf as float32 bits, (int)class_pred, hit mask),
+ *       in image, slot order; cursor (d_base, d_next), cap and the clipping of the counts exactly as for yf_val_match.
+ *   The result does not depend on the order the hardware runs anything in.  Stream-ordered, no allocation, no synchronisation, plain
+ *   vector stores and LDS atomics only.
+ *   YF_E_INVALID before any launch: a null pointer, N < 1, K_max < 1, T < 0 or > 512, cap < 0, num_thresholds < 1 or > 16, a threshold
+ *   that is NaN or infinite (as a double or once cast to float), d_next == d_base. */
+int yf_val_match_iouv(int device, const float *d_det, const int32_t *d_counts, int N, int K_max, const float *d_targets, int T,
+                      const double *iou_thresholds, int num_thresholds, const int64_t *d_base, int64_t *d_next, int32_t *d_records,
+                      int64_t cap, void *stream);
+
 /* The loss end of the reference's training step (first slice; the layers' backward is not part of it):
  *   yf_train_loss = YOLOLossV3.forward(input, targets) for ONE head   src/model_training/loss/yolo_loss.py:48-97 (+ get_target :144-196)
  *                   and, if d_grad_head is not NULL, d(total loss)/d(input): what loss.backward() (train.py:131) leaves in input.grad.

@@ -1,0 +1,96 @@
+#!/usr/bin/env python3
+"""Validation.get_metrics wall time, match="host" against match="device" (validation.py, val_match_iouv_kernel).  GPU box:
+    python tools/val_metrics_bench.py    the VOC fixture tree (tests/golden/voc, 20 frames) 26 times behind a wrapping data set: 520
+                                         images, of which a get_metrics sees 512 (32 whole batches; the loader drops the last 8),
+                                         DetectDataset(cache="device"), the shipped 256x320 weights, batch 16, yolov5's conf_thres 0.001
+                                         and ten IoU thresholds; one untimed round, then three timed rounds with the two modes in turn,
+                                         in one process.  Checks that both modes return the same dict, prints both series (seconds per
+                                         get_metrics), the ratio of their medians, the number of detections matched and one JSON line."""
+import argparse
+import json
+import logging
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+import voc_tree  # noqa: E402
+import yolo_fastest_amd as yf  # noqa: E402
+from yolo_fastest_amd import validation as V  # noqa: E402
+from yolo_fastest_amd.dataset import DetectDataset  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--images", type=int, default=512, help="at least this many images per get_metrics")
+ap.add_argument("--batch", type=int, default=16)
+ap.add_argument("--rounds", type=int, default=3)
+a = ap.parse_args()
+dev = torch.device("cuda:0")
+WEIGHTS = os.path.join(ROOT, "yolo-fastest-and-embedded-deployment_amd", "assets", "weights", "yolo_fastest_256x320_epoch28.pth")
+
+
+class Repeated(torch.utils.data.Dataset):
+    """`times` passes over a DetectDataset as one data set (whole batches through its __getitems__)"""
+
+    def __init__(self, ds, times):
+        self.ds, self.times = ds, times
+
+    def __len__(self):
+        return len(self.ds) * self.times
+
+    def __getitem__(self, i):
+        return self.ds[i % len(self.ds)]
+
+    def __getitems__(self, idx):
+        return self.ds.__getitems__([i % len(self.ds) for i in idx])
+
+
+def main():
+    log = logging.getLogger("val-metrics-bench")
+    log.addHandler(logging.NullHandler())
+    log.propagate = False
+    io = yf.io_params_for(256)
+    model = yf.YoloFastest(io).to(dev).eval()
+    model.load_state_dict(torch.load(WEIGHTS, map_location=dev))
+    params = {"train_params": {"batch_size": a.batch, "IOU_val_thre": 0.5},
+              "io_params": dict(io, class_names=["carrier", "defender", "destroyer"])}
+    with tempfile.TemporaryDirectory() as tmp:
+        trees = voc_tree.make_trees(tmp)
+        base = DetectDataset(io["input_shape"], [512, 640, 3], log, aug_params=voc_tree.aug_params(trees), max_boxes=64, device=dev, val=True,
+                             augment=False, cache="device")
+        ds = Repeated(base, -(-a.images // len(base)))
+        vals = {}
+        for mode in ("host", "device"):
+            losses = [V.YOLOLossV3(io["anchors"][i], io["num_cls"], io["input_shape"], dev) for i in range(2)]
+            vals[mode] = V.Validation(params, log, ds, dev, losses, match=mode)
+        series = {"host": [], "device": []}
+        result = {}
+        for rnd in range(a.rounds + 1):                       # round 0 fills the cache and the allocator: not timed
+            for mode in ("host", "device"):
+                torch.manual_seed(rnd)
+                torch.cuda.synchronize(dev)
+                t0 = time.perf_counter()
+                out = vals[mode].get_metrics(model, rnd)
+                torch.cuda.synchronize(dev)
+                if rnd:
+                    series[mode].append(time.perf_counter() - t0)
+                result[mode] = ({k: (v.tolist() if hasattr(v, "tolist") else v) for k, v in out.items()}, vals[mode].metrics_detections)
+            if result["host"] != result["device"]:
+                raise SystemExit("the two modes disagree in round %d: %r / %r" % (rnd, result["host"], result["device"]))
+    images = len(ds) // a.batch * a.batch
+    for mode in ("host", "device"):
+        print("%-6s  %s   s per get_metrics (%d images, batch %d)" % (mode, "  ".join("%.4f" % t for t in series[mode]), images, a.batch))
+    ratio = statistics.median(series["host"]) / statistics.median(series["device"])
+    scores, detections = result["host"]
+    print("median host / median device = %.2f; slowest device round %.4f s, fastest host round %.4f s; %d detections, mAP@.5 %.4f, "
+          "mAP@.5:.95 %.4f" % (ratio, max(series["device"]), min(series["host"]), detections, scores["mAP50"], scores["mAP50_95"]))
+    print(json.dumps({"images": images, "batch": a.batch, "detections": detections, "host_s": series["host"],
+                      "device_s": series["device"], "ratio_of_medians": ratio, "mAP50": scores["mAP50"], "mAP50_95": scores["mAP50_95"]}))
+
+
+if __name__ == "__main__":
+    main()

@@ -11,6 +11,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -1302,6 +1303,30 @@ int yf_val_match(int device, const float* d_det, const int32_t* d_counts, int N,
     if (d_base == d_next) return fail(YF_E_INVALID, "yf_val_match: d_next must not be d_base (every image's wave reads the base)");
     HIP_OK(hipSetDevice(device));
     yf::launch_val_match(d_det, d_counts, N, K_max, d_targets, T, (float)iou_thres, d_base, d_next, d_records, cap, (hipStream_t)stream);
+    HIP_OK(hipGetLastError());
+    return YF_OK;
+}
+
+// yolov5's process_batch at several IoU thresholds on the same inputs, one launch per batch (include/yolo_fastest_hip.h states the rule).
+int yf_val_match_iouv(int device, const float* d_det, const int32_t* d_counts, int N, int K_max, const float* d_targets, int T,
+                      const double* iou_thresholds, int num_thresholds, const int64_t* d_base, int64_t* d_next, int32_t* d_records, int64_t cap,
+                      void* stream)
+{
+    if (!d_det || !d_counts || !d_targets || !iou_thresholds || !d_base || !d_next || !d_records)
+        return fail(YF_E_INVALID, "yf_val_match_iouv: null pointer");
+    if (N < 1 || K_max < 1 || T < 0 || cap < 0) return fail(YF_E_INVALID, "yf_val_match_iouv: N >= 1, K_max >= 1, T >= 0, cap >= 0");
+    if (T > yf::VAL_IOUV_MAX_T) return fail(YF_E_INVALID, "yf_val_match_iouv: at most %d targets per image", (int)yf::VAL_IOUV_MAX_T);
+    if (num_thresholds < 1 || num_thresholds > yf::VAL_IOUV_MAX_THRESHOLDS)
+        return fail(YF_E_INVALID, "yf_val_match_iouv: 1 .. %d thresholds", (int)yf::VAL_IOUV_MAX_THRESHOLDS);
+    float thr[yf::VAL_IOUV_MAX_THRESHOLDS];
+    for (int j = 0; j < num_thresholds; ++j) {
+        thr[j] = (float)iou_thresholds[j];
+        if (!std::isfinite(iou_thresholds[j]) || !std::isfinite(thr[j]))
+            return fail(YF_E_INVALID, "yf_val_match_iouv: threshold %d is not finite (as a float)", j);
+    }
+    if (d_base == d_next) return fail(YF_E_INVALID, "yf_val_match_iouv: d_next must not be d_base (every image's workgroup reads the base)");
+    HIP_OK(hipSetDevice(device));
+    yf::launch_val_match_iouv(d_det, d_counts, N, K_max, d_targets, T, thr, num_thresholds, d_base, d_next, d_records, cap, (hipStream_t)stream);
     HIP_OK(hipGetLastError());
     return YF_OK;
 }

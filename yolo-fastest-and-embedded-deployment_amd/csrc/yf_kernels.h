@@ -336,6 +336,13 @@ int launch_val_nms(const float* pred, int N, int M, int nc, float conf_thres, fl
 enum { VAL_MATCH_MAX_T = 65536 };
 void launch_val_match(const float* det, const int32_t* counts, int N, int kmax, const float* targets, int T, float thres, const int64_t* base,
                       int64_t* next, int32_t* records, int64_t cap, hipStream_t s);
+// the same inputs scored as yolov5 does, at nthr IoU thresholds (thr: HOST floats): records int32 [cap,4] = (obj_conf bits, class_conf bits,
+// class, hit mask: bit j = true positive at thr[j]).  One workgroup of VAL_IOUV_THREADS per image; T <= VAL_IOUV_MAX_T (the winner table
+// int32 [nthr][T] of one image sits in LDS, sized per launch: 32 KB at the two caps)
+enum { VAL_IOUV_THREADS = 256, VAL_IOUV_MAX_T = 512, VAL_IOUV_MAX_THRESHOLDS = 16 };
+struct IouvThresholds { float v[VAL_IOUV_MAX_THRESHOLDS]; };
+void launch_val_match_iouv(const float* det, const int32_t* counts, int N, int kmax, const float* targets, int T, const float* thr, int nthr,
+                           const int64_t* base, int64_t* next, int32_t* records, int64_t cap, hipStream_t s);
 // training-time loss of one head and its gradient with respect to the head tensor (yf_loss_kernels.hip)
 size_t train_loss_workspace_bytes(int N, int fh, int fw, int na = 3, int nc = 3);
 void launch_train_loss(const float* head, int N, int fh, int fw, const float* anc, int na, int nc, const float* targets, int T, float ignore_thres,

@@ -738,6 +738,76 @@ void launch_val_match(const float* det, const int32_t* counts, int N, int kmax, 
                        reinterpret_cast<long long*>(next), records, (long long)cap);
 }
 
+// yolov5's process_batch (v6.1 on: no second re-sort by IoU) for a whole batch at up to 16 IoU thresholds, stated directly
+// (include/yolo_fastest_hip.h): every detection has ONE best target, the same-class target of largest non-NaN IoU (box_iou: no +1, + 1e-7f,
+// fp32), ties to the lowest index; at threshold j it is a candidate if that IoU >= thr[j]; among the candidates of one target the lowest slot
+// wins.  One workgroup per image, lanes over detections, VAL_IOUV_THREADS slots a round.  The targets are read at wave-uniform addresses.
+// s_winner[j][t] (threshold-major: at one j the lanes' targets t are consecutive dwords, one bank each; [t][16] would put every lane of a
+// ds_min on two banks) takes an LDS min of the slot -- the order the waves arrive in cannot show.  A round's detections read their entries
+// back after ONE barrier: a later round only offers larger slots, and a detection reads only entries it offered its own slot to, so
+// what it reads is final.  Every loop bound is a clamped argument, as in val_match_kernel.
+__global__ void __launch_bounds__(VAL_IOUV_THREADS) val_match_iouv_kernel(const float* __restrict__ det, const int32_t* __restrict__ counts, int N,
+                                                                          int kmax, const float* __restrict__ targets, int T, IouvThresholds thr,
+                                                                          int nthr, const long long* __restrict__ base, long long* __restrict__ next,
+                                                                          int32_t* __restrict__ rec, long long cap)
+{
+    extern __shared__ int s_winner[];                              // [nthr][T]
+    const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    long long before = 0;                                          // records of the images in front of this one (every wave sums them itself)
+    for (int j = lane; j < img; j += 64) before += min(max(counts[j], 0), kmax);
+    for (int d = 32; d > 0; d >>= 1) before += __shfl_xor(before, d);
+    const int n = min(max(counts[img], 0), kmax);
+    const long long at = base[0] + before;
+    if (img == N - 1 && tid == 0) next[0] = at + n;
+    for (int i = tid; i < nthr * T; i += VAL_IOUV_THREADS) s_winner[i] = 0x7fffffff;
+    __syncthreads();
+    const float* tg = targets + (long)img * T * 6;
+    for (int k0 = 0; k0 < n; k0 += VAL_IOUV_THREADS) {             // (n is the workgroup's: every wave meets every barrier)
+        const int k = k0 + tid;
+        int bt = -1;
+        float best = 0.f, conf = 0.f, ccls = 0.f, cls = 0.f;
+        unsigned pass = 0;
+        if (k < n) {
+            const float* q = det + ((long)img * kmax + k) * 7;
+            const float b0 = q[0], b1 = q[1], b2 = q[2], b3 = q[3];
+            conf = q[4]; ccls = q[5]; cls = q[6];
+            const float ad = (b2 - b0) * (b3 - b1);
+            for (int t = 0; t < T; ++t) {
+                const float* p = tg + (long)t * 6;
+                if (!(p[5] > 1.f)) continue;                       // marker > 1: the same for the whole workgroup
+                const float t0 = p[0], t1 = p[1], t2 = p[2], t3 = p[3];
+                const float iw = torch_clamp0(torch_min(b2, t2) - torch_max(b0, t0));
+                const float ih = torch_clamp0(torch_min(b3, t3) - torch_max(b1, t1));
+                const float inter = iw * ih;
+                const float a_t = (t2 - t0) * (t3 - t1);
+                const float iou = inter / ((a_t + ad) - inter + 1e-7f);
+                if (p[4] == cls && iou == iou && (bt < 0 || iou > best)) { bt = t; best = iou; }
+            }
+            if (bt >= 0)
+                for (int j = 0; j < nthr; ++j)
+                    if (best >= thr.v[j]) { pass |= 1u << j; atomicMin(&s_winner[j * T + bt], k); }
+        }
+        __syncthreads();
+        if (k < n && at + k >= 0 && at + k < cap) {                // (a negative cursor is garbage: count on, write nothing)
+            unsigned hit = 0;
+            for (int j = 0; j < nthr; ++j)
+                if (((pass >> j) & 1u) && s_winner[j * T + bt] == k) hit |= 1u << j;
+            int32_t* o = rec + (at + k) * 4;
+            o[0] = (int32_t)__float_as_uint(conf); o[1] = (int32_t)__float_as_uint(ccls); o[2] = (int32_t)cls; o[3] = (int32_t)hit;
+        }
+    }
+}
+
+void launch_val_match_iouv(const float* det, const int32_t* counts, int N, int kmax, const float* targets, int T, const float* thr, int nthr,
+                           const int64_t* base, int64_t* next, int32_t* records, int64_t cap, hipStream_t s)
+{
+    IouvThresholds th = {};
+    for (int j = 0; j < nthr && j < VAL_IOUV_MAX_THRESHOLDS; ++j) th.v[j] = thr[j];
+    const size_t lds = (size_t)nthr * T * sizeof(int);             // T <= VAL_IOUV_MAX_T, nthr <= 16: at most 32 KB
+    hipLaunchKernelGGL(val_match_iouv_kernel, dim3(N), dim3(VAL_IOUV_THREADS), lds, s, det, counts, N, kmax, targets, T, th, nthr,
+                       reinterpret_cast<const long long*>(base), reinterpret_cast<long long*>(next), records, (long long)cap);
+}
+
 static int pow2_at_least(int n)
 {
     int p = 64;

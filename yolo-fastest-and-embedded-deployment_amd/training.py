@@ -892,7 +892,7 @@ def cosine_factor(epoch, total_epochs):
 
 
 def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, logger=None, val_match="host", optimizer=None,
-          branch_weight=False, ema=False, box_loss=None, lambda_box=5.0):
+          branch_weight=False, ema=False, box_loss=None, lambda_box=5.0, val_metrics=False):
     """The reference's `train(params, device, tbwriter)` (train.py:44-160) with the iteration on the GPU kernels of this package.
     Same control flow and arithmetic: one YOLOLossV3 per stride (:50-53), the model from `pretrained_pth` or initialize_weights()
     (:58-65), DataLoader(batch_size, drop_last, shuffle) (:71-73), Adam(lr0, betas (0.9, 0.999), eps 1e-8) (:84), the cosine
@@ -921,6 +921,10 @@ def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, l
     lambda_box = 5.0 is the sum of the reference's weights on x, y and on w, h; nobody has trained with it.  tbwriter then gets the
     scalar `box` in place of `x`, and no `y`, `w`, `h`.  It composes with branch_weight and ema (train_step is unchanged).  The decode
     stays the reference's, so the checkpoints load into detect.py as before.
+    `val_metrics=True`, opt-in like these: on the epochs where get_mAP runs, Validation.get_metrics (yolov5's P, R, mAP@.5, mAP@.5:.95 at
+    conf_thres 0.001) runs right behind it on the same model (`ema.ema` with ema=True) and logs its table; tbwriter gets
+    `metrics/precision`, `metrics/recall`, `metrics/mAP_0.5` and `metrics/mAP_0.5:0.95` per epoch, and rank 0 writes the validated model's
+    state-dict to `YOLO-Fastest_best.pth` whenever the fitness (0.1 mAP@.5 + 0.9 mAP@.5:.95) strictly improves.  With False none of it runs.
     Returns the trained model."""
     import logging
     import os
@@ -981,6 +985,7 @@ def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, l
         return cosine_factor(epoch, total_epochs)
     scheduler = lr_scheduler.LambdaLR(optimizer, lr_lambda=lf)
     start_epoch = 0
+    best_fitness = float("-inf")                              # (val_metrics) the first validated epoch always improves on it
     scheduler.last_epoch = start_epoch - 1
     total_steps = (total_epochs - start_epoch) * batch_per_epoch
     step_count = 0
@@ -1031,7 +1036,16 @@ def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, l
                 sync_buffers(model_ema.ema)
                 model_ema.ema._weights_dirty = True
         if epoch > 4 and val is not None:
-            val.get_mAP(epoch=epoch, model=model if model_ema is None else model_ema.ema)
+            validated = model if model_ema is None else model_ema.ema
+            val.get_mAP(epoch=epoch, model=validated)
+            if val_metrics:
+                scores = val.get_metrics(model=validated, epoch=epoch)
+                if tbwriter is not None:
+                    for name, key in (("precision", "precision"), ("recall", "recall"), ("mAP_0.5", "mAP50"), ("mAP_0.5:0.95", "mAP50_95")):
+                        tbwriter.add_scalar("metrics/" + name, scores[key], epoch)
+                if rank == 0 and scores["fitness"] > best_fitness:
+                    best_fitness = scores["fitness"]
+                    torch.save(validated.state_dict(), os.path.join(save_path, "YOLO-Fastest_best.pth"))
         if rank == 0:
             torch.save(model.state_dict(), os.path.join(save_path, "YOLO-Fastest_epoch_{}.pth".format(str(epoch))))
             if model_ema is not None:

@@ -197,6 +197,36 @@ def _conf_keys(conf):
     return keys
 
 
+def match_iouv_image(det, targets, thr):
+    """yf_val_match_iouv's rule (include/yolo_fastest_hip.h) for one image on the host, numpy float32 in the kernel's operation order:
+    det [n, 7] as yf_val_nms_ex leaves it, targets [T, 6] recovered corners, thr float32 [nthr] -> hit masks int32 [n]."""
+    import numpy as np
+    det, targets = np.asarray(det, np.float32).reshape(-1, 7), np.asarray(targets, np.float32).reshape(-1, 6)
+    n, T = len(det), len(targets)
+    hit = np.zeros(n, np.int32)
+    if not n or not T:
+        return hit
+    d, t = det[:, None, :], targets[None, :, :]
+    with np.errstate(all="ignore"):
+        iw = np.minimum(d[..., 2], t[..., 2]) - np.maximum(d[..., 0], t[..., 0])          # np.minimum / np.maximum hand NaN on, as torch
+        ih = np.minimum(d[..., 3], t[..., 3]) - np.maximum(d[..., 1], t[..., 1])
+        inter = np.where(iw < 0, np.float32(0), iw) * np.where(ih < 0, np.float32(0), ih)
+        a_t = (t[..., 2] - t[..., 0]) * (t[..., 3] - t[..., 1])
+        a_d = (d[..., 2] - d[..., 0]) * (d[..., 3] - d[..., 1])
+        iou = inter / ((a_t + a_d) - inter + np.float32(1e-7))
+        ok = (t[..., 5] > 1) & (t[..., 4] == d[..., 6]) & ~np.isnan(iou)
+        has = ok.any(1)
+        best = np.where(ok, iou, -np.inf).max(1)
+        bt = (ok & (iou == best[:, None])).argmax(1)                                       # the lowest index among equals
+        slots = np.arange(n)
+        for j, th in enumerate(np.asarray(thr, np.float32)):
+            cand = has & (best >= th)
+            winner = np.full(T, n)
+            np.minimum.at(winner, bt[cand], slots[cand])
+            hit |= (cand & (winner[bt] == slots)).astype(np.int32) << j
+    return hit
+
+
 def collate_fn(batch):
     """What the reference's DetectDataset.collate_fn does (dataloader/detect_dataset.py:106-117): stack (h,w,c) images and
     (64,6) boxes, NHWC -> NCHW, divide the images by 255.  A batch that dataset.DetectDataset.__getitems__ built already (device
@@ -225,7 +255,8 @@ class Validation:
     `collate_fn` above (images / 255) -- dataset.DetectDataset(..., val=True, augment=False) itself, batch by batch on the GPU.
     `match="device"` (not in the reference; default "host"): the matching runs on the GPU too (yf_val_match behind the NMS, one launch per
     batch, no read-back per batch); the (confidence, class, hit) records read back after the last batch rebuild the same `match_list`,
-    sort keys included (`_conf_keys`), and the same `target_num`, so everything from the sort on is the code below either way."""
+    sort keys included (`_conf_keys`), and the same `target_num`, so everything from the sort on is the code below either way.
+    `get_metrics` (not in the reference either) scores the same pass as yolov5 does; it reads and changes none of `get_mAP`'s state."""
 
     def __init__(self, params, logger, dataset, device, model_loss, match="host"):
         from torch.utils.data import DataLoader
@@ -303,33 +334,35 @@ class Validation:
             for v in cls:
                 self.target_num[int(v)] += 1
 
-    def _match_device(self, model):
-        """The batches of `get_mAP` with the matching on the device.  Records (conf bits, class, hit) go to one int32 [cap, 3] buffer; the
-        write cursor is two int64 device slots used in turn (yf_val_match reads one and writes the other).  The host only keeps an upper
-        bound of the cursor (+ bs * K_max per batch) and reads the true value -- the one synchronisation before the end -- when a batch
-        could pass the capacity; the buffer is then reallocated if the batch really might not fit.  After the last batch two reads come
-        back: (cursor, overflow flag) as one pair, then the filled part of the buffer."""
+    def _device_records(self, model, width, conf_thres, nms_thres, on_targets, launch):
+        """The batches of a validation pass with the matching on the device -> the records, int32 [total, width] on the host (None if the
+        loader gave no batch).  `launch(lib, index, det, cnt, bs, kmax, t_dev, T, base, next, rec, cap, stream)` is the matching entry
+        (yf_val_match, yf_val_match_iouv) on one batch; `on_targets` sees every batch's recovered host targets.  Records go to one int32
+        [cap, width] buffer; the write cursor is two int64 device slots used in turn (the entry reads one and writes the other).  The
+        host only keeps an upper bound of the cursor (+ bs * K_max per batch) and reads the true value -- the one synchronisation before
+        the end -- when a batch could pass the capacity; the buffer is then reallocated if the batch really might not fit.  After the
+        last batch two reads come back: (cursor, overflow flag) as one pair, then the filled part of the buffer."""
         lib = _lib.lib()
         dev = torch.device(self.device)
         index = dev.index if dev.index is not None else torch.cuda.current_device()
         cap = max(int(self._record_capacity), 1)
-        rec = torch.empty((cap, 3), dtype=torch.int32, device=dev)
+        rec = torch.empty((cap, width), dtype=torch.int32, device=dev)
         cursor = torch.zeros(2, dtype=torch.int64, device=dev)
         over = torch.zeros((), dtype=torch.int64, device=dev)    # images with more than their batch's kmax detections, summed on the stream
         bound, turn, batches = 0, 0, 0
         for imgs, targets in self.dataloader:
             targets = self._recover_targets(targets.float())                      # host, float32, as in host mode
-            self._count_targets(targets)
+            on_targets(targets)
             imgs = imgs.to(self.device).float()
             pred = model(imgs)
             output = torch.cat([self.model_loss[i](p) for i, p in enumerate(pred)], 1)
-            det, cnt, kmax = _nms_device(output, self.num_cls, self.conf_thres, self.nms_thres, None, model)
+            det, cnt, kmax = _nms_device(output, self.num_cls, conf_thres, nms_thres, None, model)
             bs, T = targets.shape[0], targets.shape[1]
             if bound + bs * kmax > cap:
                 bound = int(cursor[turn])                                         # the true number of records so far
                 if bound + bs * kmax > cap:
                     cap = max(2 * cap, bound + bs * kmax)
-                    grown = torch.empty((cap, 3), dtype=torch.int32, device=dev)
+                    grown = torch.empty((cap, width), dtype=torch.int32, device=dev)
                     grown[:bound] = rec[:bound]
                     rec = grown
             # a pinned staging block per batch, from torch's caching host allocator (it hands a block out again only after the copy that
@@ -337,18 +370,28 @@ class Validation:
             # here waits for the stream
             t_dev = targets.contiguous().pin_memory().to(dev, non_blocking=True) if T else det   # (T = 0: never read)
             stream = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(lib.yf_val_match(index, det.data_ptr(), cnt.data_ptr(), bs, kmax, t_dev.data_ptr(), T, float(self.IOU_threshold),
-                                        cursor[turn:].data_ptr(), cursor[1 - turn:].data_ptr(), rec.data_ptr(), cap, ctypes.c_void_p(stream)))
+            _lib.check(launch(lib, index, det.data_ptr(), cnt.data_ptr(), bs, kmax, t_dev.data_ptr(), T, cursor[turn:].data_ptr(),
+                              cursor[1 - turn:].data_ptr(), rec.data_ptr(), cap, ctypes.c_void_p(stream)))
             turn = 1 - turn
             bound += bs * kmax
             over += (cnt > kmax).sum()            # against THIS batch's kmax
             batches += 1
         if not batches:
-            return
+            return None
         total, overflow = torch.stack((cursor[turn], over)).tolist()
         if overflow:
             raise OverflowError("more than kmax detections in an image")
-        rec = rec[:total].cpu()
+        return rec[:total].cpu()
+
+    def _match_device(self, model):
+        """The batches of `get_mAP` with the matching on the device (`_device_records` with yf_val_match): records (conf bits, class, hit)."""
+        thres = float(self.IOU_threshold)
+
+        def launch(lib, index, det, cnt, bs, kmax, t_dev, T, base, nxt, rec, cap, stream):
+            return lib.yf_val_match(index, det, cnt, bs, kmax, t_dev, T, thres, base, nxt, rec, cap, stream)
+        rec = self._device_records(model, 3, self.conf_thres, self.nms_thres, self._count_targets, launch)
+        if rec is None:
+            return
         keys = _conf_keys(rec[:, 0].contiguous().view(torch.float32))
         for key, c, hit in zip(keys, rec[:, 1].tolist(), rec[:, 2].tolist()):
             self.match_list[c].append((key, bool(hit)))
@@ -383,6 +426,79 @@ class Validation:
             self.logger.info("mean AP: %.3f" % (mAP))
             self.logger.info("——————————————————————————")
         return mAP
+
+    def get_metrics(self, model, epoch, conf_thres=0.001, nms_thres=0.6, iouv=None):
+        """Not in the reference (opt-in; `get_mAP` is untouched): the pass scored as yolov5's val.py scores one -- P, R, mAP@.5 and
+        mAP@.5:.95 from detections down to `conf_thres`, each matched to the targets at every IoU threshold of `iouv` (default
+        torch.linspace(0.5, 0.95, 10); 1..16 finite values; "mAP@.5" is the column of iouv[0]) by process_batch's rule, ranked by
+        obj_conf * class_conf (a float32 product), then metrics.ap_per_class.  Forward, decode and yf_val_nms_ex are `get_mAP`'s with
+        these two thresholds, so the detections are the REFERENCE's NMS (ranked by obj_conf, +1 IoU, per class): only the scoring is
+        yolov5's, and yolov5's max_det is not applied.  Matching follows `self.match`: "device" = yf_val_match_iouv behind the NMS, one
+        launch per batch, records read back at the end; "host" = `match_iouv_image` per image on the NMS output.  Same records, hence
+        the same numbers, either way.  Label counts come from the host targets.  Logs yolov5's table (header, an `all` row, a row per
+        class; the means run over the classes that have labels, as yolov5's do) and returns {"precision", "recall", "mAP50", "mAP50_95",
+        "fitness"} (floats), "ap" (float64 [num_cls, len(iouv)]) and "labels" (int64 [num_cls]).  `epoch` is there for get_mAP's
+        signature; yolov5's table does not print it."""
+        import numpy as np
+        from . import metrics
+        if iouv is None:
+            iouv = torch.linspace(0.5, 0.95, 10)
+        thr = [float(v) for v in iouv]
+        if not 1 <= len(thr) <= 16 or not all(math.isfinite(v) for v in thr):
+            raise ValueError("iouv must hold 1 to 16 finite IoU thresholds, got %r" % (thr,))
+        labels = np.zeros(self.num_cls, np.int64)
+        seen = [0]
+
+        def count(targets):                       # targets [bs, T, 6] recovered, host
+            cls = targets[..., 4][targets[..., 5] > 1]
+            if not bool(((cls == cls.trunc()) & (cls >= 0) & (cls < self.num_cls)).all()):
+                raise ValueError("a target's class is not one of 0 .. %d" % (self.num_cls - 1))
+            labels[:] += np.bincount(cls.long().numpy(), minlength=self.num_cls)
+            seen[0] += targets.shape[0]
+        model.eval()
+        for loss in self.model_loss:
+            object.__setattr__(loss, "model", model)      # (not a registered submodule, see YOLOLossV3.__init__)
+        with torch.no_grad():
+            if self.match == "device":
+                c_thr = (ctypes.c_double * len(thr))(*thr)
+
+                def launch(lib, index, det, cnt, bs, kmax, t_dev, T, base, nxt, rec, cap, stream):
+                    return lib.yf_val_match_iouv(index, det, cnt, bs, kmax, t_dev, T, c_thr, len(thr), base, nxt, rec, cap, stream)
+                rec = self._device_records(model, 4, conf_thres, nms_thres, count, launch)
+                rec = np.zeros((0, 4), np.int32) if rec is None else rec.numpy()
+            else:
+                thr32 = np.asarray(thr, np.float64).astype(np.float32)
+                rows = [np.zeros((0, 4), np.int32)]
+                for imgs, targets in self.dataloader:
+                    targets = self._recover_targets(targets.float())
+                    count(targets)
+                    imgs = imgs.to(self.device).float()
+                    pred = model(imgs)
+                    output = torch.cat([self.model_loss[i](p) for i, p in enumerate(pred)], 1)
+                    output = non_max_suppression(output, self.num_cls, conf_thres=conf_thres, nms_thres=nms_thres, model=model)
+                    for img_pred, img_target in zip(output, targets.numpy()):
+                        if img_pred is None:
+                            continue
+                        d = img_pred.cpu().numpy()
+                        rows.append(np.stack((d[:, 4].view(np.int32), d[:, 5].view(np.int32), d[:, 6].astype(np.int32),
+                                              match_iouv_image(d, img_target, thr32)), 1))
+                rec = np.concatenate(rows)
+        self.metrics_detections = len(rec)                                                   # of this pass (tools/val_metrics_bench.py prints it)
+        conf = rec[:, 0].copy().view(np.float32) * rec[:, 1].copy().view(np.float32)          # float32 product, formed here in both modes
+        tp = ((rec[:, 3:4] >> np.arange(len(thr))) & 1).astype(bool)
+        p, r, _, ap = metrics.ap_per_class(tp, conf, rec[:, 2], labels)
+        have = labels > 0
+
+        def mean(v):
+            return float(v[have].mean()) if have.any() else 0.0
+        out = {"precision": mean(p), "recall": mean(r), "mAP50": mean(ap[:, 0]), "mAP50_95": mean(ap.mean(1)), "ap": ap, "labels": labels}
+        out["fitness"] = float(metrics.fitness(out["mAP50"], out["mAP50_95"]))
+        row = "%20s" + "%11i" * 2 + "%11.3g" * 4
+        self.logger.info(("%20s" + "%11s" * 6) % ("Class", "Images", "Labels", "P", "R", "mAP@.5", "mAP@.5:.95"))
+        self.logger.info(row % ("all", seen[0], labels.sum(), out["precision"], out["recall"], out["mAP50"], out["mAP50_95"]))
+        for c in range(self.num_cls):
+            self.logger.info(row % (self.cls_name[c], seen[0], labels[c], p[c], r[c], ap[c, 0], ap[c].mean()))
+        return out
 
     def _calculate_AP(self, cls):
         """validate.py:87-119 in one pass (running TP / FP counts instead of the reference's re-count per prefix)."""
