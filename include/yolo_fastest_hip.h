@@ -185,6 +185,46 @@ int yf_val_match_iouv(int device, const float *d_det, const int32_t *d_counts, i
                       const double *iou_thresholds, int num_thresholds, const int64_t *d_base, int64_t *d_next, int32_t *d_records,
                       int64_t cap, void *stream);
 
+/* yolov5's own NMS (v6.1 / v7.0 utils/general.py::non_max_suppression, with torchvision.ops.nms stated as its CPU kernel's loop) on the same
+ * decoded rows, one launch per batch.  Not in the reference; yf_val_nms / yf_val_nms_ex above are untouched.  Neither yolov5 nor
+ * torchvision was available where this was written: the rule below is the definition, and parity with a real torchvision build is
+ * unpinned (as the OpenCV restatements' parity with a real OpenCV build is).  All arithmetic is fp32.  Per image, on d_pred float32
+ * [N,M,5+C] rows (cx, cy, w, h, obj, cls_0 ..):
+ *   Candidate rows: obj > (float)conf_thres -- strict, a NaN fails.  Corners x1 = cx - w/2, y1 = cy - h/2, x2 = cx + w/2, y2 = cy + h/2.
+ *       Scores s_j = cls_j * obj (an fp32 product).  multi_label holds only if the argument is non-zero AND C > 1.
+ *   Candidates, with multi_label: every (m, j) with s_j > conf_thres, candidate index m * C + j.  Without: one per row, j = the first index
+ *       of the largest s_j, kept if s_j > conf_thres, candidate index m; a row with a NaN score is dropped (torch.max hands the NaN on).
+ *   Ranking: by s descending, equal scores by the lowest candidate index -- this library's definition: torch's argsort is unstable
+ *       there, so yolov5's own order among equal scores is whatever its sort leaves.  Only the first max_nms stay.
+ *   Suppression: c = agnostic ? 0 : (float)j * 7680.0f; the suppression sees b = (x1 + c, y1 + c, x2 + c, y2 + c), each sum rounded to
+ *       fp32 as yolov5's are, and area = (b.x2 - b.x1) * (b.y2 - b.y1).  Walk the candidates in rank order; one that is still live is
+ *       kept, and every later live q dies iff inter / (area + area_q - inter) > (float)iou_thres, where
+ *       inter = max(0, min(x2, q.x2) - max(x1, q.x1)) * max(0, min(y2, q.y2) - max(y1, q.y1)) and min(a, b) = (b < a) ? b : a,
+ *       max(a, b) = (a < b) ? b : a (std::min / std::max: a NaN second operand is dropped, a NaN first one stays).  No epsilon, no +1:
+ *       0 / 0 is NaN and suppresses nothing.  Stop after max_det keeps.
+ *   d_det float32 [N,K_max,7]: the kept candidates in rank order (confidence-descending across classes, the order process_batch assumes)
+ *       = (x1, y1, x2, y2 WITHOUT the offset, obj, cls_j as read, (float)j): yf_val_nms_ex's record layout, which yf_val_match_iouv and
+ *       the fp32 product obj * cls_j (commutative: yolov5's conf bit for bit) consume unchanged.  d_counts int32 [N] = number kept, at
+ *       most max_det.  Slots past the count, and kept candidates past K_max, are not written.  A corner that the arithmetic makes NaN
+ *       (inf - inf) is a NaN; WHICH NaN (sign, payload) is the processor's choice and unspecified.  Values copied from d_pred keep their bits.
+ *   d_work: yf_val_nms_v5_work_bytes(N, M, num_classes, multi_label) bytes of device scratch, 8-byte aligned (0 from the helper: its
+ *       arguments are refused below).  With B = M * C (multi_label) or M candidates at most, padded to a power of two P >= 64, an image's
+ *       table is P 8-byte sort keys (~score bits << 32 | candidate index: no limit on M besides M * C <= 2^31 - 1) and P liveness bytes.
+ *       It sits in LDS when 9 P + YF_VAL_NMS_V5_LDS_STATIC <= YF_VAL_NMS_V5_LDS_BUDGET (P <= 16384), and d_work is then not touched;
+ *       otherwise in the image's 9 P bytes of d_work.  The result is the same either way.
+ *   Not built: the `classes` filter, `labels` autolabelling, `merge`, the wall-clock `time_limit` break, and val.py's rescale and clip of
+ *       the boxes to the original image size.
+ *   `device` = HIP device index; stream-ordered, no allocation, no synchronisation, plain vector stores only.
+ *   YF_E_INVALID before any launch: a null pointer, N < 1, M < 1, num_classes < 1, M * num_classes > 2^31 - 1, conf_thres NaN or negative
+ *   (the sort key needs positive score bits to be monotone), iou_thres NaN, max_det < 1, max_nms < 1, K_max < 1, work_bytes below the
+ *   helper's value. */
+#define YF_VAL_NMS_V5_LDS_BUDGET 163840  /* bytes of LDS one workgroup may use: MI355X has 160 KiB per CU, all of it open to one workgroup */
+#define YF_VAL_NMS_V5_LDS_STATIC 256     /* of which reserved for the kernel's own counters */
+int yf_val_nms_v5(int device, const float *d_pred, int N, int M, int num_classes, double conf_thres, double iou_thres,
+                  int multi_label, int agnostic, int max_det, int max_nms, int K_max,
+                  void *d_work, size_t work_bytes, float *d_det, int32_t *d_counts, void *stream);
+size_t yf_val_nms_v5_work_bytes(int N, int M, int num_classes, int multi_label);
+
 /* The loss end of the reference's training step (first slice; the layers' backward is not part of it):
  *   yf_train_loss = YOLOLossV3.forward(input, targets) for ONE head   src/model_training/loss/yolo_loss.py:48-97 (+ get_target :144-196)
  *                   and, if d_grad_head is not NULL, d(total loss)/d(input): what loss.backward() (train.py:131) leaves in input.grad.

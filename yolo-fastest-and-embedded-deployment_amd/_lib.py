@@ -17,6 +17,7 @@ _c = ctypes
 
 YF_OPT_ADAM, YF_OPT_SGD, YF_OPT_MAX_GROUPS, YF_OPT_TABLE_ENTRY_BYTES = 0, 1, 8, 56     # yf_train_opt_multi_pinned
 YF_OPT_EMA_TABLE_ENTRY_BYTES, YF_EMA_TABLE_ENTRY_BYTES = 64, 32                        # yf_train_opt_ema_multi_pinned, yf_train_ema_multi_pinned
+YF_VAL_NMS_V5_LDS_BUDGET, YF_VAL_NMS_V5_LDS_STATIC = 163840, 256                       # yf_val_nms_v5: where an image's key table sits
 
 
 class OptGroup(_c.Structure):
@@ -63,6 +64,9 @@ _SIGS = {
                                 _c.c_void_p, _c.c_int64, _c.c_void_p]),
     "yf_val_match_iouv": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.POINTER(_c.c_double), _c.c_int,
                                      _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_void_p]),
+    "yf_val_nms_v5": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_double, _c.c_double, _c.c_int, _c.c_int, _c.c_int,
+                                 _c.c_int, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "yf_val_nms_v5_work_bytes": (_c.c_size_t, [_c.c_int] * 4),
     "yf_train_loss_workspace_bytes": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_size_t)]),
     "yf_train_loss": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_double), _c.c_void_p, _c.c_int,
                                  _c.c_double, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_void_p, _c.c_void_p]),

@@ -1331,6 +1331,34 @@ int yf_val_match_iouv(int device, const float* d_det, const int32_t* d_counts, i
     return YF_OK;
 }
 
+// yolov5's own NMS on the decoded rows (include/yolo_fastest_hip.h states the rule), in yf_val_nms_ex's record layout.  No engine.
+static_assert(YF_VAL_NMS_V5_LDS_BUDGET == yf::VAL_NMS_V5_LDS_BUDGET && YF_VAL_NMS_V5_LDS_STATIC == yf::VAL_NMS_V5_LDS_STATIC,
+              "the header documents the kernel's LDS budget");
+size_t yf_val_nms_v5_work_bytes(int N, int M, int num_classes, int multi_label)
+{
+    return yf::val_nms_v5_work_bytes(N, M, num_classes, multi_label);
+}
+
+int yf_val_nms_v5(int device, const float* d_pred, int N, int M, int num_classes, double conf_thres, double iou_thres, int multi_label,
+                  int agnostic, int max_det, int max_nms, int K_max, void* d_work, size_t work_bytes, float* d_det, int32_t* d_counts, void* stream)
+{
+    if (!d_pred || !d_work || !d_det || !d_counts) return fail(YF_E_INVALID, "yf_val_nms_v5: null pointer");
+    if (N < 1 || M < 1 || num_classes < 1) return fail(YF_E_INVALID, "yf_val_nms_v5: N >= 1, M >= 1, num_classes >= 1");
+    if ((long)M * num_classes > 0x7fffffffL) return fail(YF_E_INVALID, "yf_val_nms_v5: M * num_classes is at most 2^31 - 1");
+    if (!(conf_thres >= 0.0)) return fail(YF_E_INVALID, "yf_val_nms_v5: conf_thres is NaN or negative");
+    if (iou_thres != iou_thres) return fail(YF_E_INVALID, "yf_val_nms_v5: iou_thres is NaN");
+    if (max_det < 1 || max_nms < 1 || K_max < 1) return fail(YF_E_INVALID, "yf_val_nms_v5: max_det >= 1, max_nms >= 1, K_max >= 1");
+    const size_t need = yf::val_nms_v5_work_bytes(N, M, num_classes, multi_label);
+    if (work_bytes < need) return fail(YF_E_INVALID, "yf_val_nms_v5: work_bytes %zu, yf_val_nms_v5_work_bytes gives %zu", work_bytes, need);
+    HIP_OK(hipSetDevice(device));
+    const int rc = yf::launch_val_nms_v5(d_pred, N, M, num_classes, (float)conf_thres, (float)iou_thres, multi_label, agnostic, max_det, max_nms,
+                                         K_max, d_work, d_det, d_counts, (hipStream_t)stream);
+    if (rc == -1) return fail(YF_E_HIP, "yf_val_nms_v5: hipGetDevice failed or the device index is not below %d", (int)yf::YF_MAX_DEVICES);
+    if (rc) return fail(YF_E_HIP, "yf_val_nms_v5: hipFuncSetAttribute(val_nms_v5_kernel) failed");
+    HIP_OK(hipGetLastError());
+    return YF_OK;
+}
+
 // Training-time loss of ONE head (first slice).  anchors: HOST double[3][2] of this head, net-input pixels.
 int yf_train_loss_workspace_bytes(yf_handle h, int N, int fh, int fw, size_t* out)
 {

@@ -331,6 +331,13 @@ size_t post_lds_bytes(int ncell);
 void launch_val_decode(const float* in, float* out, int N, int h, int w, int M_total, int m_off, const float* anc, int na, int nc, float stride_w,
                        float stride_h, hipStream_t s);
 int launch_val_nms(const float* pred, int N, int M, int nc, float conf_thres, float nms_thres, int kmax, float* det, int32_t* counts, hipStream_t s);
+// yolov5's NMS on the same rows (include/yolo_fastest_hip.h: yf_val_nms_v5), det / counts in launch_val_nms's layout.  An image's table
+// (keys + liveness bytes, val_nms_v5_work_bytes / N) sits in LDS when it and the kernel's static LDS (reserved: VAL_NMS_V5_LDS_STATIC) fit
+// VAL_NMS_V5_LDS_BUDGET -- MI355X: 160 KiB of LDS per CU, and one workgroup may declare all of it -- else in `work`.
+enum { VAL_NMS_V5_LDS_BUDGET = 160 * 1024, VAL_NMS_V5_LDS_STATIC = 256 };
+size_t val_nms_v5_work_bytes(int N, int M, int nc, int multi_label);
+int launch_val_nms_v5(const float* pred, int N, int M, int nc, float conf_thres, float iou_thres, int multi_label, int agnostic, int max_det,
+                      int max_nms, int kmax, void* work, float* det, int32_t* counts, hipStream_t s);
 // detections of launch_val_nms against targets [N,T,6] = (x1,y1,x2,y2,cls,marker): records int32 [cap,3] = (conf bits, class, hit), appended at
 // *base; *next = *base + sum of min(counts, kmax).  T <= VAL_MATCH_MAX_T (the alive bits of one image sit in LDS: one bit per target, sized per launch)
 enum { VAL_MATCH_MAX_T = 65536 };

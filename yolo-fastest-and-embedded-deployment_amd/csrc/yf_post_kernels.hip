@@ -663,6 +663,175 @@ int launch_val_nms(const float* pred, int N, int M, int nc, float conf_thres, fl
     return 0;
 }
 
+// yolov5's non_max_suppression (v6.1 / v7.0) with torchvision.ops.nms stated as its CPU kernel's loop; include/yolo_fastest_hip.h holds
+// the rule.  One workgroup per image, as val_nms_kernel: candidates -> 64-bit keys (~score bits << 32 | candidate index), bitonic sort,
+// greedy walk over the ranks.  The key table and the liveness bytes behind it sit in LDS when the launch's candidate bound fits the
+// workgroup's LDS, else in the image's slice of `work`; everything goes through the one `keys` pointer.  Every loop bound is a clamped
+// argument; candidate indexes and ranks are unsigned (M * nc <= 2^31 - 1, the padded table at most 2^31 entries).
+__device__ __forceinline__ float std_min(float a, float b) { return (b < a) ? b : a; }
+__device__ __forceinline__ float std_max(float a, float b) { return (a < b) ? b : a; }
+
+struct V5Box { float x1, y1, x2, y2, area; };
+
+// one prediction row without multi_label: the first index of the largest obj * cls_j, -1 if a product is NaN (torch.max hands NaN on, and
+// NaN > conf_thres fails)
+__device__ __forceinline__ int v5_best_class(const float* q, int nc, float* best)
+{
+    const float obj = q[4];
+    float b = q[5] * obj;
+    int cls = 0;
+    bool nan = b != b;
+    for (int k = 1; k < nc; ++k) {
+        const float v = q[5 + k] * obj;
+        nan |= v != v;
+        if (v > b) { b = v; cls = k; }
+    }
+    *best = b;
+    return nan ? -1 : cls;
+}
+
+__global__ void __launch_bounds__(POST_THREADS) val_nms_v5_kernel(const float* __restrict__ pred, int M, int nc, unsigned bound, float conf_thres,
+                                                                  float iou_thres, int multi, int agnostic, int max_det, unsigned max_nms, int kmax,
+                                                                  unsigned char* work, unsigned long long slice, int use_lds,
+                                                                  float* __restrict__ det, int32_t* counts)
+{
+    const int attrs = 5 + nc;   // floats per prediction row
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    __shared__ unsigned s_wave_cnt[POST_THREADS / 64];
+    __shared__ unsigned s_total;
+    const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* P = pred + (long)blockIdx.x * M * attrs;
+    // the table is sized for `bound` keys padded to a power of two (pad), pad * 8 bytes of keys, then pad liveness bytes
+    unsigned char* table = use_lds ? smem : work + (unsigned long long)blockIdx.x * slice;
+    uint64_t* keys = reinterpret_cast<uint64_t*>(table);
+    unsigned char* alive = table + slice / 9 * 8;
+    if (tid == 0) s_total = 0;
+    __syncthreads();
+    for (unsigned base = 0; base < bound; base += POST_THREADS) {
+        const unsigned idx = base + tid;   // candidate index: m * nc + j with multi_label, else m
+        bool pass = false;
+        uint64_t key = 0;
+        if (idx < bound) {
+            const unsigned m = multi ? idx / (unsigned)nc : idx;
+            const float* q = P + (long)m * attrs;
+            const float obj = q[4];
+            if (obj > conf_thres) {
+                float s;
+                if (multi) s = q[5 + (idx - m * (unsigned)nc)] * obj;
+                else if (v5_best_class(q, nc, &s) < 0) s = 0.f;
+                pass = s > conf_thres;     // conf_thres >= 0: s is positive, its bits are monotone
+                key = ((uint64_t)(~__float_as_uint(s)) << 32) | (uint64_t)idx;
+            }
+        }
+        unsigned long long bm = __ballot(pass);
+        unsigned before = __popcll(bm & ((1ull << lane) - 1ull));
+        if (lane == 0) s_wave_cnt[wave] = __popcll(bm);
+        __syncthreads();
+        unsigned off = s_total;
+        for (unsigned wv = 0; wv < wave; ++wv) off += s_wave_cnt[wv];
+        if (pass) keys[off + before] = key;
+        __syncthreads();
+        if (tid == 0) { unsigned tt = s_total; for (int wv = 0; wv < POST_THREADS / 64; ++wv) tt += s_wave_cnt[wv]; s_total = tt; }
+        __syncthreads();
+    }
+    unsigned K = s_total;
+    if (K == 0) { if (tid == 0) counts[blockIdx.x] = 0; return; }
+    unsigned mpad = 64;
+    while (mpad < K) mpad <<= 1;           // <= the table's pad: K <= bound
+    for (unsigned i = K + tid; i < mpad; i += POST_THREADS) keys[i] = ~0ull;   // above every real key: no score has all bits clear
+    __syncthreads();
+    for (unsigned k = 2; k <= mpad && k; k <<= 1)
+        for (unsigned j = k >> 1; j > 0; j >>= 1) {
+            for (unsigned i = tid; i < mpad; i += POST_THREADS) {
+                unsigned l = i ^ j;
+                if (l > i) {
+                    uint64_t x = keys[i], y = keys[l];
+                    bool up = (i & k) == 0;
+                    if ((x > y) == up) { keys[i] = y; keys[l] = x; }
+                }
+            }
+            __syncthreads();
+        }
+    if (K > max_nms) K = max_nms;
+    for (unsigned i = tid; i < K; i += POST_THREADS) alive[i] = 1;
+    __syncthreads();
+    // the candidate at rank r: its row, its class, and the box the suppression sees (corners + class offset, each rounded to fp32)
+    auto box_of = [&](unsigned r, const float** row, int* cls) {
+        const unsigned idx = (unsigned)(keys[r] & 0xffffffffull);
+        const unsigned m = multi ? idx / (unsigned)nc : idx;
+        const float* q = P + (long)m * attrs;
+        float s;
+        const int j = multi ? (int)(idx - m * (unsigned)nc) : v5_best_class(q, nc, &s);
+        const float c = agnostic ? 0.f : __fmul_rn((float)j, 7680.0f);   // (_rn: the product and each sum round on their own, whatever
+        const float cx = q[0], cy = q[1], w = q[2], h = q[3];             //  the build's fp-contract setting is)
+        V5Box b;
+        b.x1 = __fadd_rn(cx - w / 2, c); b.y1 = __fadd_rn(cy - h / 2, c); b.x2 = __fadd_rn(cx + w / 2, c); b.y2 = __fadd_rn(cy + h / 2, c);
+        b.area = (b.x2 - b.x1) * (b.y2 - b.y1);
+        *row = q; *cls = j;
+        return b;
+    };
+    int nk = 0;
+    for (unsigned i = 0; i < K; ++i) {
+        if (!alive[i]) continue;           // one address for the workgroup: the branch is uniform
+        const float* q;
+        int ci;
+        const V5Box bi = box_of(i, &q, &ci);
+        if (tid == 0 && nk < kmax) {
+            const float cx = q[0], cy = q[1], w = q[2], h = q[3];
+            float* o = det + ((long)blockIdx.x * kmax + nk) * 7;
+            o[0] = cx - w / 2; o[1] = cy - h / 2; o[2] = cx + w / 2; o[3] = cy + h / 2; o[4] = q[4]; o[5] = q[5 + ci]; o[6] = (float)ci;
+        }
+        if (++nk >= max_det) break;
+        for (unsigned j = i + 1 + tid; j < K; j += POST_THREADS) {
+            if (!alive[j]) continue;
+            const float* qq;
+            int cj;
+            const V5Box bj = box_of(j, &qq, &cj);
+            const float iw = std_max(0.f, std_min(bi.x2, bj.x2) - std_max(bi.x1, bj.x1));
+            const float ih = std_max(0.f, std_min(bi.y2, bj.y2) - std_max(bi.y1, bj.y1));
+            const float inter = iw * ih;
+            if (inter / (bi.area + bj.area - inter) > iou_thres) alive[j] = 0;     // 0 / 0 is NaN: nothing dies
+        }
+        __syncthreads();
+    }
+    if (tid == 0) counts[blockIdx.x] = nk;
+}
+
+// bytes of one image's table: `bound` candidates padded to a power of two (at least 64), 8 bytes of key and one liveness byte each
+static unsigned long long val_nms_v5_slice(long bound)
+{
+    unsigned long long pad = 64;
+    while (pad < (unsigned long long)bound) pad <<= 1;
+    return pad * 9;
+}
+
+size_t val_nms_v5_work_bytes(int N, int M, int nc, int multi_label)
+{
+    if (N < 1 || M < 1 || nc < 1 || (long)M * nc > 0x7fffffffL) return 0;
+    return (size_t)N * val_nms_v5_slice(multi_label && nc > 1 ? (long)M * nc : (long)M);
+}
+
+int launch_val_nms_v5(const float* pred, int N, int M, int nc, float conf_thres, float iou_thres, int multi_label, int agnostic, int max_det,
+                      int max_nms, int kmax, void* work, float* det, int32_t* counts, hipStream_t s)
+{
+    const int multi = multi_label && nc > 1;
+    const long bound = multi ? (long)M * nc : (long)M;
+    const unsigned long long slice = val_nms_v5_slice(bound);
+    const int use_lds = slice + VAL_NMS_V5_LDS_STATIC <= VAL_NMS_V5_LDS_BUDGET;
+    const size_t lds = use_lds ? (size_t)slice : 0;
+    static size_t attr_set[YF_MAX_DEVICES] = {};
+    const int dev = current_device();
+    if (dev < 0) return -1;              // no current device, or its index is not below YF_MAX_DEVICES; -2: the attribute call failed
+    if (lds > 48 * 1024 && lds > attr_set[dev]) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(val_nms_v5_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+            return -2;
+        attr_set[dev] = lds;
+    }
+    hipLaunchKernelGGL(val_nms_v5_kernel, dim3(N), dim3(POST_THREADS), lds, s, pred, M, nc, (unsigned)bound, conf_thres, iou_thres, multi,
+                       agnostic ? 1 : 0, max_det, (unsigned)max_nms, kmax, static_cast<unsigned char*>(work), slice, use_lds, det, counts);
+    return 0;
+}
+
 // validate.py:46-74 for a whole batch: every detection of val_nms_kernel's output against the image's targets, TP / FP per detection.
 // One wave per image; lanes are targets, 64 at a time.  The detections of an image are visited in slot order (class-ascending, then
 // confidence-descending: the reference's unique() loop over its per-class loop); a detection takes the lowest-index target of its class

@@ -892,7 +892,7 @@ def cosine_factor(epoch, total_epochs):
 
 
 def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, logger=None, val_match="host", optimizer=None,
-          branch_weight=False, ema=False, box_loss=None, lambda_box=5.0, val_metrics=False):
+          branch_weight=False, ema=False, box_loss=None, lambda_box=5.0, val_metrics=False, val_nms="reference"):
     """The reference's `train(params, device, tbwriter)` (train.py:44-160) with the iteration on the GPU kernels of this package.
     Same control flow and arithmetic: one YOLOLossV3 per stride (:50-53), the model from `pretrained_pth` or initialize_weights()
     (:58-65), DataLoader(batch_size, drop_last, shuffle) (:71-73), Adam(lr0, betas (0.9, 0.999), eps 1e-8) (:84), the cosine
@@ -925,6 +925,8 @@ def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, l
     conf_thres 0.001) runs right behind it on the same model (`ema.ema` with ema=True) and logs its table; tbwriter gets
     `metrics/precision`, `metrics/recall`, `metrics/mAP_0.5` and `metrics/mAP_0.5:0.95` per epoch, and rank 0 writes the validated model's
     state-dict to `YOLO-Fastest_best.pth` whenever the fitness (0.1 mAP@.5 + 0.9 mAP@.5:.95) strictly improves.  With False none of it runs.
+    `val_nms` is get_metrics' `nms` ("reference", the default, or "yolov5": the detections get_metrics scores come from yolov5's own NMS,
+    yf_val_nms_v5); it needs val_metrics=True, anything else with it raises ValueError.  get_mAP is the reference's either way.
     Returns the trained model."""
     import logging
     import os
@@ -940,6 +942,10 @@ def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, l
     io, tp = params["io_params"], params["train_params"]
     if optimizer not in (None, "adam", "sgd"):
         raise ValueError("optimizer must be None (the reference's Adam), \"adam\" or \"sgd\", got %r" % (optimizer,))
+    if val_nms not in validation.NMS_KINDS:
+        raise ValueError("val_nms must be 'reference' or 'yolov5', not %r" % (val_nms,))
+    if val_nms != "reference" and not val_metrics:
+        raise ValueError("val_nms=%r is read by get_metrics only: pass val_metrics=True" % (val_nms,))
     head_weights = None
     if branch_weight:
         head_weights = [float(v) for v in tp["branch_weight"]]
@@ -1039,7 +1045,7 @@ def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, l
             validated = model if model_ema is None else model_ema.ema
             val.get_mAP(epoch=epoch, model=validated)
             if val_metrics:
-                scores = val.get_metrics(model=validated, epoch=epoch)
+                scores = val.get_metrics(model=validated, epoch=epoch, nms=val_nms)
                 if tbwriter is not None:
                     for name, key in (("precision", "precision"), ("recall", "recall"), ("mAP_0.5", "mAP50"), ("mAP_0.5:0.95", "mAP50_95")):
                         tbwriter.add_scalar("metrics/" + name, scores[key], epoch)

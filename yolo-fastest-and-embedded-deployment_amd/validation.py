@@ -174,6 +174,50 @@ def non_max_suppression(prediction, num_classes, conf_thres=0.5, nms_thres=0.4, 
     return [det[i, :n].clone() if n else None for i, n in enumerate(counts)]
 
 
+def _nms_v5_device(prediction, conf_thres, iou_thres, agnostic, multi_label, max_det, max_nms):
+    """yf_val_nms_v5 on the current stream -> (det float32 [bs, max_det, 7], cnt int32 [bs], kmax = max_det) in `_nms_device`'s layout, all
+    on the device, nothing read back.  cnt never exceeds kmax."""
+    if not prediction.is_cuda:
+        raise RuntimeError("validation path (HIP) has no CPU implementation: pass GPU tensors")
+    p = prediction.contiguous().float()
+    bs, M, attrs = p.shape
+    nc = attrs - 5
+    if nc < 1 or bs < 1 or M < 1:
+        raise ValueError("prediction must be [images >= 1, rows >= 1, 5 + classes] with at least one class, got %s" % (tuple(p.shape),))
+    if not 0.0 <= float(conf_thres) <= 1.0 or not 0.0 <= float(iou_thres) <= 1.0:       # yolov5's own asserts
+        raise ValueError("conf_thres and iou_thres must lie in 0 .. 1, got %r and %r" % (conf_thres, iou_thres))
+    kmax, max_nms = int(max_det), int(max_nms)
+    if kmax < 1 or max_nms < 1:
+        raise ValueError("max_det and max_nms must be at least 1, got %r and %r" % (max_det, max_nms))
+    lib = _lib.lib()
+    index = p.device.index if p.device.index is not None else torch.cuda.current_device()
+    need = lib.yf_val_nms_v5_work_bytes(bs, M, nc, int(bool(multi_label)))
+    if not need:
+        raise ValueError("%d rows x %d classes is more than 2^31 - 1 candidates" % (M, nc))
+    work = torch.empty((need + 7) // 8, dtype=torch.int64, device=p.device)                # 8-byte aligned scratch
+    det = torch.empty((bs, kmax, 7), dtype=torch.float32, device=p.device)
+    cnt = torch.empty((bs,), dtype=torch.int32, device=p.device)
+    stream = torch.cuda.current_stream(p.device).cuda_stream
+    _lib.check(lib.yf_val_nms_v5(index, p.data_ptr(), bs, M, nc, float(conf_thres), float(iou_thres), int(bool(multi_label)),
+                                 int(bool(agnostic)), kmax, max_nms, kmax, work.data_ptr(), work.numel() * 8, det.data_ptr(), cnt.data_ptr(),
+                                 ctypes.c_void_p(stream)))
+    return det, cnt, kmax
+
+
+def non_max_suppression_v5(prediction, conf_thres=0.25, iou_thres=0.45, agnostic=False, multi_label=False, max_det=300, max_nms=30000,
+                           model=None):
+    """Not in the reference: yolov5's non_max_suppression (v6.1 / v7.0; include/yolo_fastest_hip.h: yf_val_nms_v5 states the rule) on
+    decoded rows [bs, M, 5 + C] -> a list with one [n, 6] tensor (x1, y1, x2, y2, conf = obj * cls, cls) per image, confidence-descending,
+    an empty [0, 6] one where nothing is kept: yolov5's return shape.  Not built: `classes`, `labels`, `merge`, the time limit.  `model`
+    is there for `non_max_suppression`'s call shape only: the entry needs no engine, the device is the tensor's."""
+    det, cnt, _ = _nms_v5_device(prediction, conf_thres, iou_thres, agnostic, multi_label, max_det, max_nms)
+    out = torch.cat((det[..., :4], det[..., 4:5] * det[..., 5:6], det[..., 6:7]), 2)       # slots past the count hold garbage: cut below
+    return [out[i, :n].clone() for i, n in enumerate(cnt.cpu().tolist())]
+
+
+NMS_KINDS = ("reference", "yolov5")
+
+
 def _key_fallback(t):
     """the sort key of validate.py:72 for one confidence (a 0-dim tensor): its printed form"""
     return str(t)
@@ -334,9 +378,10 @@ class Validation:
             for v in cls:
                 self.target_num[int(v)] += 1
 
-    def _device_records(self, model, width, conf_thres, nms_thres, on_targets, launch):
+    def _device_records(self, model, width, nms, on_targets, launch):
         """The batches of a validation pass with the matching on the device -> the records, int32 [total, width] on the host (None if the
-        loader gave no batch).  `launch(lib, index, det, cnt, bs, kmax, t_dev, T, base, next, rec, cap, stream)` is the matching entry
+        loader gave no batch).  `nms(output)` is the NMS on one batch's decoded rows -> (det, cnt, kmax) on the device (`_nms_device`,
+        `_nms_v5_device`).  `launch(lib, index, det, cnt, bs, kmax, t_dev, T, base, next, rec, cap, stream)` is the matching entry
         (yf_val_match, yf_val_match_iouv) on one batch; `on_targets` sees every batch's recovered host targets.  Records go to one int32
         [cap, width] buffer; the write cursor is two int64 device slots used in turn (the entry reads one and writes the other).  The
         host only keeps an upper bound of the cursor (+ bs * K_max per batch) and reads the true value -- the one synchronisation before
@@ -356,7 +401,7 @@ class Validation:
             imgs = imgs.to(self.device).float()
             pred = model(imgs)
             output = torch.cat([self.model_loss[i](p) for i, p in enumerate(pred)], 1)
-            det, cnt, kmax = _nms_device(output, self.num_cls, conf_thres, nms_thres, None, model)
+            det, cnt, kmax = nms(output)
             bs, T = targets.shape[0], targets.shape[1]
             if bound + bs * kmax > cap:
                 bound = int(cursor[turn])                                         # the true number of records so far
@@ -389,7 +434,9 @@ class Validation:
 
         def launch(lib, index, det, cnt, bs, kmax, t_dev, T, base, nxt, rec, cap, stream):
             return lib.yf_val_match(index, det, cnt, bs, kmax, t_dev, T, thres, base, nxt, rec, cap, stream)
-        rec = self._device_records(model, 3, self.conf_thres, self.nms_thres, self._count_targets, launch)
+        def nms(output):
+            return _nms_device(output, self.num_cls, self.conf_thres, self.nms_thres, None, model)
+        rec = self._device_records(model, 3, nms, self._count_targets, launch)
         if rec is None:
             return
         keys = _conf_keys(rec[:, 0].contiguous().view(torch.float32))
@@ -427,13 +474,18 @@ class Validation:
             self.logger.info("——————————————————————————")
         return mAP
 
-    def get_metrics(self, model, epoch, conf_thres=0.001, nms_thres=0.6, iouv=None):
+    def get_metrics(self, model, epoch, conf_thres=0.001, nms_thres=0.6, iouv=None, nms="reference", max_det=300):
         """Not in the reference (opt-in; `get_mAP` is untouched): the pass scored as yolov5's val.py scores one -- P, R, mAP@.5 and
         mAP@.5:.95 from detections down to `conf_thres`, each matched to the targets at every IoU threshold of `iouv` (default
         torch.linspace(0.5, 0.95, 10); 1..16 finite values; "mAP@.5" is the column of iouv[0]) by process_batch's rule, ranked by
         obj_conf * class_conf (a float32 product), then metrics.ap_per_class.  Forward, decode and yf_val_nms_ex are `get_mAP`'s with
         these two thresholds, so the detections are the REFERENCE's NMS (ranked by obj_conf, +1 IoU, per class): only the scoring is
-        yolov5's, and yolov5's max_det is not applied.  Matching follows `self.match`: "device" = yf_val_match_iouv behind the NMS, one
+        yolov5's, and yolov5's max_det is not applied.  That is `nms="reference"`, the default.  `nms="yolov5"` takes the detections from
+        yolov5's own NMS instead (yf_val_nms_v5: ranked and thresholded by obj * cls, no +1, class offsets) as val.py runs it:
+        multi_label=True, agnostic only for a one-class model, max_nms=30000, `nms_thres` as its iou_thres and at most `max_det`
+        detections per image -- yolov5's protocol from the logits to the table, except that val.py's rescale and clip of the boxes to
+        the original image is not built (the targets here are in net-input pixels already).  `max_det` is not read with "reference".
+        Matching follows `self.match`: "device" = yf_val_match_iouv behind the NMS, one
         launch per batch, records read back at the end; "host" = `match_iouv_image` per image on the NMS output.  Same records, hence
         the same numbers, either way.  Label counts come from the host targets.  Logs yolov5's table (header, an `all` row, a row per
         class; the means run over the classes that have labels, as yolov5's do) and returns {"precision", "recall", "mAP50", "mAP50_95",
@@ -446,8 +498,17 @@ class Validation:
         thr = [float(v) for v in iouv]
         if not 1 <= len(thr) <= 16 or not all(math.isfinite(v) for v in thr):
             raise ValueError("iouv must hold 1 to 16 finite IoU thresholds, got %r" % (thr,))
+        if nms not in NMS_KINDS:
+            raise ValueError("nms must be 'reference' or 'yolov5', not %r" % (nms,))
+        if nms == "yolov5" and int(max_det) < 1:
+            raise ValueError("max_det must be at least 1, got %r" % (max_det,))
         labels = np.zeros(self.num_cls, np.int64)
         seen = [0]
+
+        def nms_device(output):                   # -> (det [bs, kmax, 7], cnt [bs], kmax) on the device
+            if nms == "yolov5":
+                return _nms_v5_device(output, conf_thres, nms_thres, self.num_cls == 1, True, max_det, 30000)
+            return _nms_device(output, self.num_cls, conf_thres, nms_thres, None, model)
 
         def count(targets):                       # targets [bs, T, 6] recovered, host
             cls = targets[..., 4][targets[..., 5] > 1]
@@ -464,7 +525,7 @@ class Validation:
 
                 def launch(lib, index, det, cnt, bs, kmax, t_dev, T, base, nxt, rec, cap, stream):
                     return lib.yf_val_match_iouv(index, det, cnt, bs, kmax, t_dev, T, c_thr, len(thr), base, nxt, rec, cap, stream)
-                rec = self._device_records(model, 4, conf_thres, nms_thres, count, launch)
+                rec = self._device_records(model, 4, nms_device, count, launch)
                 rec = np.zeros((0, 4), np.int32) if rec is None else rec.numpy()
             else:
                 thr32 = np.asarray(thr, np.float64).astype(np.float32)
@@ -475,7 +536,11 @@ class Validation:
                     imgs = imgs.to(self.device).float()
                     pred = model(imgs)
                     output = torch.cat([self.model_loss[i](p) for i, p in enumerate(pred)], 1)
-                    output = non_max_suppression(output, self.num_cls, conf_thres=conf_thres, nms_thres=nms_thres, model=model)
+                    if nms == "yolov5":
+                        det, cnt, _ = nms_device(output)
+                        output = [det[i, :n] if n else None for i, n in enumerate(cnt.cpu().tolist())]
+                    else:
+                        output = non_max_suppression(output, self.num_cls, conf_thres=conf_thres, nms_thres=nms_thres, model=model)
                     for img_pred, img_target in zip(output, targets.numpy()):
                         if img_pred is None:
                             continue
