@@ -296,6 +296,44 @@ int yf_train_head_loss_box(int device, int H, int W, const float *d_head, int N,
                            int num_classes, const float *d_targets, int T, double ignore_thres, void *d_work, size_t work_bytes,
                            float *d_losses, float *d_grad_head, void *stream, int box_kind, double lambda_box);
 
+/* The same loss with yolov5's objectness and class options (opt-in; the six loss keys of its hyp files and its model.gr).
+ * yf_train_head_loss_box's arguments, then eight doubles:
+ *     obj_pw, cls_pw    BCE positive weight of the objectness / the class term        neutral 1, 1
+ *     label_smoothing   eps of yolov5's smooth_BCE                                    neutral 0
+ *     fl_gamma          focal exponent gamma                                          neutral 0
+ *     fl_alpha          focal alpha (not read while gamma == 0)
+ *     obj_iou           yolov5's gr: how far the objectness target follows the IoU    neutral 0
+ *     lambda_conf, lambda_cls   the `obj` and `cls` gains (plain factors)             neutral 1, 1
+ *   get_target, the masks, the box terms and the normalisations (conf: a mean over all E cells, cls: over C * n_pos) are those of
+ *   yf_train_head_loss_box.  Only the BCE element and its targets change.  p is a float32 sigmoid times its mask, as there:
+ *     base(p,t,w) = -( w t max(log p, -100) + (1 - t) max(log(1 - p), -100) )
+ *     d base / d p = ( -w t (1 - p) + (1 - t) p ) / max((1 - p) p, 1e-12), times (1 - p) p for the logit
+ *   (at w = 1 and a 0/1 target these are torch's BCELoss element and backward, the ones yf_train_head_loss_ex uses).
+ *   Focal loss, only when gamma > 0 (yolov5's FocalLoss around BCE), on EVERY element of conf_obj, conf_noobj and cls:
+ *     p_t = t p + (1 - t)(1 - p)      af = t alpha + (1 - t)(1 - alpha)      elem = base af (1 - p_t)^gamma
+ *     the modulating factor is differentiated too: d (1 - p_t)^gamma / d p = gamma (1 - p_t)^(gamma - 1) (1 - 2 t)
+ *   0 < gamma < 1 is refused: that derivative is unbounded at p_t = 1.
+ *   Positive weights: obj_pw is the w of conf_obj (conf_noobj has target 0, where w is moot), cls_pw the w of cls.
+ *   Label smoothing: the class target is cp = float32(1 - 0.5 eps) where the class plane is 1 and cn = float32(0.5 eps) where it is 0
+ *   (cp, cn formed in double on the host).  The planes in the workspace stay get_target's 0 / 1; smoothing is applied where they are read.
+ *   IoU objectness target: at a positive cell t_obj = float32((1 - g) + g min(max(value, 0), 1)), g = obj_iou, value the cell's GIoU /
+ *   DIoU / CIoU value above; a CONSTANT in the backward (yolov5's iou.detach().clamp(0)).  g > 0 with YF_BOX_REF is refused.  A positive
+ *   cell whose noobj_mask is still 1 (its best anchor's IoU is not above the ignore threshold) keeps its conf_noobj element, as before.
+ *   total = [2.5 (x + y + w + h) or lambda_box * box] + lambda_conf * conf + lambda_cls * cls; d_losses[5] and [6] stay the UNWEIGHTED
+ *   conf and cls.  Nobody has trained with any of these options; yolov5's files use fl_gamma 0 or 1.5 and gr 1.
+ *   With the neutral values d_losses, the gradient and the whole workspace are those of yf_train_head_loss_box bit for bit, for every
+ *   box_kind (the same launches).  Otherwise a term no option touches (conf: obj_pw, gamma, obj_iou; cls: cls_pw, gamma, eps) keeps that
+ *   entry's float32 arithmetic, its gradient channels multiplied by the float32 gain; a touched term's elements and derivatives are
+ *   evaluated in double on the float32 sigmoid and rounded to float32 once, at the gradient store.  Five launches, no atomic feeds the
+ *   gradient, no host synchronisation; d_work and its size are yf_train_head_loss_box's.
+ *   YF_E_INVALID before any launch for everything yf_train_head_loss_box refuses, a non-finite option, obj_pw or cls_pw <= 0,
+ *   label_smoothing, fl_alpha or obj_iou outside [0, 1], fl_gamma < 0 or in (0, 1), obj_iou > 0 with YF_BOX_REF, a negative gain. */
+int yf_train_head_loss_hyp_workspace_bytes(int N, int fh, int fw, int num_anchors, int num_classes, size_t *out);
+int yf_train_head_loss_hyp(int device, int H, int W, const float *d_head, int N, int fh, int fw, const double *anchors, int num_anchors,
+                           int num_classes, const float *d_targets, int T, double ignore_thres, void *d_work, size_t work_bytes,
+                           float *d_losses, float *d_grad_head, void *stream, int box_kind, double lambda_box, double obj_pw, double cls_pw,
+                           double label_smoothing, double fl_gamma, double fl_alpha, double obj_iou, double lambda_conf, double lambda_cls);
+
 /* Operators of the reference's TRAINING step (second slice): every layer type of YoloFastest in train mode, forward
  * and backward, on NCHW float32 device tensors like the reference's (src/model_training/model/yolo_fastest.py:16-66, train.py:98-160).
  * Per-layer kernels (MFMA GEMMs for the pointwise / dense convs, split reductions added in a fixed order: DESIGN.md section 4) -- not the

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Training-step throughput (train.py:111-132: zero_grad, train-mode forward, two-head loss, backward, Adam) on synthetic frames.
-GPU box: python tools/train_bench.py [--batch 16] [--steps 20] [--optimizer reference|adam|sgd] [--ema off|fused|loop] [--box-loss giou|diou|ciou] [--cpu]   (--cpu also times oracle/ on the host cores: the baseline)"""
+GPU box: python tools/train_bench.py [--batch 16] [--steps 20] [--optimizer reference|adam|sgd] [--ema off|fused|loop] [--box-loss giou|diou|ciou] [--loss-hyp all] [--cpu]   (--cpu also times oracle/ on the host cores: the baseline)"""
 import argparse
 import os
 import sys
@@ -28,6 +28,9 @@ ap.add_argument("--ema", choices=["off", "fused", "loop"], default="off",
                      "loop = yolov5's own update(), a Python loop over the state dict on torch kernels")
 ap.add_argument("--box-loss", choices=["giou", "diou", "ciou"], default=None, metavar="KIND",
                 help="YOLOLossV3(box_loss=KIND): one IoU-family box term per positive cell in place of the reference's four (giou, diou, ciou)")
+ap.add_argument("--loss-hyp", choices=["all"], default=None,
+                help="all: every objectness / class option of YOLOLossV3 away from its neutral value (obj_pw 1.7, cls_pw 0.6, label_smoothing 0.1, "
+                     "fl_gamma 1.5, fl_alpha 0.3, lambda_conf 0.7, lambda_cls 1.3, and obj_iou 1 when --box-loss is given): timing values, not a recipe")
 ap.add_argument("--cpu", action="store_true")
 ap.add_argument("--json", action="store_true", help="also print one JSON line (metric, value, ms per iteration, cpu baseline)")
 a = ap.parse_args()
@@ -47,7 +50,11 @@ for b in range(a.batch):
     t[b, :k, 0:2] = rng.uniform(0.05, 0.95, (k, 2)); t[b, :k, 2:4] = rng.uniform(0.03, 0.4, (k, 2))
     t[b, :k, 4] = rng.integers(0, 3, k); t[b, :k, 5] = 255.0
 tt = torch.from_numpy(t)
-crit = [val.YOLOLossV3(io["anchors"][i], 3, io["input_shape"], dev, model=m, box_loss=a.box_loss) for i in range(2)]
+hyp = {}
+if a.loss_hyp == "all":
+    hyp = dict(obj_pw=1.7, cls_pw=0.6, label_smoothing=0.1, fl_gamma=1.5, fl_alpha=0.3, obj_iou=1.0 if a.box_loss else 0.0, lambda_conf=0.7,
+               lambda_cls=1.3)
+crit = [val.YOLOLossV3(io["anchors"][i], 3, io["input_shape"], dev, model=m, box_loss=a.box_loss, **hyp) for i in range(2)]
 tp = yf.config_params["train_params"]
 if a.optimizer == "reference":               # train.py:84: one group
     opt = training.Adam(m.parameters(), lr=0.001)
@@ -91,7 +98,7 @@ print("GPU  batch %d %dx%d: %.2f ms / iteration, %.0f examples/s, loss %.4f" % (
 line = {"metric": "training_examples_per_second", "value": round(a.batch / dt, 1), "unit": "examples/s", "ms_per_iteration": round(dt * 1e3, 3),
         "steps": a.steps, "warmup": a.warmup, "dtype": "f32", "data": "synthetic",
         "config": {"workload": "train.py:111-132 iteration (zero_grad, train-mode forward, two-head loss, backward, Adam)", "batch": a.batch,
-                   "input": [H, W], "optimizer": a.optimizer, "ema": a.ema, "box_loss": a.box_loss}, "cpu_baseline": None}
+                   "input": [H, W], "optimizer": a.optimizer, "ema": a.ema, "box_loss": a.box_loss, "loss_hyp": a.loss_hyp}, "cpu_baseline": None}
 if a.cpu:
     from oracle import backbone_oracle as bo, loss_oracle as lo
     sd = bo.training_state(sd0)

@@ -81,6 +81,10 @@ _SIGS = {
     "yf_train_head_loss_box": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_double),
                                           _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_double, _c.c_void_p, _c.c_size_t, _c.c_void_p,
                                           _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double]),
+    "yf_train_head_loss_hyp_workspace_bytes": (_c.c_int, [_c.c_int] * 5 + [_c.POINTER(_c.c_size_t)]),
+    "yf_train_head_loss_hyp": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_double),
+                                          _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_double, _c.c_void_p, _c.c_size_t, _c.c_void_p,
+                                          _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double] + [_c.c_double] * 8),   # ... box_kind, lambda_box, the options
     "yf_train_conv_forward": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p] + [_c.c_int] * 8 + [_c.c_void_p]),
     "yf_train_conv_backward_data": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p] + [_c.c_int] * 8 + [_c.c_void_p]),
     "yf_train_conv_backward_weight": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p] + [_c.c_int] * 8 +

@@ -1445,6 +1445,50 @@ int yf_train_head_loss_box(int device, int H, int W, const float* d_head, int N,
     return YF_OK;
 }
 
+// The same with yolov5's objectness / class options (yolo_fastest_hip.h); the neutral values run yf_train_head_loss_box's launches.
+int yf_train_head_loss_hyp_workspace_bytes(int N, int fh, int fw, int num_anchors, int num_classes, size_t* out)
+{
+    if (!out || N <= 0 || fh <= 0 || fw <= 0 || num_anchors < 1 || num_anchors > yf::POST_MAX_ANCHORS || num_classes < 1)
+        return fail(YF_E_INVALID, "yf_train_head_loss_hyp_workspace_bytes: bad argument");
+    *out = yf::train_loss_box_workspace_bytes(N, fh, fw, num_anchors, num_classes);
+    return YF_OK;
+}
+
+int yf_train_head_loss_hyp(int device, int H, int W, const float* d_head, int N, int fh, int fw, const double* anchors, int num_anchors,
+                           int num_classes, const float* d_targets, int T, double ignore_thres, void* d_work, size_t work_bytes, float* d_losses,
+                           float* d_grad_head, void* stream, int box_kind, double lambda_box, double obj_pw, double cls_pw, double label_smoothing,
+                           double fl_gamma, double fl_alpha, double obj_iou, double lambda_conf, double lambda_cls)
+{
+    if (!d_head || !anchors || !d_targets || !d_work || !d_losses || N <= 0 || fh <= 0 || fw <= 0 || T <= 0 || H <= 0 || W <= 0 ||
+        num_anchors < 1 || num_anchors > yf::POST_MAX_ANCHORS || num_classes < 1)
+        return fail(YF_E_INVALID, "yf_train_head_loss_hyp: bad argument");
+    if (box_kind < YF_BOX_REF || box_kind > YF_BOX_CIOU) return fail(YF_E_INVALID, "yf_train_head_loss_hyp: box_kind must be 0 .. 3");
+    if (!(lambda_box >= 0.0 && lambda_box < HUGE_VAL)) return fail(YF_E_INVALID, "yf_train_head_loss_hyp: lambda_box must be finite and >= 0");
+    const double opt[8] = {obj_pw, cls_pw, label_smoothing, fl_gamma, fl_alpha, obj_iou, lambda_conf, lambda_cls};
+    for (double v : opt)
+        if (!std::isfinite(v)) return fail(YF_E_INVALID, "yf_train_head_loss_hyp: every option must be finite");
+    if (!(obj_pw > 0.0 && cls_pw > 0.0)) return fail(YF_E_INVALID, "yf_train_head_loss_hyp: obj_pw and cls_pw must be > 0");
+    if (!(label_smoothing >= 0.0 && label_smoothing <= 1.0)) return fail(YF_E_INVALID, "yf_train_head_loss_hyp: label_smoothing must lie in 0 .. 1");
+    if (!(fl_gamma == 0.0 || fl_gamma >= 1.0))
+        return fail(YF_E_INVALID, "yf_train_head_loss_hyp: fl_gamma must be 0 or >= 1 (the derivative is unbounded at p_t = 1 in between)");
+    if (!(fl_alpha >= 0.0 && fl_alpha <= 1.0)) return fail(YF_E_INVALID, "yf_train_head_loss_hyp: fl_alpha must lie in 0 .. 1");
+    if (!(obj_iou >= 0.0 && obj_iou <= 1.0)) return fail(YF_E_INVALID, "yf_train_head_loss_hyp: obj_iou must lie in 0 .. 1");
+    if (obj_iou > 0.0 && box_kind == YF_BOX_REF)
+        return fail(YF_E_INVALID, "yf_train_head_loss_hyp: obj_iou > 0 needs an IoU-family box_kind (YF_BOX_REF has no IoU value)");
+    if (!(lambda_conf >= 0.0 && lambda_cls >= 0.0)) return fail(YF_E_INVALID, "yf_train_head_loss_hyp: lambda_conf and lambda_cls must be >= 0");
+    if (work_bytes < yf::train_loss_box_workspace_bytes(N, fh, fw, num_anchors, num_classes))
+        return fail(YF_E_WORKSPACE, "yf_train_head_loss_hyp: workspace too small");
+    if (reinterpret_cast<uintptr_t>(d_work) & 7) return fail(YF_E_INVALID, "yf_train_head_loss_hyp: workspace must be 8-byte aligned");
+    HIP_OK(hipSetDevice(device));
+    const double stride_h = (double)H / fh, stride_w = (double)W / fw;      // as in yf_train_head_loss_ex
+    float anc[2 * yf::POST_MAX_ANCHORS];
+    for (int a = 0; a < num_anchors; ++a) { anc[2 * a] = (float)(anchors[2 * a] / stride_w); anc[2 * a + 1] = (float)(anchors[2 * a + 1] / stride_h); }
+    yf::launch_train_loss_hyp(d_head, N, fh, fw, anc, num_anchors, num_classes, d_targets, T, (float)ignore_thres, d_work, d_losses, d_grad_head,
+                              box_kind, lambda_box, opt, (hipStream_t)stream);
+    HIP_OK(hipGetLastError());
+    return YF_OK;
+}
+
 
 int yf_detect(yf_handle h, const float* d_x, int N, double conf_thres, double nms_thres, const double* anchors, int origin_h,
               int origin_w, int K_max, int32_t* d_boxes, float* d_scores, int32_t* d_cls, int32_t* d_src, int32_t* d_counts,

@@ -358,6 +358,10 @@ void launch_train_loss(const float* head, int N, int fh, int fw, const float* an
 size_t train_loss_box_workspace_bytes(int N, int fh, int fw, int na, int nc);
 void launch_train_loss_box(const float* head, int N, int fh, int fw, const float* anc, int na, int nc, const float* targets, int T,
                            float ignore_thres, void* work, float* losses, float* grad, int box_kind, double lambda_box, hipStream_t s);
+// the same with yolov5's objectness / class options (opt[8]: the options of yf_train_head_loss_hyp in its order); the box entry's workspace
+void launch_train_loss_hyp(const float* head, int N, int fh, int fw, const float* anc, int na, int nc, const float* targets, int T,
+                           float ignore_thres, void* work, float* losses, float* grad, int box_kind, double lambda_box, const double* opt,
+                           hipStream_t s);
 // training-step operators (yf_train_kernels.hip): NCHW fp32, correctness-first
 // BatchNorm's partial sums out of the conv's epilogue (the large maps): the caller sets part / cap_bytes (a region no concurrent kernel
 // uses: behind BatchNorm's own megabyte of the scratch), the conv launcher sets count (> 0: it left count pairs per channel in

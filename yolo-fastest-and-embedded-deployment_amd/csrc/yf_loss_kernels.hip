@@ -10,11 +10,15 @@
 //
 // yf_train_head_loss_box (opt-in) regresses the box as ONE IoU-family term per positive cell in place of the reference's four
 // (yf_box_term.h): two more target planes, loss_cells_kernel<GRAD, true> and loss_final_box_kernel, the same five launches.
+//
+// yf_train_head_loss_hyp (opt-in) adds yolov5's objectness / class options to either: loss_cells_kernel<GRAD, BOX, true> evaluates the
+// BCE elements a non-neutral option touches through yf_loss_term.h, loss_final_hyp_kernel applies the two gains; five launches again.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
 #include "yf_box_term.h"
+#include "yf_loss_term.h"
 #include "yf_kernels.h"
 
 namespace yf {
@@ -83,17 +87,32 @@ __device__ __forceinline__ float bce(float p, float t) { return -(t * fmaxf(logf
 // its derivative with respect to p: (p - t) / max((1 - p) p, 1e-12)
 __device__ __forceinline__ float dbce(float p, float t) { return (p - t) / fmaxf((1.f - p) * p, 1e-12f); }
 __device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
+// d(conf) / d(confidence logit) and d(cls) / d(class logit) of the reference's terms in float32: inv = 1 / E, m and nm the two masks
+__device__ __forceinline__ float conf_grad(float pc, float m, float nm, float inv)
+{
+    return inv * (dbce(pc * m, m) * m + 0.5f * dbce(pc * nm, 0.f) * nm) * (1.f - pc) * pc;
+}
+__device__ __forceinline__ float cls_grad(float pk, float tk, int nc, float npos) { return dbce(pk, tk) * (1.f - pk) * pk / ((float)nc * npos); }
 
 // what loss_cells_kernel<GRAD, true> needs on top: the anchors the targets were matched with, which IoU-family term, and its weight
 struct LossBox { LossAnchors anc; int na, kind; double lambda; };
+// what loss_cells_kernel<GRAD, BOX, true> needs on top of that: the options of yf_train_head_loss_hyp by value.  cp, cn: the smoothed
+// class targets.  conf_plain / cls_plain: no option touches that term's elements (only its gain may differ from 1), which then stay the
+// float32 arithmetic of the other instantiations, bit for bit; otherwise they are loss_elem's, in double on the float32 sigmoid.
+struct LossHyp { double obj_pw, cls_pw, gamma, alpha, obj_iou, lambda_conf, lambda_cls; float cp, cn; int conf_plain, cls_plain; };
+struct LossBoxHyp : LossBox { LossHyp hyp; };
+template <bool HYP> struct LossArgs { using type = LossBox; };
+template <> struct LossArgs<true> { using type = LossBoxHyp; };
 
 // acc: [0] sum bce x, [1] y, [2] sum (w)^2, [3] h, [4] conf obj, [5] conf noobj, [6] cls, [7] n_pos
 // BOX: [0] sum over the positive cells of 1 - value (yf_box_term.h, evaluated in double per positive cell: a float32 evaluation
 // cancels in GIoU's enclosing-area term for a clamped, huge box), [1..3] zero; channels 0..3 of the gradient are lambda / E times
 // its derivative, rounded to float32 once at the store, an exact 0 at every other cell.  Channels 4.. as without BOX.
-template <bool GRAD, bool BOX>
+// HYP: [4], [5], [6] are sums of loss_elem's elements where an option touches them (the objectness target of a positive cell is then
+// t_obj, the class targets cp / cn); channel 4 of the gradient carries lambda_conf, channels 5.. lambda_cls.
+template <bool GRAD, bool BOX, bool HYP = false>
 __global__ void __launch_bounds__(256) loss_cells_kernel(const float* __restrict__ head, const float* __restrict__ dense, long E, int fh, int fw,
-                                                         int nc, double* __restrict__ acc, float* __restrict__ grad, LossBox box)
+                                                         int nc, double* __restrict__ acc, float* __restrict__ grad, typename LossArgs<HYP>::type box)
 {
     const int attrs = 5 + nc;
     __shared__ double red[8][4];
@@ -108,12 +127,17 @@ __global__ void __launch_bounds__(256) loss_cells_kernel(const float* __restrict
         const float tx = dense[LT_TX * E + e], ty = dense[LT_TY * E + e], tw = dense[LT_TW * E + e], th = dense[LT_TH * E + e];
         const float dw = w * m - tw * m, dh = h * m - th * m;
         double dbox[4] = {0, 0, 0, 0};                       // BOX: d value / d logit of this cell
+        [[maybe_unused]] float tobj = 1.f;                   // HYP: the objectness target of a positive cell
+        [[maybe_unused]] double dobj = 0, dnoobj = 0;        // HYP: d element / d pc of the two confidence elements
         if constexpr (BOX) {
             if (m == 1.f) {
                 const int a = (int)(na % box.na);
                 const double tl[4] = {(double)t[0], (double)t[hw], (double)w, (double)h};
-                s[0] = 1.0 - box_term(box.kind, tl, (double)box.anc.w[a], (double)box.anc.h[a], (double)tx, (double)ty,
-                                      (double)dense[(LT_C0 + nc) * E + e], (double)dense[(LT_C0 + nc + 1) * E + e], GRAD ? dbox : nullptr);
+                const double value = box_term(box.kind, tl, (double)box.anc.w[a], (double)box.anc.h[a], (double)tx, (double)ty,
+                                              (double)dense[(LT_C0 + nc) * E + e], (double)dense[(LT_C0 + nc + 1) * E + e], GRAD ? dbox : nullptr);
+                s[0] = 1.0 - value;
+                if constexpr (HYP)                           // a constant in the backward (yolov5's iou.detach().clamp(0))
+                    if (box.hyp.obj_iou > 0.0) tobj = (float)((1.0 - box.hyp.obj_iou) + box.hyp.obj_iou * fmin(fmax(value, 0.0), 1.0));
             }
         } else {
             s[0] = bce(px * m, tx * m);                      // yolo_loss.py:78-79
@@ -121,10 +145,23 @@ __global__ void __launch_bounds__(256) loss_cells_kernel(const float* __restrict
             s[2] = dw * dw;                                  // :80-81
             s[3] = dh * dh;
         }
-        s[4] = bce(pc * m, m);                               // :84
-        s[5] = bce(pc * nm, nm * 0.f);
+        bool conf_plain = true, cls_plain = true;
+        if constexpr (HYP) { conf_plain = box.hyp.conf_plain; cls_plain = box.hyp.cls_plain; }
+        if (conf_plain) {
+            s[4] = bce(pc * m, m);                           // :84
+            s[5] = bce(pc * nm, nm * 0.f);
+        } else if constexpr (HYP) {                          // both masks are 0 or 1; a masked-out element is an exact 0, as above
+            if (m == 1.f) s[4] = loss_elem((double)pc, (double)tobj, box.hyp.obj_pw, box.hyp.gamma, box.hyp.alpha, GRAD ? &dobj : nullptr);
+            if (nm == 1.f) s[5] = loss_elem((double)pc, 0.0, 1.0, box.hyp.gamma, box.hyp.alpha, GRAD ? &dnoobj : nullptr);
+        }
         if (m == 1.f) {                                      // :87 pred_cls[mask == 1]
-            for (int k = 0; k < nc; ++k) s[6] += bce(sigm(t[(5 + k) * hw]), dense[(LT_C0 + k) * E + e]);
+            if (cls_plain) {
+                for (int k = 0; k < nc; ++k) s[6] += bce(sigm(t[(5 + k) * hw]), dense[(LT_C0 + k) * E + e]);
+            } else if constexpr (HYP) {
+                for (int k = 0; k < nc; ++k)
+                    s[6] += loss_elem((double)sigm(t[(5 + k) * hw]), (double)(dense[(LT_C0 + k) * E + e] == 1.f ? box.hyp.cp : box.hyp.cn),
+                                      box.hyp.cls_pw, box.hyp.gamma, box.hyp.alpha, nullptr);
+            }
             s[7] = 1.0;
         }
         if constexpr (GRAD) {
@@ -140,14 +177,32 @@ __global__ void __launch_bounds__(256) loss_cells_kernel(const float* __restrict
                 g[2 * hw] = 2.5f * inv * 2.f * dw * m;
                 g[3 * hw] = 2.5f * inv * 2.f * dh * m;
             }
-            g[4 * hw] = inv * (dbce(pc * m, m) * m + 0.5f * dbce(pc * nm, 0.f) * nm) * (1.f - pc) * pc;
-            for (int k = 0; k < nc; ++k) {
-                float gk = 0.f;
-                if (m == 1.f) {
-                    const float pk = sigm(t[(5 + k) * hw]), tk = dense[(LT_C0 + k) * E + e];
-                    gk = dbce(pk, tk) * (1.f - pk) * pk / ((float)nc * npos);
+            if constexpr (!HYP) {
+                g[4 * hw] = conf_grad(pc, m, nm, inv);
+                for (int k = 0; k < nc; ++k)
+                    g[(5 + k) * hw] = m == 1.f ? cls_grad(sigm(t[(5 + k) * hw]), dense[(LT_C0 + k) * E + e], nc, npos) : 0.f;
+            } else {
+                // total = [box part] + lambda_conf conf + lambda_cls cls.  A plain term: the float32 value above times the float32 gain (a
+                // gain of 2 doubles its bits); otherwise everything in double, rounded to float32 once at the store
+                const LossHyp& hp = box.hyp;
+                if (conf_plain)
+                    g[4 * hw] = (float)hp.lambda_conf * conf_grad(pc, m, nm, inv);
+                else
+                    g[4 * hw] = (float)(hp.lambda_conf / (double)E * (dobj + 0.5 * dnoobj) * (1.0 - (double)pc) * (double)pc);
+                for (int k = 0; k < nc; ++k) {
+                    float gk = 0.f;
+                    if (m == 1.f) {
+                        const float pk = sigm(t[(5 + k) * hw]), tk = dense[(LT_C0 + k) * E + e];
+                        if (cls_plain) {
+                            gk = (float)hp.lambda_cls * cls_grad(pk, tk, nc, npos);
+                        } else {
+                            double d;
+                            loss_elem((double)pk, (double)(tk == 1.f ? hp.cp : hp.cn), hp.cls_pw, hp.gamma, hp.alpha, &d);
+                            gk = (float)(hp.lambda_cls * d * (1.0 - (double)pk) * (double)pk / ((double)nc * acc[7]));
+                        }
+                    }
+                    g[(5 + k) * hw] = gk;
                 }
-                g[(5 + k) * hw] = gk;
             }
             return;
         }
@@ -183,6 +238,24 @@ __global__ void loss_final_box_kernel(const double* __restrict__ acc, long E, in
     const float lcls = (float)(acc[6] / ((double)nc * acc[7]));     // no positive cell: nan, as in loss_final_kernel
     losses[0] = lambda * lbox + lconf * 1.0f + lcls * 1.0f;
     losses[1] = lbox; losses[2] = 0.f; losses[3] = 0.f; losses[4] = 0.f; losses[5] = lconf; losses[6] = lcls;
+    losses[7] = (float)acc[8];
+}
+
+// yf_train_head_loss_hyp: either of the two above with the gains on conf and cls in the total; [5] and [6] stay unweighted
+__global__ void loss_final_hyp_kernel(const double* __restrict__ acc, long E, int nc, int box, float lambda, float lambda_conf, float lambda_cls,
+                                      float* __restrict__ losses)
+{
+    const float lx = (float)(acc[0] / (double)E), ly = (float)(acc[1] / (double)E), lw = (float)(acc[2] / (double)E), lh = (float)(acc[3] / (double)E);
+    const float lconf = (float)(acc[4] / (double)E) + 0.5f * (float)(acc[5] / (double)E);
+    const float lcls = (float)(acc[6] / ((double)nc * acc[7]));     // no positive cell: nan, as in loss_final_kernel
+    if (box) {
+        losses[0] = lambda * lx + lconf * lambda_conf + lcls * lambda_cls;
+        losses[1] = lx; losses[2] = 0.f; losses[3] = 0.f; losses[4] = 0.f;
+    } else {
+        losses[0] = lx * 2.5f + ly * 2.5f + lw * 2.5f + lh * 2.5f + lconf * lambda_conf + lcls * lambda_cls;
+        losses[1] = lx; losses[2] = ly; losses[3] = lw; losses[4] = lh;
+    }
+    losses[5] = lconf; losses[6] = lcls;
     losses[7] = (float)acc[8];
 }
 
@@ -231,6 +304,43 @@ void launch_train_loss_box(const float* head, int N, int fh, int fw, const float
                            float ignore_thres, void* work, float* losses, float* grad, int box_kind, double lambda_box, hipStream_t s)
 {
     launch_loss(head, N, fh, fw, anc, na, nc, targets, T, ignore_thres, work, losses, grad, box_kind, lambda_box, s);
+}
+
+// opt[8] = obj_pw, cls_pw, label_smoothing, fl_gamma, fl_alpha, obj_iou, lambda_conf, lambda_cls (validated by the entry).  With every
+// option neutral this IS launch_train_loss_box: the same kernels, hence the same bits.
+void launch_train_loss_hyp(const float* head, int N, int fh, int fw, const float* anc, int na, int nc, const float* targets, int T,
+                           float ignore_thres, void* work, float* losses, float* grad, int box_kind, double lambda_box, const double* opt,
+                           hipStream_t s)
+{
+    const bool focal = opt[3] > 0.0;
+    LossHyp hp{};
+    hp.obj_pw = opt[0]; hp.cls_pw = opt[1]; hp.gamma = opt[3]; hp.alpha = opt[4]; hp.obj_iou = opt[5]; hp.lambda_conf = opt[6]; hp.lambda_cls = opt[7];
+    hp.cp = (float)(1.0 - 0.5 * opt[2]); hp.cn = (float)(0.5 * opt[2]);
+    hp.conf_plain = opt[0] == 1.0 && !focal && opt[5] == 0.0;
+    hp.cls_plain = opt[1] == 1.0 && !focal && opt[2] == 0.0;
+    if (hp.conf_plain && hp.cls_plain && opt[6] == 1.0 && opt[7] == 1.0) {
+        launch_loss(head, N, fh, fw, anc, na, nc, targets, T, ignore_thres, work, losses, grad, box_kind, lambda_box, s);
+        return;
+    }
+    const long E = (long)N * na * fh * fw;
+    LossBoxHyp lb{};
+    for (int a = 0; a < na && a < LOSS_MAX_ANCHORS; ++a) { lb.anc.w[a] = anc[2 * a]; lb.anc.h[a] = anc[2 * a + 1]; }
+    lb.na = na; lb.kind = box_kind; lb.lambda = lambda_box; lb.hyp = hp;
+    double* acc = reinterpret_cast<double*>(work);
+    float* dense = reinterpret_cast<float*>(static_cast<char*>(work) + 16 * sizeof(double));
+    const unsigned nb = (unsigned)((E + 255) / 256);
+    hipLaunchKernelGGL(loss_init_kernel, dim3(nb), dim3(256), 0, s, dense, E, LT_C0 + nc + 2, acc);
+    hipLaunchKernelGGL(loss_targets_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, s, targets, T, dense, E, N, fh, fw, lb.anc, na, nc,
+                       ignore_thres, acc, 1);
+    if (box_kind > 0) {
+        hipLaunchKernelGGL((loss_cells_kernel<false, true, true>), dim3(nb), dim3(256), 0, s, head, dense, E, fh, fw, nc, acc, (float*)nullptr, lb);
+        if (grad) hipLaunchKernelGGL((loss_cells_kernel<true, true, true>), dim3(nb), dim3(256), 0, s, head, dense, E, fh, fw, nc, acc, grad, lb);
+    } else {
+        hipLaunchKernelGGL((loss_cells_kernel<false, false, true>), dim3(nb), dim3(256), 0, s, head, dense, E, fh, fw, nc, acc, (float*)nullptr, lb);
+        if (grad) hipLaunchKernelGGL((loss_cells_kernel<true, false, true>), dim3(nb), dim3(256), 0, s, head, dense, E, fh, fw, nc, acc, grad, lb);
+    }
+    hipLaunchKernelGGL(loss_final_hyp_kernel, dim3(1), dim3(1), 0, s, acc, E, nc, (int)(box_kind > 0), (float)lambda_box, (float)hp.lambda_conf,
+                       (float)hp.lambda_cls, losses);
 }
 
 }  // namespace yf

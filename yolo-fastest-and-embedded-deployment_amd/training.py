@@ -891,8 +891,13 @@ def cosine_factor(epoch, total_epochs):
     return ((1 + math.cos(epoch * math.pi / total_epochs)) / 2) * 0.8 + 0.2
 
 
+# train(loss_hyp=...): yolov5's key -> validation.YOLOLossV3's keyword
+LOSS_HYP_KEYS = {"obj": "lambda_conf", "cls": "lambda_cls", "obj_pw": "obj_pw", "cls_pw": "cls_pw", "fl_gamma": "fl_gamma",
+                 "label_smoothing": "label_smoothing", "gr": "obj_iou", "fl_alpha": "fl_alpha"}
+
+
 def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, logger=None, val_match="host", optimizer=None,
-          branch_weight=False, ema=False, box_loss=None, lambda_box=5.0, val_metrics=False, val_nms="reference"):
+          branch_weight=False, ema=False, box_loss=None, lambda_box=5.0, val_metrics=False, val_nms="reference", loss_hyp=None):
     """The reference's `train(params, device, tbwriter)` (train.py:44-160) with the iteration on the GPU kernels of this package.
     Same control flow and arithmetic: one YOLOLossV3 per stride (:50-53), the model from `pretrained_pth` or initialize_weights()
     (:58-65), DataLoader(batch_size, drop_last, shuffle) (:71-73), Adam(lr0, betas (0.9, 0.999), eps 1e-8) (:84), the cosine
@@ -921,6 +926,13 @@ def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, l
     lambda_box = 5.0 is the sum of the reference's weights on x, y and on w, h; nobody has trained with it.  tbwriter then gets the
     scalar `box` in place of `x`, and no `y`, `w`, `h`.  It composes with branch_weight and ema (train_step is unchanged).  The decode
     stays the reference's, so the checkpoints load into detect.py as before.
+    `loss_hyp`, opt-in like these: a dict with the loss keys of yolov5's hyp files -- `obj`, `cls`, `obj_pw`, `cls_pw`, `fl_gamma`,
+    `label_smoothing`, plus `gr` (yolov5's model.gr) and `fl_alpha` -- handed to both heads' YOLOLossV3 (yf_train_head_loss_hyp;
+    include/yolo_fastest_hip.h states the definition).  `obj` and `cls` are PLAIN gains on conf and cls in the total: they are not
+    rescaled by the class count or the image size as yolov5's train.py rescales its own.  A missing key keeps its neutral value; an unknown
+    key, a value the entry refuses, or gr > 0 without box_loss raises ValueError.  None (the default) constructs the loss objects as
+    before.  yolov5's files use fl_gamma 0 or 1.5 and gr 1; no values are recommended, and nothing here has been trained with any of
+    them.  It composes with branch_weight, ema, optimizer and box_loss (train_step is unchanged); the decode is untouched.
     `val_metrics=True`, opt-in like these: on the epochs where get_mAP runs, Validation.get_metrics (yolov5's P, R, mAP@.5, mAP@.5:.95 at
     conf_thres 0.001) runs right behind it on the same model (`ema.ema` with ema=True) and logs its table; tbwriter gets
     `metrics/precision`, `metrics/recall`, `metrics/mAP_0.5` and `metrics/mAP_0.5:0.95` per epoch, and rank 0 writes the validated model's
@@ -946,6 +958,16 @@ def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, l
         raise ValueError("val_nms must be 'reference' or 'yolov5', not %r" % (val_nms,))
     if val_nms != "reference" and not val_metrics:
         raise ValueError("val_nms=%r is read by get_metrics only: pass val_metrics=True" % (val_nms,))
+    hyp_kwargs = {}
+    if loss_hyp is not None:
+        unknown = sorted(set(loss_hyp) - set(LOSS_HYP_KEYS))
+        if unknown:
+            raise ValueError("loss_hyp: unknown key(s) %s; known: %s" % (", ".join(map(repr, unknown)), ", ".join(LOSS_HYP_KEYS)))
+        hyp_kwargs = {LOSS_HYP_KEYS[k]: float(v) for k, v in loss_hyp.items()}
+        if hyp_kwargs.get("obj_iou", 0.0) > 0 and box_loss is None:
+            raise ValueError("loss_hyp['gr'] > 0 needs box_loss: the reference's four coordinate terms have no IoU value")
+        validation.YOLOLossV3(anchors=io["anchors"][0], num_classes=io["num_cls"], input_shape=io["input_shape"], device=device,
+                              box_loss=box_loss, lambda_box=lambda_box, **hyp_kwargs)       # every other refusal, before anything is built
     head_weights = None
     if branch_weight:
         head_weights = [float(v) for v in tp["branch_weight"]]
@@ -956,7 +978,7 @@ def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, l
     total_epochs, batch_size = tp["total_epochs"], tp["batch_size"]
     model = YoloFastest(io).to(device)
     model_loss = [validation.YOLOLossV3(anchors=io["anchors"][i], num_classes=io["num_cls"], input_shape=io["input_shape"], device=device,
-                                        model=model, box_loss=box_loss, lambda_box=lambda_box) for i in range(len(io["strides"]))]
+                                        model=model, box_loss=box_loss, lambda_box=lambda_box, **hyp_kwargs) for i in range(len(io["strides"]))]
     for ml in model_loss:
         ml.ignore_threshold = tp.get("IOU_loss_thre", 0.5)
     if tp.get("pretrained_pth") and os.path.exists(tp["pretrained_pth"]):

@@ -34,14 +34,44 @@ def _engine(t, H, W, model=None):
 
 
 BOX_KINDS = {"giou": 1, "diou": 2, "ciou": 3}        # YF_BOX_GIOU, YF_BOX_DIOU, YF_BOX_CIOU
+# the options of yf_train_head_loss_hyp in its argument order, with their neutral values (fl_alpha is not read while fl_gamma is 0)
+LOSS_HYP_DEFAULTS = (("obj_pw", 1.0), ("cls_pw", 1.0), ("label_smoothing", 0.0), ("fl_gamma", 0.0), ("fl_alpha", 0.25), ("obj_iou", 0.0),
+                     ("lambda_conf", 1.0), ("lambda_cls", 1.0))
+
+
+def check_loss_hyp(box_loss, obj_pw, cls_pw, label_smoothing, fl_gamma, fl_alpha, obj_iou, lambda_conf, lambda_cls):
+    """ValueError for what yf_train_head_loss_hyp refuses -> the eight options as floats, in its argument order"""
+    v = [float(x) for x in (obj_pw, cls_pw, label_smoothing, fl_gamma, fl_alpha, obj_iou, lambda_conf, lambda_cls)]
+    for (name, _), x in zip(LOSS_HYP_DEFAULTS, v):
+        if not math.isfinite(x):
+            raise ValueError("%s must be finite, got %r" % (name, x))
+    if v[0] <= 0 or v[1] <= 0:
+        raise ValueError("obj_pw and cls_pw must be > 0, got %r and %r" % (v[0], v[1]))
+    for i in (2, 4, 5):
+        if not 0.0 <= v[i] <= 1.0:
+            raise ValueError("%s must lie in 0 .. 1, got %r" % (LOSS_HYP_DEFAULTS[i][0], v[i]))
+    if v[3] < 0 or 0 < v[3] < 1:
+        raise ValueError("fl_gamma must be 0 or >= 1 (the focal derivative is unbounded at p_t = 1 in between), got %r" % v[3])
+    if v[5] > 0 and box_loss is None:
+        raise ValueError("obj_iou > 0 needs box_loss: the reference's four coordinate terms have no IoU value")
+    if v[6] < 0 or v[7] < 0:
+        raise ValueError("lambda_conf and lambda_cls must be >= 0, got %r and %r" % (v[6], v[7]))
+    return tuple(v)
 
 
 class YOLOLossV3(torch.nn.Module):
-    def __init__(self, anchors, num_classes, input_shape, device, model=None, box_loss=None, lambda_box=5.0):
+    def __init__(self, anchors, num_classes, input_shape, device, model=None, box_loss=None, lambda_box=5.0, obj_pw=1.0, cls_pw=1.0,
+                 label_smoothing=0.0, fl_gamma=0.0, fl_alpha=0.25, obj_iou=0.0, lambda_conf=1.0, lambda_cls=1.0):
         """`box_loss` (opt-in; None = the reference's four coordinate terms, exactly as before): "giou", "diou" or "ciou" regresses the box
         of a positive cell as one IoU-family term (yf_train_head_loss_box; include/yolo_fastest_hip.h states the definition), and the
         training loss is lambda_box * box + conf + cls.  lambda_box = 5.0 is the sum of the reference's weights on x, y and on w, h;
-        nobody has trained with it.  The decode (no targets) is the reference's either way."""
+        nobody has trained with it.  The decode (no targets) is the reference's either way.
+        The eight keyword arguments behind it (opt-in; the defaults are neutral and leave the entry called above as it is) are yolov5's
+        objectness / class options (yf_train_head_loss_hyp; the header states the definition): `obj_pw`, `cls_pw` the BCE positive
+        weights, `label_smoothing` the eps of smooth_BCE, `fl_gamma` / `fl_alpha` the focal loss around every BCE element (gamma 0: off,
+        alpha not read; 0 < gamma < 1 is refused), `obj_iou` yolov5's gr (the objectness target of a positive cell follows the clamped
+        IoU value; needs `box_loss`), `lambda_conf` / `lambda_cls` plain gains on conf and cls in the total (the returned conf and cls stay
+        unweighted).  yolov5's hyp files use fl_gamma 0 or 1.5 and gr 1; nothing here has been trained with any of them."""
         super().__init__()
         # the YoloFastest whose heads this decodes (None: validation.bind's default).  NOT registered as a submodule: the loss object's
         # .train() / .eval() / .to() / state_dict() must not reach into the network (the reference's YOLOLossV3 does not hold the model)
@@ -61,6 +91,7 @@ class YOLOLossV3(torch.nn.Module):
             raise ValueError("lambda_box must be finite and >= 0, got %r" % (lambda_box,))
         self.box_loss = box_loss
         self.lambda_box = float(lambda_box)
+        self.loss_hyp = check_loss_hyp(box_loss, obj_pw, cls_pw, label_smoothing, fl_gamma, fl_alpha, obj_iou, lambda_conf, lambda_cls)
 
     def forward(self, input, targets=None):
         if targets is not None:
@@ -96,7 +127,12 @@ class _TrainLossFn(torch.autograd.Function):
         need = ctypes.c_size_t()
         na, nc = loss_mod.num_anchors, loss_mod.num_classes
         box = loss_mod.box_loss
-        if box is None:
+        hyp = loss_mod.loss_hyp
+        if all(v == d for v, (name, d) in zip(hyp, LOSS_HYP_DEFAULTS) if name != "fl_alpha"):
+            hyp = None                                       # every option neutral: exactly the entries below
+        if hyp is not None:
+            _lib.check(lib.yf_train_head_loss_hyp_workspace_bytes(bs, fh, fw, na, nc, ctypes.byref(need)))
+        elif box is None:
             _lib.check(lib.yf_train_head_loss_workspace_bytes_ex(bs, fh, fw, na, nc, ctypes.byref(need)))
         else:
             _lib.check(lib.yf_train_head_loss_box_workspace_bytes(bs, fh, fw, na, nc, ctypes.byref(need)))
@@ -105,7 +141,12 @@ class _TrainLossFn(torch.autograd.Function):
         grad = torch.empty_like(x)
         anc = (ctypes.c_double * (2 * na))(*[float(v) for a in loss_mod.anchors for v in a[:2]])
         stream = torch.cuda.current_stream(x.device).cuda_stream
-        if box is None:
+        if hyp is not None:
+            _lib.check(lib.yf_train_head_loss_hyp(dev_index, H, W, x.data_ptr(), bs, fh, fw, anc, na, nc, targets.data_ptr(), targets.shape[1],
+                                                  float(loss_mod.ignore_threshold), work.data_ptr(), work.numel() * 8, losses.data_ptr(),
+                                                  grad.data_ptr(), ctypes.c_void_p(stream), BOX_KINDS[box] if box else 0, loss_mod.lambda_box,
+                                                  *hyp))
+        elif box is None:
             _lib.check(lib.yf_train_head_loss_ex(dev_index, H, W, x.data_ptr(), bs, fh, fw, anc, na, nc, targets.data_ptr(), targets.shape[1],
                                                  float(loss_mod.ignore_threshold), work.data_ptr(), work.numel() * 8, losses.data_ptr(),
                                                  grad.data_ptr(), ctypes.c_void_p(stream)))
