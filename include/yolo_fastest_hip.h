@@ -695,6 +695,10 @@ int yf_op_dtype(yf_handle h, int op, int *kernel_dtype);
 /* Kernel dispatches launch `op` issues at batch N: 1, except a chained residual launch at small batches, which is issued block by block
  * (DESIGN.md section 4 "Small batches").  Counter tools that match rocprofv3's dispatch rows to launches by order need it. */
 int yf_op_dispatches(yf_handle h, int op, int N, int *dispatches);
+/* Kernel dispatches decode + NMS issue for N frames with room for K_max survivors each, under the present yf_set_post_split mode: 2 where
+ * the per-(frame, class) form runs (post_split_kernel + the assembly launch), 1 for one workgroup per frame (also the fall-back above 64
+ * classes, whatever the mode). */
+int yf_post_dispatches(yf_handle h, int N, int K_max, int *dispatches);
 /* One forward pass (whole batch in one pass) with a HIP event recorded on `stream` around every launch; blocks until
  * the pass is done and returns each launch's duration in ms in op_ms[yf_num_launches]. */
 int yf_profile_forward(yf_handle h, const float *d_x, int N, void *d_workspace, size_t workspace_bytes, void *stream,

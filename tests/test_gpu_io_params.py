@@ -6,7 +6,10 @@ REFERENCE module / post-process / loss on numpy-seeded weights and inputs for ev
   c1 (1 class), c5rgb (5 classes, 3-channel input), c20 (20 classes: 75 head channels, the run-time head loop), a2 (2 anchors),
   c80rgb (80 classes: 255 head channels, 3-channel input).
 Tolerances as in test_gpu_parity.py: heads within max(3 x E, 5e-5) of the graph in fp64 (E = the reference's own fp32 distance from
-it), decode + NMS bit-exact including order given identical logits."""
+it), decode + NMS bit-exact including order given identical logits.
+The per-launch criteria of the stem and head launches at these io_params (every tile form and head mode, tens of fp32 ulps / a few fp16
+ulps per launch) are in tests/test_gpu_io_replay.py; the randomised decode + NMS battery at other (num_cls, num_anchors) in
+tests/test_gpu_io_post.py."""
 import ctypes
 import os
 

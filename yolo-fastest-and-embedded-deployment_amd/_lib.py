@@ -175,6 +175,7 @@ _SIGS = {
                                      _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "yf_draw_boxes_u8": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "yf_op_dispatches": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(_c.c_int)]),
+    "yf_post_dispatches": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(_c.c_int)]),
     "yf_profile_head_offsets": (_c.c_int, [_c.c_void_p, _c.c_int, _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_size_t)]),
 }
 EXPORTS = tuple(_SIGS)

@@ -1091,11 +1091,16 @@ static yf::PostArgs make_post_args(yf_handle h, const float* d_hl, const float* 
 // frames), the model has <= 8 classes and one workgroup per frame would leave at least half of the CUs idle (2 N <= #CU: with 256 dense
 // 320x256 frames the per-frame form is the faster one, 0.057 against 0.075 ms).  The scratch is the engine's, grown on demand (the first dense
 // call of a size allocates: not inside a stream capture); lanes of one batch use disjoint frame ranges of it.
-static int post_setup(yf_handle h, yf::PostArgs& a, int N)
+static bool post_takes_split(yf_handle h, int nc, int kmax, int N)
 {
     const int n_cu = yf::device_cu_count(h->device);
-    const bool on = h->post_split == 1 || (h->post_split == 0 && a.kmax >= 256 && a.nc <= 8 && n_cu > 0 && 2 * N <= n_cu);
-    if (!on || a.nc > 64) return YF_OK;
+    const bool on = h->post_split == 1 || (h->post_split == 0 && kmax >= 256 && nc <= 8 && n_cu > 0 && 2 * N <= n_cu);
+    return on && nc <= 64;
+}
+
+static int post_setup(yf_handle h, yf::PostArgs& a, int N)
+{
+    if (!post_takes_split(h, a.nc, a.kmax, N)) return YF_OK;
     const size_t need = yf::post_split_tmp_ints(N, a.nc, a.kmax);
     if (need > h->post_tmp_ints) {
         if (h->d_post_tmp) { HIP_OK(hipDeviceSynchronize()); (void)hipFree(h->d_post_tmp); h->d_post_tmp = nullptr; h->post_tmp_ints = 0; }
@@ -1652,6 +1657,13 @@ int yf_op_dispatches(yf_handle h, int op, int N, int* dispatches)
         const Tensor& ti = h->plan().tensors[o.in1];
         if (yf::mdw2_esplit_ok(ti.H, ti.W, h->num_out, N, o.kdt, h->split_sums ? h->d_esplit : nullptr)) *dispatches = 3;
     }
+    return YF_OK;
+}
+
+int yf_post_dispatches(yf_handle h, int N, int K_max, int* dispatches)
+{
+    if (!h || !dispatches || N <= 0 || K_max <= 0) return fail(YF_E_INVALID, "yf_post_dispatches: bad argument");
+    *dispatches = post_takes_split(h, h->num_cls, K_max, N) ? 2 : 1;
     return YF_OK;
 }
 
