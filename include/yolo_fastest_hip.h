@@ -527,6 +527,52 @@ int yf_cv_preprocess_u8(yf_handle h, const uint8_t *d_src, int N, int src_h, int
 int yf_forward_bgr_u8(yf_handle h, const uint8_t *d_bgr, int N, int src_h, int src_w, int gray_bits, float *d_head_large, float *d_head_small,
                       void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* yolov5's letterbox in front of the net and its scale_boxes behind the NMS (opt-in; the reference squashes every frame to the net's size
+ * and scales every box to the CONFIGURED original shape: yf_cv_preprocess_u8, the origin_h / origin_w of yf_decode_nms).
+ *
+ * The rule.  H, W: the net's input size, C its channels (1 or 3); the frame is uint8 [h, w, 3], BGR.  Geometry is yolov5's
+ * letterbox(im, (H, W), auto=False, scaleFill=False, scaleup=True), in IEEE double with Python's round (half to even):
+ *     r      = min(H / h, W / w)
+ *     new_w  = int(round(w * r));  new_h = int(round(h * r))
+ *     dw, dh = (W - new_w) / 2, (H - new_h) / 2
+ *     top, bottom = int(round(dh - 0.1)), int(round(dh + 0.1));   left, right = int(round(dw - 0.1)), int(round(dw + 0.1))
+ * Pixels, in the reference's order of operations (detect.py:110-116): BGR2GRAY first when C == 1; then cv2.resize(img, (new_w, new_h)) with
+ * the arithmetic of yf_cv_preprocess_u8 -- 11-bit INTER_LINEAR, exactly 1/2 in both directions -> the 2x2 mean, same size -> a copy, decided
+ * on (h, w) against (new_h, new_w), not against (H, W) --; then cv2.copyMakeBorder(top, bottom, left, right, value=114): every destination
+ * byte outside [top, top + new_h) x [left, left + new_w) is 114, in all channels.  A frame of the net's aspect ratio comes out as
+ * yf_cv_preprocess_u8's bytes with no border.
+ * Boxes come back by yolov5's scale_boxes((H, W), boxes, (h, w)) with ratio_pad=None, then .round(); in double, per coordinate:
+ *     gain = min(H / h, W / w);  pad_w = (W - w * gain) / 2;  pad_h = (H - h * gain) / 2
+ *     x' = round_half_even(clip((x - pad_w) / gain, 0, w));   y' = round_half_even(clip((y - pad_h) / gain, 0, h))
+ * -- yolov5's FLOAT pad, not the integer left / top the pixels were placed with (they differ by less than one source pixel).
+ * Not covered: auto=True (the minimal rectangle), scaleFill, scaleup=False.
+ *
+ * yf_letterbox_geometry: host only, never touches a GPU.  out = new_h, new_w, top, bottom, left, right.  YF_E_INVALID for a size <= 0.
+ *
+ * yf_cv_letterbox_u8: N frames of ANY sizes in ONE launch.  d_frames / heights / widths: HOST arrays of N device pointers (each a
+ * contiguous uint8 [h, w, 3] frame with no alignment requirement: its own allocation, a slice of a stack, a view) and their sizes.
+ * gray_bits: 0 = the three channels are kept (d_dst [N, dst_h, dst_w, 3], still BGR), 14 | 15 = BGR2GRAY with those coefficients
+ * (d_dst [N, dst_h, dst_w]).  The per-frame table (pointer, h, w and the six geometry integers: YF_LB_TABLE_ENTRY_BYTES each) is filled
+ * on the host into the caller's PINNED copy and uploaded on `stream` into d_table; as with yf_train_opt_multi_pinned the previous upload
+ * from h_table_pinned must have executed before the next call rewrites it (wait on an event recorded behind the call).  Stream-ordered:
+ * no allocation, no synchronisation.  The resize coefficients are computed inside the kernel from (h -> new_h, w -> new_w) with the
+ * expressions of yf_cv_resize_tables: no table pool, no per-size cache.  Every source index is clamped to the frame; h == 1 and w == 1 are
+ * legal.  YF_E_INVALID before any launch for: N <= 0, a null pointer, a size <= 0, a side above 8192, gray_bits outside {0, 14, 15}, a
+ * table smaller than N entries, and a frame so thin that new_h or new_w rounds to 0 (cv2.resize raises there too).
+ *
+ * yf_scale_boxes: one launch, in place.  Rewrites the first min(max(count, 0), K_max) boxes (x1, y1, x2, y2 in net coordinates: the NMS
+ * run with origin 0, 0) of every frame by the rule above.  Frame f's boxes start at d_boxes + f * frame_stride, its count is
+ * d_counts[f * count_stride] (strides in int32 elements): the separate tensors of yf_decode_nms are (4 K_max, 1), the record block of
+ * yf_decode_nms_packed is (1 + 8 K_max, 1 + 8 K_max) with d_boxes = d_records + 1 and d_counts = d_records.  Slots past the count and
+ * frames with count -2 are left untouched, as is a frame whose d_frame_hw (device int32 [N, 2]: h, w) entry is not positive. */
+#define YF_LB_TABLE_ENTRY_BYTES 40
+#define YF_LB_MAX_SIDE 8192
+int yf_letterbox_geometry(int src_h, int src_w, int dst_h, int dst_w, int32_t out[6]);
+int yf_cv_letterbox_u8(int device, int N, const void *const *d_frames, const int *heights, const int *widths, int gray_bits, int dst_h, int dst_w,
+                       uint8_t *d_dst, void *d_table, size_t table_bytes, void *h_table_pinned, void *stream);
+int yf_scale_boxes(int device, int32_t *d_boxes, long frame_stride, const int32_t *d_counts, long count_stride, int N, int K_max, int net_h,
+                   int net_w, const int32_t *d_frame_hw, void *stream);
+
 /* The image half of the reference's DetectDataset.__getitem__ (src/model_training/dataloader/detect_dataset.py:90-103, :132-143) on the
  * device, handle-free like the training operators (a dataset owns no model), for N same-size source frames in ONE launch:
  *     x = fliplr?(GaussianBlur_k(resize(cvtColor_BGR2GRAY?(frame))))        per frame: k in {0 (none), 3, 5, 7}, flip in {0, 1}

@@ -17,6 +17,7 @@ _c = ctypes
 
 YF_OPT_ADAM, YF_OPT_SGD, YF_OPT_MAX_GROUPS, YF_OPT_TABLE_ENTRY_BYTES = 0, 1, 8, 56     # yf_train_opt_multi_pinned
 YF_OPT_EMA_TABLE_ENTRY_BYTES, YF_EMA_TABLE_ENTRY_BYTES = 64, 32                        # yf_train_opt_ema_multi_pinned, yf_train_ema_multi_pinned
+YF_LB_TABLE_ENTRY_BYTES, YF_LB_MAX_SIDE = 40, 8192                                     # yf_cv_letterbox_u8
 YF_VAL_NMS_V5_LDS_BUDGET, YF_VAL_NMS_V5_LDS_STATIC = 163840, 256                       # yf_val_nms_v5: where an image's key table sits
 
 
@@ -149,6 +150,11 @@ _SIGS = {
     "yf_cv_preprocess_u8": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p]),
     "yf_forward_bgr_u8": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p,
                                      _c.c_size_t, _c.c_void_p]),
+    "yf_letterbox_geometry": (_c.c_int, [_c.c_int] * 4 + [_c.POINTER(_c.c_int32)]),
+    "yf_cv_letterbox_u8": (_c.c_int, [_c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p,
+                                      _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_void_p]),   # device, N, frames / heights / widths (host), gray_bits, H, W, dst, table ...
+    "yf_scale_boxes": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_long, _c.c_void_p, _c.c_long, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p,
+                                  _c.c_void_p]),
     "yf_augment_u8": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p,
                                  _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "yf_augment_warp_u8": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p,

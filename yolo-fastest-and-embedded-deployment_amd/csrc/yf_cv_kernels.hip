@@ -240,16 +240,10 @@ void launch_mode(const CvArgs& a, unsigned grid, hipStream_t s)
 
 }  // namespace
 
-// cv::resize(INTER_LINEAR, 8-bit): the tables OpenCV's resize() builds on the host -- xofs / ialpha with the edge resets of its horizontal
-// pass, yofs / ibeta with clamped row indices -- from ITS float arithmetic (modules/imgproc/src/resize.cpp; restated in oracle/cv_oracle.py):
-// `scale = 1. / inv_scale` in double, `fx = (float)((dx + 0.5) * scale - 0.5)`, cvFloor, `cvRound(f * 2048)` (half to even).  IEEE double /
-// float operations, built with -ffp-contract=off: the device evaluates exactly what the host expression does.
-__global__ void cv_tables_kernel(int src_h, int src_w, int dst_h, int dst_w, int4* __restrict__ xtab, int4* __restrict__ ytab)
+// One entry {i0, i1, c0, c1} of those tables (see cv_tables_kernel below): destination index d of an axis resized src -> dst; isx: the
+// horizontal pass, which resets at the edges where the vertical pass clamps.  Both indices are inside [0, src - 1].
+__device__ __forceinline__ int4 cv_linear_coef(int d, int src, int dst, bool isx)
 {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= dst_w + dst_h) return;
-    const bool isx = i < dst_w;
-    const int d = isx ? i : i - dst_w, src = isx ? src_w : src_h, dst = isx ? dst_w : dst_h;
     const double inv_scale = (double)dst / (double)src, scale = 1.0 / inv_scale;
     float f = (float)(((double)d + 0.5) * scale - 0.5);
     int sidx = (int)floorf(f);
@@ -260,7 +254,20 @@ __global__ void cv_tables_kernel(int src_h, int src_w, int dst_h, int dst_w, int
     }
     const int c1 = (int)nearbyintf(f * 2048.f), c0 = (int)nearbyintf((1.f - f) * 2048.f);
     const int i0 = sidx < 0 ? 0 : (sidx > src - 1 ? src - 1 : sidx), i1 = sidx + 1 < 0 ? 0 : (sidx + 1 > src - 1 ? src - 1 : sidx + 1);
-    (isx ? xtab : ytab)[d] = make_int4(i0, i1, c0, c1);
+    return make_int4(i0, i1, c0, c1);
+}
+
+// cv::resize(INTER_LINEAR, 8-bit): the tables OpenCV's resize() builds on the host -- xofs / ialpha with the edge resets of its horizontal
+// pass, yofs / ibeta with clamped row indices -- from ITS float arithmetic (modules/imgproc/src/resize.cpp; restated in oracle/cv_oracle.py):
+// `scale = 1. / inv_scale` in double, `fx = (float)((dx + 0.5) * scale - 0.5)`, cvFloor, `cvRound(f * 2048)` (half to even).  IEEE double /
+// float operations, built with -ffp-contract=off: the device evaluates exactly what the host expression does.
+__global__ void cv_tables_kernel(int src_h, int src_w, int dst_h, int dst_w, int4* __restrict__ xtab, int4* __restrict__ ytab)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= dst_w + dst_h) return;
+    const bool isx = i < dst_w;
+    const int d = isx ? i : i - dst_w, src = isx ? src_w : src_h, dst = isx ? dst_w : dst_h;
+    (isx ? xtab : ytab)[d] = cv_linear_coef(d, src, dst, isx);
 }
 
 void launch_cv_tables(int src_h, int src_w, int dst_h, int dst_w, int4* xtab, int4* ytab, hipStream_t s)
@@ -282,6 +289,92 @@ int launch_cv_pre(const CvArgs& a, hipStream_t s)
     else if (a.gray == 15) launch_mode<15, 1>(a, grid, s);
     else if (a.gray == 0 && a.dc == 1) launch_mode<0, 1>(a, grid, s);
     else if (a.gray == 0) launch_mode<0, 3>(a, grid, s);
+    else return -1;
+    return 0;
+}
+
+// yolov5's letterbox (include/yolo_fastest_hip.h states the rule) for a RAGGED batch: frame n's table entry names its pixels, its size and
+// its geometry, and the destination [n, dh, dw(, 3)] is the same for every frame, so the grid is uniform: a workgroup owns LB_TR
+// destination rows of one frame and a thread 4 consecutive destination pixels of one of them.  Such a quad lies in the 114 border -- one
+// 4-byte store per channel word -- or computes its taps: [BGR2GRAY] + cv2.resize(h x w -> new_h x new_w) by the arithmetic of cv_pre_kernel,
+// with the coefficients cv_tables_kernel would put into a table computed here, per thread (a batch may hold as many sizes as frames, so
+// there is nothing to cache).  The copy / 2x2-mean / linear decision is per frame, hence uniform in the workgroup.  Source bytes are
+// gathered one by one: frame pointers and row strides of arbitrary sizes have no alignment to rely on.
+constexpr int LB_TR = 4;          // destination rows per workgroup
+
+template <int GRAY>   // 0: the three channels kept; 14 / 15: BGR -> gray
+__global__ void __launch_bounds__(256) cv_letterbox_kernel(const LbEntry* __restrict__ tab, uint8_t* __restrict__ dst, int dh, int dw)
+{
+    constexpr int DC = GRAY != 0 ? 1 : 3;
+    const int groups = (dh + LB_TR - 1) / LB_TR;
+    const int n = blockIdx.x / groups, dy0 = (blockIdx.x - n * groups) * LB_TR;
+    const LbEntry e = tab[n];
+    const int mode = (e.h == e.new_h && e.w == e.new_w) ? 0 : (e.h == 2 * e.new_h && e.w == 2 * e.new_w) ? 1 : 2;
+    const long rs = (long)e.w * 3;
+    const int ymax = e.h - 1, xmax = e.w - 1;
+    const int quads = (dw + 3) >> 2;
+#pragma unroll 1
+    for (int t = threadIdx.x; t < LB_TR * quads; t += 256) {
+        const int k = t / quads, dx0 = (t - k * quads) * 4, dy = dy0 + k;
+        if (dy >= dh) break;
+        uint32_t packed[DC];
+#pragma unroll
+        for (int w = 0; w < DC; ++w) packed[w] = 0x72727272u;      // 114: cv2.copyMakeBorder's value
+        const int iy = dy - e.top;
+        if (iy >= 0 && iy < e.new_h && dx0 + 3 >= e.left && dx0 < e.left + e.new_w) {
+            int y0 = iy, y1 = iy, b0 = 0, b1 = 0;
+            if (mode == 1) { y0 = 2 * iy; y1 = 2 * iy + 1; }
+            if (mode == 2) { const int4 ty = cv_linear_coef(iy, e.h, e.new_h, false); y0 = ty.x; y1 = ty.y; b0 = ty.z; b1 = ty.w; }
+            y0 = min(max(y0, 0), ymax); y1 = min(max(y1, 0), ymax);
+            const uint8_t* const row0 = e.src + y0 * rs;
+            const uint8_t* const row1 = e.src + y1 * rs;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int ix = dx0 + i - e.left;
+                if (dx0 + i >= dw || ix < 0 || ix >= e.new_w) continue;
+                int x0 = ix, x1 = ix, a0 = 0, a1 = 0;
+                if (mode == 1) { x0 = 2 * ix; x1 = 2 * ix + 1; }
+                if (mode == 2) { const int4 tx = cv_linear_coef(ix, e.w, e.new_w, true); x0 = tx.x; x1 = tx.y; a0 = tx.z; a1 = tx.w; }
+                x0 = min(max(x0, 0), xmax); x1 = min(max(x1, 0), xmax);
+#pragma unroll
+                for (int c = 0; c < DC; ++c) {
+                    int v;
+                    if (mode == 0) {
+                        v = cv_px<GRAY>(row0, x0, 3, c);
+                    } else if (mode == 1) {
+                        v = (cv_px<GRAY>(row0, x0, 3, c) + cv_px<GRAY>(row0, x1, 3, c) + cv_px<GRAY>(row1, x0, 3, c) + cv_px<GRAY>(row1, x1, 3, c) + 2) >> 2;
+                    } else {
+                        const int r0 = cv_px<GRAY>(row0, x0, 3, c) * a0 + cv_px<GRAY>(row0, x1, 3, c) * a1;
+                        const int r1 = cv_px<GRAY>(row1, x0, 3, c) * a0 + cv_px<GRAY>(row1, x1, 3, c) * a1;
+                        v = (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2;
+                    }
+                    const int kk = i * DC + c, sh = 8 * (kk & 3);
+                    packed[kk >> 2] = (packed[kk >> 2] & ~(255u << sh)) | ((uint32_t)(v & 255) << sh);
+                }
+            }
+        }
+        uint8_t* o = dst + (((long)n * dh + dy) * dw + dx0) * DC;
+        const int nb = (dw - dx0 < 4 ? dw - dx0 : 4) * DC;
+        if (nb == 4 * DC && ((reinterpret_cast<uintptr_t>(o) & 3) == 0)) {
+#pragma unroll
+            for (int w = 0; w < DC; ++w) reinterpret_cast<uint32_t*>(o)[w] = packed[w];
+        } else {
+#pragma unroll
+            for (int kk = 0; kk < 4 * DC; ++kk)
+                if (kk < nb) o[kk] = (uint8_t)(packed[kk >> 2] >> (8 * (kk & 3)));
+        }
+    }
+}
+
+int launch_cv_letterbox(const LbEntry* d_table, int n, int gray, int dh, int dw, uint8_t* dst, hipStream_t s)
+{
+    static_assert(sizeof(LbEntry) == 40, "YF_LB_TABLE_ENTRY_BYTES");
+    const long blocks = (long)n * ((dh + LB_TR - 1) / LB_TR);
+    if (n <= 0 || dh <= 0 || dw <= 0 || blocks > 0x7fffffffL) return -1;
+    const dim3 grid((unsigned)blocks), wg(256);
+    if (gray == 14) hipLaunchKernelGGL(cv_letterbox_kernel<14>, grid, wg, 0, s, d_table, dst, dh, dw);
+    else if (gray == 15) hipLaunchKernelGGL(cv_letterbox_kernel<15>, grid, wg, 0, s, d_table, dst, dh, dw);
+    else if (gray == 0) hipLaunchKernelGGL(cv_letterbox_kernel<0>, grid, wg, 0, s, d_table, dst, dh, dw);
     else return -1;
     return 0;
 }

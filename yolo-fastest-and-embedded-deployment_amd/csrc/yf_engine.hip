@@ -1251,6 +1251,73 @@ int yf_forward_bgr_u8(yf_handle h, const uint8_t* d_bgr, int N, int src_h, int s
     return forward_via_cv(h, d_bgr, N, src_h, src_w, 3, gray_bits, d_hl, d_hs, ws, ws_bytes, stream);
 }
 
+// yolov5's letterbox(auto=False, scaleFill=False, scaleup=True) geometry in double, Python's round = rint in the default rounding mode
+static void letterbox_geometry(int h, int w, int H, int W, int32_t out[6])
+{
+    const double r = fmin((double)H / (double)h, (double)W / (double)w);
+    const int new_w = (int)rint((double)w * r), new_h = (int)rint((double)h * r);
+    const double dw = (double)(W - new_w) / 2.0, dh = (double)(H - new_h) / 2.0;
+    out[0] = new_h; out[1] = new_w;
+    out[2] = (int)rint(dh - 0.1); out[3] = (int)rint(dh + 0.1);
+    out[4] = (int)rint(dw - 0.1); out[5] = (int)rint(dw + 0.1);
+}
+
+int yf_letterbox_geometry(int src_h, int src_w, int dst_h, int dst_w, int32_t out[6])
+{
+    if (!out || src_h <= 0 || src_w <= 0 || dst_h <= 0 || dst_w <= 0) return fail(YF_E_INVALID, "yf_letterbox_geometry: bad argument");
+    letterbox_geometry(src_h, src_w, dst_h, dst_w, out);
+    return YF_OK;
+}
+
+int yf_cv_letterbox_u8(int device, int N, const void* const* d_frames, const int* heights, const int* widths, int gray_bits, int dst_h, int dst_w,
+                       uint8_t* d_dst, void* d_table, size_t table_bytes, void* h_table_pinned, void* stream)
+{
+    static_assert(sizeof(yf::LbEntry) == YF_LB_TABLE_ENTRY_BYTES, "the kernel's table entry (yf_kernels.h)");
+    const char* who = "yf_cv_letterbox_u8";
+    if (N <= 0 || !d_frames || !heights || !widths || !d_dst || !d_table || !h_table_pinned) return fail(YF_E_INVALID, "%s: bad argument", who);
+    if (gray_bits != 0 && gray_bits != 14 && gray_bits != 15) return fail(YF_E_INVALID, "%s: gray_bits must be 0 (three channels), 14 or 15", who);
+    if (dst_h <= 0 || dst_w <= 0 || dst_h > YF_LB_MAX_SIDE || dst_w > YF_LB_MAX_SIDE) return fail(YF_E_INVALID, "%s: destination %dx%d", who, dst_h, dst_w);
+    if (table_bytes < (size_t)N * YF_LB_TABLE_ENTRY_BYTES)
+        return fail(YF_E_INVALID, "%s: the table holds %zu bytes, %d frames need %zu", who, table_bytes, N, (size_t)N * YF_LB_TABLE_ENTRY_BYTES);
+    for (int i = 0; i < N; ++i) {
+        if (!d_frames[i]) return fail(YF_E_INVALID, "%s: frame %d: null pointer", who, i);
+        if (heights[i] <= 0 || widths[i] <= 0 || heights[i] > YF_LB_MAX_SIDE || widths[i] > YF_LB_MAX_SIDE)
+            return fail(YF_E_INVALID, "%s: frame %d: size %dx%d (1 .. %d)", who, i, heights[i], widths[i], YF_LB_MAX_SIDE);
+    }
+    // every refusal comes before the pinned copy is written: a refused call leaves the previous table as it was
+    int32_t g[6];
+    for (int i = 0; i < N; ++i) {
+        letterbox_geometry(heights[i], widths[i], dst_h, dst_w, g);
+        if (g[0] < 1 || g[1] < 1)
+            return fail(YF_E_INVALID, "%s: frame %d: %dx%d letterboxed into %dx%d is %dx%d (cv2.resize raises on an empty size)", who, i, heights[i],
+                        widths[i], dst_h, dst_w, g[0], g[1]);
+    }
+    yf::LbEntry* const host = static_cast<yf::LbEntry*>(h_table_pinned);
+    for (int i = 0; i < N; ++i) {
+        letterbox_geometry(heights[i], widths[i], dst_h, dst_w, g);
+        host[i] = yf::LbEntry{static_cast<const uint8_t*>(d_frames[i]), heights[i], widths[i], g[0], g[1], g[2], g[3], g[4], g[5]};
+    }
+    HIP_OK(hipSetDevice(device));
+    HIP_OK(hipMemcpyAsync(d_table, host, (size_t)N * sizeof(yf::LbEntry), hipMemcpyHostToDevice, (hipStream_t)stream));
+    if (yf::launch_cv_letterbox(static_cast<const yf::LbEntry*>(d_table), N, gray_bits, dst_h, dst_w, d_dst, (hipStream_t)stream))
+        return fail(YF_E_INVALID, "%s: %d frames of %d rows are more workgroups than one launch takes", who, N, dst_h);
+    HIP_OK(hipGetLastError());
+    return YF_OK;
+}
+
+int yf_scale_boxes(int device, int32_t* d_boxes, long frame_stride, const int32_t* d_counts, long count_stride, int N, int K_max, int net_h,
+                   int net_w, const int32_t* d_frame_hw, void* stream)
+{
+    if (!d_boxes || !d_counts || !d_frame_hw || N <= 0 || K_max <= 0 || net_h <= 0 || net_w <= 0)
+        return fail(YF_E_INVALID, "yf_scale_boxes: bad argument");
+    if (frame_stride < 4L * K_max || count_stride < 1) return fail(YF_E_INVALID, "yf_scale_boxes: strides %ld / %ld for K_max %d", frame_stride, count_stride, K_max);
+    if (((long)N * K_max + 255) / 256 > 0x7fffffffL) return fail(YF_E_INVALID, "yf_scale_boxes: too many box slots for one launch");
+    HIP_OK(hipSetDevice(device));
+    yf::launch_scale_boxes(d_boxes, frame_stride, d_counts, count_stride, N, K_max, net_h, net_w, d_frame_hw, (hipStream_t)stream);
+    HIP_OK(hipGetLastError());
+    return YF_OK;
+}
+
 int yf_nms_sorted(yf_handle h, const int32_t* d_boxes, int n, double nms_thres, int32_t* d_sup, void* stream)
 {
     if (!h || !d_boxes || !d_sup || n < 0) return fail(YF_E_INVALID, "yf_nms_sorted: bad argument");

@@ -206,6 +206,16 @@ struct CvArgs {
 int launch_cv_pre(const CvArgs& a, hipStream_t s);
 // cv::resize's xofs / ialpha and yofs / ibeta tables for one source size, built ON THE DEVICE (stream-ordered, no allocation, capturable)
 void launch_cv_tables(int src_h, int src_w, int dst_h, int dst_w, int4* xtab, int4* ytab, hipStream_t s);
+// yolov5's letterbox for frames of any sizes in one launch (yf_cv_letterbox_u8): one table entry per frame, YF_LB_TABLE_ENTRY_BYTES
+struct LbEntry {
+    const uint8_t* src;                          // u8 [h, w, 3] BGR, contiguous, any alignment
+    int h, w;
+    int new_h, new_w, top, bottom, left, right;  // yf_letterbox_geometry
+};
+int launch_cv_letterbox(const LbEntry* d_table, int n, int gray, int dh, int dw, uint8_t* dst, hipStream_t s);   // gray 0 (3 channels) | 14 | 15
+// yolov5's scale_boxes + round, in place (yf_scale_boxes)
+void launch_scale_boxes(int32_t* boxes, long frame_stride, const int32_t* counts, long count_stride, int n, int kmax, int net_h, int net_w,
+                        const int32_t* frame_hw, hipStream_t s);
 void launch_preprocess(const uint8_t* in, float* out, long N, int H, int W, int down2, hipStream_t s, int channels = 1);   // channels 3: HWC BGR in, NCHW RGB planes out
 
 struct FbArgs {

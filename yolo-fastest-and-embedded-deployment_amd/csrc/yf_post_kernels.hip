@@ -1017,4 +1017,38 @@ int launch_post(const PostArgs& a, int N, hipStream_t s)
     return 0;
 }
 
+// yolov5's scale_boxes(img1_shape = (net_h, net_w), boxes, img0_shape = (h, w)) with ratio_pad=None, then .round(), in place on the int
+// boxes the NMS left in net coordinates (include/yolo_fastest_hip.h states the rule).  IEEE double throughout, -ffp-contract=off: the
+// device evaluates what the Python expression does.  One thread per box slot; slots past the frame's count are not touched.
+__global__ void __launch_bounds__(256) scale_boxes_kernel(int32_t* __restrict__ boxes, long frame_stride, const int32_t* __restrict__ counts,
+                                                          long count_stride, int n, int kmax, double net_h, double net_w,
+                                                          const int32_t* __restrict__ frame_hw)
+{
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (long)n * kmax) return;
+    const int f = (int)(t / kmax), k = (int)(t - (long)f * kmax);
+    const int count = counts[f * count_stride];
+    if (k >= count) return;                      // (count -2, 0: nothing; count > kmax: the kmax stored ones)
+    const int hi = frame_hw[2 * f], wi = frame_hw[2 * f + 1];
+    if (hi <= 0 || wi <= 0) return;
+    const double h = (double)hi, w = (double)wi;
+    const double gain = fmin(net_h / h, net_w / w);
+    const double pad_w = (net_w - w * gain) / 2.0, pad_h = (net_h - h * gain) / 2.0;
+    int32_t* const b = boxes + f * frame_stride + 4 * k;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const double pad = (c & 1) ? pad_h : pad_w, lim = (c & 1) ? h : w;
+        const double v = ((double)b[c] - pad) / gain;
+        b[c] = (int32_t)rint(fmin(fmax(v, 0.0), lim));
+    }
+}
+
+void launch_scale_boxes(int32_t* boxes, long frame_stride, const int32_t* counts, long count_stride, int n, int kmax, int net_h, int net_w,
+                        const int32_t* frame_hw, hipStream_t s)
+{
+    const long threads = (long)n * kmax;
+    hipLaunchKernelGGL(scale_boxes_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, boxes, frame_stride, counts, count_stride, n,
+                       kmax, (double)net_h, (double)net_w, frame_hw);
+}
+
 }  // namespace yf

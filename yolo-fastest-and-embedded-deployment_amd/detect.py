@@ -15,6 +15,10 @@ Result writer: `result_<name>` images with the reference's bo
 reference's general.py:56-67 without cv2) and the reference's log lines; `self.last_labels` keeps the label strings per image.
 `write="device"` (opt-in) draws and JPEG-encodes the result images on the device instead (plot.draw_boxes_device, jpeg.encode_batch): the
 same files byte for byte, the frames never leave the GPU, and a batch is encoded while the host prepares the next one.
+`letterbox=True` (opt-in) follows yolov5 where the reference squashes: every frame is letterboxed to the net's size (aspect ratio kept,
+border 114; model.letterbox_u8: one launch per batch whatever the frames' sizes, where the default path pre-processes a batch of mixed
+sizes frame by frame) and every box goes back to ITS frame's coordinates (post_process.scale_boxes), where the default path scales all
+boxes to the configured `origin_img_shape`.
 """
 import ctypes
 import os
@@ -49,11 +53,12 @@ def preprocess_u8(model, u8, input_shape):
 
 
 class Detect_YOLO():
-    def __init__(self, device, model_path, config_params, logger, decode="host", progressive=False, write="host"):
+    def __init__(self, device, model_path, config_params, logger, decode="host", progressive=False, write="host", letterbox=False):
         jpeg.check_decode(decode, progressive)
         if write not in ("host", "device"):
             raise ValueError('write must be "host" or "device"')
         self.write = write
+        self.letterbox = bool(letterbox)             # yolov5's letterbox + scale_boxes; `origin_img_shape` is not read in this mode
         self._label_masks = {}                       # write="device": plot.label_mask per (label, thickness), rendered once
         self._write_stream = None
         self.decode = decode
@@ -172,12 +177,17 @@ class Detect_YOLO():
     def detect_bgr_u8(self, bgr, kmax=64, gray_bits=None):
         """bgr: uint8 GPU tensor [N,h,w,3] as cv2.imread returns frames, any size.  The whole of detect.py:108-182 on the device; per-frame
         lists in the coordinates of `origin_img_shape` (after __adjust_coord, :131-139)."""
+        if self.letterbox:      # `bgr` may be a list of [h,w,3] frames of any sizes; per-frame lists in each frame's own coordinates
+            pred, hw = self.model.forward_letterbox_u8(bgr, self.input_shape, gray_bits=gray_bits)
+            return self.post_process.detect(pred, kmax=kmax, frame_hw=hw)
         pred = self.model.forward_bgr_u8(bgr, self.input_shape, gray_bits=gray_bits)
         return self.post_process.detect(pred, kmax=kmax, origin_shape=self._origin)
 
     def detect_u8(self, u8, kmax=64):
         """u8: uint8 GPU tensor [N,h,w] in the ORIGINAL image geometry (any size: cv2.resize's arithmetic brings it to the net's). Returns
         per-frame lists in original coordinates (after __adjust_coord, detect.py:181-182)."""
+        if self.letterbox:
+            raise ValueError("detect_u8 takes one-channel frames in the original geometry; letterbox=True works on BGR frames: detect_bgr_u8")
         pred = self.model.forward_u8(u8, self.input_shape)  # pre-process in front of / fused into the first kernel's loads
         return self.post_process.detect(pred, kmax=kmax, origin_shape=self._origin)
 
@@ -190,7 +200,7 @@ class Detect_YOLO():
         img_list = sorted(os.listdir(data_path))   # the reference iterates os.listdir order; its logs show it sorted
         num = len(img_list)
         self.last_labels = {}
-        origin = self._origin
+        origin = None if self.letterbox else self._origin
         batches = [img_list[b0:b0 + batch_size] for b0 in range(0, num, batch_size)]
         pipelined = len(batches) > 1 and in_flight > 1
         state = {"avg": 0.0}
@@ -215,13 +225,17 @@ class Detect_YOLO():
                                     total_time))
 
         def load(names):
-            """-> (the batch's frames and originals as `_load` returns them, the net's input)."""
+            """-> (the batch's frames and originals as `_load` returns them, the net's input, with letterbox=True the frames' (h, w) on
+            the device: else None)."""
             bgrs, oris = self._load([os.path.join(data_path, n) for n in names])
+            if self.letterbox:      # one launch, mixed sizes or not; in flight the letterboxed u8 frames are what the batch's stream receives
+                u8, hw = self.model.letterbox_u8(bgrs, self.input_shape)
+                return bgrs, oris, (u8 if pipelined else preprocess_u8(self.model, u8, self.input_shape)), hw
             if not torch.is_tensor(bgrs):      # frames of different sizes: the resize brings them to one
                 x = torch.cat([self._pre_process(b[None]) for b in bgrs])
             else:      # cv2.imread-shaped frames of one size; in flight, cvtColor + resize + (v - 128) / 255 run inside the batch's own stream
                 x = bgrs if pipelined else self._pre_process(bgrs)
-            return bgrs, oris, x
+            return bgrs, oris, x, None
 
         if pipelined:
             from .pipeline import BatchPipeline
@@ -230,17 +244,19 @@ class Detect_YOLO():
             pending = []
 
             def finish(item):
-                names, bgrs, oris, ticket, ev = item
+                names, bgrs, oris, hw, ticket, ev = item
                 raw = ticket.synchronize()
                 most = int(raw["counts"].max().item()) if raw["counts"].numel() else 0
                 if most > raw["boxes"].shape[1]:      # more survivors than the first attempt reserved: once more with room for all (post.detect does the same)
-                    raw = self.post_process.detect_raw((raw["head_large"], raw["head_small"]), kmax=most, origin_shape=origin)
+                    raw = self.post_process.detect_raw((raw["head_large"], raw["head_small"]), kmax=most, origin_shape=origin, frame_hw=hw)
+                elif hw is not None:                  # the ticket's boxes are in net coordinates: back to each frame's own
+                    self.post_process.scale_boxes(raw, hw)
                 results = self.post_process.to_lists(raw)
                 report(names, bgrs, oris, results, ev[0].elapsed_time(ev[1]) / len(names), ev[1].elapsed_time(ev[2]) / len(names))
 
             try:
                 for names in batches:
-                    bgrs, oris, x = load(names)
+                    bgrs, oris, x, hw = load(names)
                     ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
                     ev[0].record()
 
@@ -248,7 +264,7 @@ class Detect_YOLO():
                         ev[1].record()
                         return pred
                     ticket = pipe.submit(x, mid=mid, then=lambda out, ev=ev: ev[2].record())
-                    pending.append((names, bgrs, oris, ticket, ev))
+                    pending.append((names, bgrs, oris, hw, ticket, ev))
                     if len(pending) >= in_flight:
                         finish(pending.pop(0))
                 while pending:
@@ -262,7 +278,7 @@ class Detect_YOLO():
                     del writes[:]
         else:
             for names in batches:
-                bgrs, oris, x = load(names)
+                bgrs, oris, x, hw = load(names)
                 torch.cuda.synchronize(self.device)
                 start_time = time.time()
                 with torch.no_grad():
@@ -270,7 +286,7 @@ class Detect_YOLO():
                 torch.cuda.synchronize(self.device)
                 time_mark = time.time()
                 infer_time = (time_mark - start_time) * 1000 / len(names)
-                results = self.post_process.detect(pred, origin_shape=origin)
+                results = self.post_process.detect(pred, origin_shape=origin, frame_hw=hw)
                 post_process_time = (time.time() - time_mark) * 1000 / len(names)
                 report(names, bgrs, oris, results, infer_time, post_process_time)
         self.logger.info("detect avg_time: %.2fms" % (state["avg"] / max(num, 1)))

@@ -309,6 +309,64 @@ class YoloFastest(nn.Module):
                                              ctypes.c_void_p(stream)))
         return dst
 
+    def letterbox_u8(self, frames, input_shape, gray_bits=None):
+        """yolov5's letterbox(auto=False, scaleup=True) in place of detect.py:115-116's squashing resize (yf_cv_letterbox_u8: the rule is
+        in include/yolo_fastest_hip.h), ONE launch whatever the frames' sizes.  frames: a uint8 GPU tensor [N,h,w,3] (BGR) or a list of
+        [h,w,3] tensors of any sizes -> (the uint8 frames [N,H,W] -- [N,H,W,3] for a 3-channel net -- that `(img - 128.0) / 255.0` is
+        applied to next, an int32 GPU tensor [N,2] of the frames' (h, w): what YOLO_post_process.scale_boxes takes)."""
+        from .training import _PinnedTable
+        if self.input_channel not in (1, 3):
+            raise ValueError("BGR frames feed 1- and 3-channel nets (detect.py:110-113), not %d" % self.input_channel)
+        bad = ValueError("expected uint8 GPU frames [h,w,3] (cv2.imread's BGR) on one device: a tensor [N,h,w,3] or a list")
+        if torch.is_tensor(frames):                     # a stack: one check, the frames' addresses by arithmetic
+            frames = frames[None] if frames.dim() == 3 else frames
+            if not frames.is_cuda or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or frames.shape[0] < 1:
+                raise bad
+            keep = frames = frames.contiguous()
+            N, dev, step = frames.shape[0], frames.device, frames.shape[1] * frames.shape[2] * 3
+            ptrs, hs, ws = range(frames.data_ptr(), frames.data_ptr() + N * step, max(step, 1)), [frames.shape[1]] * N, [frames.shape[2]] * N
+        else:
+            frames = list(frames)
+            if not frames or not torch.is_tensor(frames[0]):
+                raise bad
+            N, dev = len(frames), frames[0].device
+            if dev.type != "cuda":
+                raise bad
+            keep, ptrs, hs, ws = [], [], [], []
+            for f in frames:                            # one pass: this loop is most of the call's host time for a few hundred frames
+                if not torch.is_tensor(f):
+                    raise bad
+                sh = f.shape
+                if f.dtype is not torch.uint8 or len(sh) != 3 or sh[2] != 3 or f.device != dev:
+                    raise bad
+                if not f.is_contiguous():
+                    f = f.contiguous()
+                keep.append(f); ptrs.append(f.data_ptr()); hs.append(sh[0]); ws.append(sh[1])
+        H, W = int(input_shape[0]), int(input_shape[1])
+        gray = 0 if self.input_channel == 3 else int(self.gray_bits if gray_bits is None else gray_bits)
+        dst = torch.empty((N, H, W) if self.input_channel == 1 else (N, H, W, 3), dtype=torch.uint8, device=dev)
+        tables = self.__dict__.setdefault("_lb_tables", {})
+        table = tables.get(dev)
+        if table is not None and table.event is not None:
+            table.event.synchronize()                   # every call uploads: the previous upload must have left the pinned copy
+        if table is None or table.args[1] < _lib.YF_LB_TABLE_ENTRY_BYTES * N:
+            table = tables[dev] = _PinnedTable(_lib.YF_LB_TABLE_ENTRY_BYTES * max(N, 256), dev)
+        stream = torch.cuda.current_stream(dev)
+        _lib.check(_lib.lib().yf_cv_letterbox_u8(dev.index, N, (ctypes.c_void_p * N)(*ptrs), (ctypes.c_int * N)(*hs), (ctypes.c_int * N)(*ws), gray,
+                                                 H, W, dst.data_ptr(), *table.args, ctypes.c_void_p(stream.cuda_stream)))
+        # (h, w) sit at int32 2, 3 of every table entry: a copy of them, on the stream behind the upload and in front of the event that
+        # lets the next call rewrite the table
+        hw = table.dev.view(torch.int32).view(-1, _lib.YF_LB_TABLE_ENTRY_BYTES // 4)[:N, 2:4].clone()
+        table.uploaded(N, stream)
+        del keep                                        # (the frames, and any contiguous copies, lived until the launch was queued)
+        return dst, hw
+
+    def forward_letterbox_u8(self, frames, input_shape, gray_bits=None, slot=0):
+        """model(letterbox(frame)): letterbox_u8 + the fused (v - 128) / 255 entry (the letterboxed frames have the net's size, so
+        forward_u8 takes them without its extra pass) -> ((head_large, head_small), the frames' (h, w) as letterbox_u8 returns them)."""
+        u8, hw = self.letterbox_u8(frames, input_shape, gray_bits=gray_bits)
+        return self.forward_u8(u8, input_shape, slot=slot), hw
+
     def forward_u8(self, u8, input_shape, slot=0):
         """model(preprocess(u8)) with the pre-process in front of the first kernel: u8 GPU tensor [N,h,w] of ANY size (the net's input size or
         exactly 2x: fused into the first kernel's loads; otherwise cv2.resize's INTER_LINEAR runs as one extra pass; input_channel 3:

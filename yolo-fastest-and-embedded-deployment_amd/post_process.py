@@ -62,10 +62,39 @@ class YOLO_post_process:
                     scores=rec[:, 1 + 4 * kmax:1 + 6 * kmax].view(torch.float32).view(n, kmax, 2),
                     cls=rec[:, 1 + 6 * kmax:1 + 7 * kmax], src=rec[:, 1 + 7 * kmax:1 + 8 * kmax], records=rec)
 
-    def detect_raw(self, pred, kmax=64, nms_thres=None, origin_shape=None, slot=0, packed=False):
+    def scale_boxes(self, raw, frame_hw):
+        """yolov5's scale_boxes(net shape, boxes, frame shape).round() in place on a detect_raw result whose boxes are in NET coordinates
+        (origin_shape=None): every frame's boxes go back to that frame's own (h, w) -- frame_hw int32 GPU tensor [N,2], as
+        model.letterbox_u8 returns it -- undoing the letterbox (yf_scale_boxes; the rule is in include/yolo_fastest_hip.h).  One launch
+        on the current stream, for the separate tensors and for the packed record block alike.  Returns raw."""
+        boxes, counts = raw["boxes"], raw["counts"]
+        N, kmax = boxes.shape[0], boxes.shape[1]
+        if not torch.is_tensor(frame_hw) or frame_hw.dtype != torch.int32 or tuple(frame_hw.shape) != (N, 2) or frame_hw.device != boxes.device:
+            raise ValueError("frame_hw must be an int32 tensor [%d, 2] on the boxes' device" % N)
+        if N == 0 or kmax == 0:
+            return raw
+        rec = raw.get("records")
+        if rec is not None:
+            b_ptr, c_ptr, fs, cs = rec.data_ptr() + 4, rec.data_ptr(), rec.stride(0), rec.stride(0)
+        else:
+            if not boxes.is_contiguous() or not counts.is_contiguous():
+                raise ValueError("boxes and counts must be contiguous")
+            b_ptr, c_ptr, fs, cs = boxes.data_ptr(), counts.data_ptr(), 4 * kmax, 1
+        dev = boxes.device
+        _lib.check(_lib.lib().yf_scale_boxes(dev.index, b_ptr, fs, c_ptr, cs, N, kmax, int(self.input_shape[0]), int(self.input_shape[1]),
+                                             frame_hw.contiguous().data_ptr(), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        return raw
+
+    def detect_raw(self, pred, kmax=64, nms_thres=None, origin_shape=None, slot=0, packed=False, frame_hw=None):
         """Batched. Returns dict of GPU tensors: boxes [N,kmax,4] i32, scores [N,kmax,2] f32, cls, src [N,kmax] i32,
         counts [N] i32 (see include/yolo_fastest_hip.h for the conventions).  packed=True: the kernel writes ONE record block
-        (`records`, int32 [N, 1 + 8 kmax]) and the five tensors are views of it -- what dist.all_gather_detections sends as is."""
+        (`records`, int32 [N, 1 + 8 kmax]) and the five tensors are views of it -- what dist.all_gather_detections sends as is.
+        frame_hw (opt-in, letterboxed input: model.letterbox_u8): the NMS runs in net coordinates and `scale_boxes` follows on the
+        same stream; origin_shape must then be None."""
+        if frame_hw is not None:
+            if origin_shape is not None:
+                raise ValueError("frame_hw (every frame's own shape) and origin_shape (one configured shape) exclude each other")
+            return self.scale_boxes(self.detect_raw(pred, kmax=kmax, nms_thres=nms_thres, slot=slot, packed=packed), frame_hw)
         hl, hs = pred[0].contiguous(), pred[1].contiguous()
         e = self._engine(pred, slot)
         N, dev = hl.shape[0], hl.device
@@ -161,14 +190,14 @@ class YOLO_post_process:
             frames.append(L)
         return frames
 
-    def detect(self, pred, kmax=64, origin_shape=None, with_src=False):
+    def detect(self, pred, kmax=64, origin_shape=None, with_src=False, frame_hw=None):
         """All frames: [[x1,y1,x2,y2,conf,cls_score,cls], ...] per frame, class-major like detect.py:162-169.  kmax is the capacity the
         first attempt reserves per frame; a frame with more survivors (the count is always the true number) makes this run the
-        post-process once more with room for all of them -- the reference's lists have no capacity."""
-        raw = self.detect_raw(pred, kmax=kmax, origin_shape=origin_shape)
+        post-process once more with room for all of them -- the reference's lists have no capacity.  frame_hw: as in detect_raw."""
+        raw = self.detect_raw(pred, kmax=kmax, origin_shape=origin_shape, frame_hw=frame_hw)
         most = int(raw["counts"].max().item()) if raw["counts"].numel() else 0
         if most > kmax:
-            raw = self.detect_raw(pred, kmax=most, origin_shape=origin_shape)
+            raw = self.detect_raw(pred, kmax=most, origin_shape=origin_shape, frame_hw=frame_hw)
         return self.to_lists(raw, with_src=with_src)
 
     # -- reference-named methods ------------------------------------------------------------------
