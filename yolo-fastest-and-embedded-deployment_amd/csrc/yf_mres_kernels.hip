@@ -137,15 +137,46 @@ __device__ __forceinline__ void mres_out_px(int mo, int r, int& oy, int& ox)
     }
 }
 
+// The part [lo, hi) of one axis of a tile's region (R rows or columns, the first one at input coordinate o0 S - 1) that lies inside the
+// image (n rows or columns).
+__host__ __device__ inline void mres_span(int o0, int S, int R, int n, int& lo, int& hi)
+{
+    const int first = o0 * S - 1;
+    lo = first < 0 ? -first : 0;
+    hi = n - first < R ? n - first : R;
+}
+// The most region pixels any tile of an H x W input has inside the image (launcher: which expansion form fits)
+static int mres_max_inimage(int H, int W, int S, int TH, int TW)
+{
+    const int RH = (TH - 1) * S + 3, RW = (TW - 1) * S + 3;
+    int most = 0;
+    for (int ty = 0; ty * TH < H / S; ++ty)
+        for (int tx = 0; tx * TW < W / S; ++tx) {
+            int y0, y1, x0, x1;
+            mres_span(ty * TH, S, RH, H, y0, y1);
+            mres_span(tx * TW, S, RW, W, x0, x1);
+            if ((y1 - y0) * (x1 - x0) > most) most = (y1 - y0) * (x1 - x0);
+        }
+    return most;
+}
+
 // S = 2: the stride-2 triples (pw-expand -> dw3x3 stride 2 -> pw-project, no residual): a.H / a.W are the INPUT dims, the tile
 // is TH x TW OUTPUT pixels and the region (TH - 1) S + 3 rows.
-template <int CIN, int CEXP, int COUT, bool RES, int S, int TH, int TW, int NWAVE, typename T>
+// XS > 0: IN-IMAGE expansion.  Region pixels outside the image are the depthwise conv's zero padding: their E records are zeroed once and
+// the expansion runs over the tile's in-image rectangle only, rows [ry0, ry1) x columns [rx0, rx1) of the region, as (nin + 15) / 16
+// M-tiles of 16 rectangle pixels in row-major order, XS of them per wave (the launcher guarantees nin <= XS NWAVE 16).  A corner tile of
+// the 16x20 tiling has 17 x 21 = 357 in-image pixels = 23 M-tiles against the region's 25: no wave owns a fourth tile, and every tile of
+// a 320x256 frame is a corner.  Each in-image pixel sees the MFMAs it saw, in the same order, from the same operands -- only the wave and
+// slot that run them differ -- so the result is the same bits.  X staging, the E layout and everything after the expansion are unchanged.
+// XS == 0: the expansion runs over the whole region and clamps what lies outside the image to zero (grids with interior 16x20 tiles).
+template <int CIN, int CEXP, int COUT, bool RES, int S, int TH, int TW, int NWAVE, typename T, int XS = 0>
 __global__ void __launch_bounds__(NWAVE * 64) mres_kernel(MresArgs a)
 {
     constexpr int RH = (TH - 1) * S + 3, RW = (TW - 1) * S + 3, NRP = RH * RW;
     constexpr int MTR = (NRP + 15) / 16, MTO = (TH * TW) / 16;
-    constexpr int MTRW = (MTR + NWAVE - 1) / NWAVE, MTOW = (MTO + NWAVE - 1) / NWAVE;
-    constexpr bool EVEN_R = MTR % NWAVE == 0, EVEN_O = MTO % NWAVE == 0;  // every wave owns the same number of tiles: no branches
+    constexpr bool INIMG = XS > 0;
+    constexpr int MTRW = INIMG ? XS : (MTR + NWAVE - 1) / NWAVE, MTOW = (MTO + NWAVE - 1) / NWAVE;
+    constexpr bool EVEN_R = !INIMG && MTR % NWAVE == 0, EVEN_O = MTO % NWAVE == 0;  // every wave owns the same number of tiles: no branches
     constexpr bool WEXP = mres_writes_expansion(CIN, CEXP, COUT, S);       // conv4_2 + conv4_3 + conv5_1: conv4_2 is a skip tensor
     constexpr int XP = CIN + 4;                           // X row pitch: conflict-free b128/b64 fragment reads
     constexpr int EPL = mres_epl(MTR, S);   // pixels per 4-channel plane
@@ -160,6 +191,7 @@ __global__ void __launch_bounds__(NWAVE * 64) mres_kernel(MresArgs a)
     static_assert(!RES || (CIN == COUT && S == 1), "residual needs same shape");
     static_assert(CHUNK == mres_chunk_floats(CIN, COUT, wmode_of<T>()), "pack layout");
     static_assert(MTRW <= 32, "in-image mask bits");
+    static_assert(MTRW * NWAVE * 16 * ((TW - 1) * S + 3) < (1 << 20), "in-image form: k / rwi by multiplication");
     extern __shared__ __attribute__((aligned(16))) float mres_smem[];
     float* X = mres_smem;                 // [MTR*16][XP]
     float* E = mres_smem + MTR * 16 * XP; // [4][EPL][4]
@@ -174,16 +206,37 @@ __global__ void __launch_bounds__(NWAVE * 64) mres_kernel(MresArgs a)
     const int lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
 
     mres_stage<CIN, S, RW, NRP, MTR, XP, WFLOATS, NWAVE * 64, T>(a, n, oy0, ox0, X, WL);
+    // in-image form: the tile's in-image rectangle (wave-uniform) and the zero padding around it, which no expansion writes.  The WHOLE
+    // of E is cleared, not only the records outside the image: three to four ds_write_b128 per thread with no index arithmetic, once per
+    // workgroup and in front of the barrier that is there anyway, against a division by RW and a predicate per record.  (Part of every
+    // measured figure of this form.)
+    int ry0 = 0, ry1 = RH, rx0 = 0, rx1 = RW;
+    if constexpr (INIMG) { mres_span(oy0, S, RH, a.H, ry0, ry1); mres_span(ox0, S, RW, a.W, rx0, rx1); }
+    const int rwi = rx1 - rx0, nin = (ry1 - ry0) * rwi, nexp = (nin + 15) >> 4;
+    const unsigned rwi_rcp = ((1u << 20) + rwi - 1) / rwi;   // k / rwi == k * rwi_rcp >> 20 for every k < 2^20 / rwi
+    if constexpr (INIMG) {
+        if (nin < NRP)
+            for (int i = threadIdx.x; i < 4 * EPL; i += NWAVE * 64) reinterpret_cast<float4*>(E)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
     __syncthreads();
 
     // ---- expansion A fragments (constant over chunks) and the in-image mask of this lane's 4 C rows ----
     float a1[MTRW][KS1];
     unsigned inmask = 0;
     int eoff[MTRW];
+    int erec[INIMG ? MTRW : 1];   // in-image form: the E record (16 bytes) of this lane's pixel of slot i
 #pragma unroll
     for (int i = 0; i < MTRW; ++i) {
         const int mt = wave + i * NWAVE;
-        const int row = (mt < MTR ? mt : 0) * 16 + r;
+        int row = (mt < MTR ? mt : 0) * 16 + r, ry_i = 0, rx_i = 0;
+        if constexpr (INIMG) {
+            // rectangle pixel k = mt*16 + r; the lanes past the rectangle's end repeat its last pixel: the same value to the same record
+            const int k = min(mt * 16 + r, nin - 1);
+            const int ky = (int)((unsigned)k * rwi_rcp >> 20);
+            ry_i = ry0 + ky; rx_i = rx0 + k - ky * rwi;
+            row = ry_i * RW + rx_i;
+            erec[i] = q * EPL + row;
+        }
 #pragma unroll
         for (int kb = 0; kb < NB1; ++kb) {
             const float4 t = *reinterpret_cast<const float4*>(&X[row * XP + kb * 16 + 4 * q]);
@@ -193,7 +246,10 @@ __global__ void __launch_bounds__(NWAVE * 64) mres_kernel(MresArgs a)
             const float2 t = *reinterpret_cast<const float2*>(&X[row * XP + NB1 * 16 + 2 * q]);
             a1[i][NB1 * 4 + 0] = t.x; a1[i][NB1 * 4 + 1] = t.y;
         }
-        {   // this lane's pixel of the expansion result (see the expand step): region pixel mt*16 + r
+        if constexpr (INIMG) {
+            // expanded-tensor writeback (a.out_exp): the rule below on the rectangle's pixels, each written by one lane
+            eoff[i] = mt * 16 + r < nin && ry_i > 0 && rx_i > 0 ? ((oy0 * S - 1 + ry_i) * a.W + ox0 * S - 1 + rx_i) * CEXP + 4 * q : -1;
+        } else {   // this lane's pixel of the expansion result (see the expand step): region pixel mt*16 + r
             const int rp = mt * 16 + r;
             const int ry = rp / RW, rx = rp - ry * RW;
             const int iy = oy0 * S - 1 + ry, ix = ox0 * S - 1 + rx;
@@ -224,7 +280,13 @@ __global__ void __launch_bounds__(NWAVE * 64) mres_kernel(MresArgs a)
         int oy, ox;
         mres_out_px<TH, TW, RW, S>(mo < MTO ? mo : 0, r, oy, ox);
         rp0[i] = (oy * S + 1) * RW + ox * S + 1;
-    }
+    }    // in-image form: the ReLU's upper limit is +inf for every pixel written.  It sits in an SGPR that the compiler cannot see through:
+    // with the constant in sight it replaces each v_med3_f32 by TWO v_max_f32 (a canonicalising one first), 24 VALU instructions per
+    // chunk for three tiles instead of 12 (tools/isa_blocks.py on the -S file shows which of the two a compiler emits; the result is
+    // the same either way).  relu_bits' v_max_i32 in its place has the same instruction count and registers when compiled, and the
+    // same value for every input but a NaN; it has not been run on the GPU, so the measured form stays.
+    float lim_in = __builtin_inff();
+    if constexpr (INIMG) asm volatile("" : "+s"(lim_in));
 
 #pragma unroll 1
     for (int c = 0; c < NCH; ++c) {
@@ -267,7 +329,12 @@ __global__ void __launch_bounds__(NWAVE * 64) mres_kernel(MresArgs a)
 #pragma unroll
         for (int i = 0; i < MTRW; ++i) {
             const int mt = wave + i * NWAVE;
-            if (EVEN_R || i < MTRW - 1 || mt < MTR) {   // only a wave's LAST tile can be missing: the others share one basic block
+            // only a wave's LAST tile runs under a guard: the others share one basic block, where the compiler interleaves their MFMA chains.
+            // In-image form: on a tile with few in-image pixels (a partial last tile row or column) the earlier slots of some waves have no
+            // M-tile either.  They are NOT skipped -- a guard per slot would split the block on every tile to spare the rare small one --:
+            // their lanes were clamped to the rectangle's last pixel in the set-up, so they recompute that pixel and store the value its
+            // owner stores to the same E record (and never to out_exp: eoff is -1).  Identical values, a barrier behind: redundant, not a race.
+            if (EVEN_R || i < MTRW - 1 || mt < (INIMG ? nexp : MTR)) {
                 f32x4 cf = f32x4{b1.x, b1.y, b1.z, b1.w};   // the bias rides in as the MFMA's C operand
                 if constexpr (X3) {   // small terms first, then hi * hi
 #pragma unroll
@@ -290,10 +357,12 @@ __global__ void __launch_bounds__(NWAVE * 64) mres_kernel(MresArgs a)
                 }
                 // weights as the A operand: the lane holds channels 4q .. 4q+3 of region pixel mt*16 + r = one E record
                 // ReLU and the zero outside the image in ONE instruction: median(x, 0, lim) with lim = +inf inside, 0 outside
-                const float lim = (inmask >> i) & 1 ? __builtin_inff() : 0.f;
+                // (in-image form: every pixel written is inside)
+                const float lim = INIMG ? lim_in : (inmask >> i) & 1 ? __builtin_inff() : 0.f;
                 const float4 ev = make_float4(__builtin_amdgcn_fmed3f(cf[0], 0.f, lim), __builtin_amdgcn_fmed3f(cf[1], 0.f, lim),
                                               __builtin_amdgcn_fmed3f(cf[2], 0.f, lim), __builtin_amdgcn_fmed3f(cf[3], 0.f, lim));
-                *reinterpret_cast<float4*>(E + (q * EPL + mt * 16 + r) * 4) = ev;
+                if constexpr (INIMG) reinterpret_cast<float4*>(E)[erec[i]] = ev;
+                else *reinterpret_cast<float4*>(E + (q * EPL + mt * 16 + r) * 4) = ev;
                 if constexpr (WEXP)
                     if (eoff[i] >= 0 && c * 16 + 4 * q < CEXP)
                         st4<T>(reinterpret_cast<T*>(a.out_exp) + (long)n * a.H * a.W * CEXP + eoff[i] + c * 16, ev);
@@ -777,8 +846,8 @@ static int launch_mres_pc_t(MresArgs a, int N, hipStream_t s)
     return 0;
 }
 
-template <int CIN, int CEXP, int COUT, bool RES, int S, int TH, int TW, int NWAVE, typename T>
-static int launch_mres_t(MresArgs a, int N, hipStream_t s)
+template <int CIN, int CEXP, int COUT, bool RES, int S, int TH, int TW, int NWAVE, typename T, int XS>
+static int launch_mres_x(MresArgs a, int N, hipStream_t s)
 {
     a.tiles_y = (a.H / S + TH - 1) / TH;
     a.tiles_x = (a.W / S + TW - 1) / TW;
@@ -792,14 +861,33 @@ static int launch_mres_t(MresArgs a, int N, hipStream_t s)
     const int dev = current_device();
     if (dev < 0) return -2;
     if (lds > 64 * 1024 && !attr_done[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(mres_kernel<CIN, CEXP, COUT, RES, S, TH, TW, NWAVE, T>),
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(mres_kernel<CIN, CEXP, COUT, RES, S, TH, TW, NWAVE, T, XS>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
             return -2;
         attr_done[dev] = true;
     }
-    hipLaunchKernelGGL((mres_kernel<CIN, CEXP, COUT, RES, S, TH, TW, NWAVE, T>), dim3((unsigned)(N * a.tiles_y * a.tiles_x)),
+    hipLaunchKernelGGL((mres_kernel<CIN, CEXP, COUT, RES, S, TH, TW, NWAVE, T, XS>), dim3((unsigned)(N * a.tiles_y * a.tiles_x)),
                        dim3(NWAVE * 64), lds, s, a);
     return 0;
+}
+
+// Which expansion form runs (mres_kernel, XS).  Where a tile that touches the image's border needs fewer expansion slots per wave than
+// an interior one -- the 16x20 tiles: 24 M-tiles at most against 25, three per wave against four -- frames without interior tiles
+// (320x256: 2x2 tiles, all corners) run the in-image form at that slot count and the others keep the full-region form; every other
+// tiling runs the in-image form at the full slot count, which holds any tile.  (Measured: profiles/mres_inimage_ab.txt.)
+template <int CIN, int CEXP, int COUT, bool RES, int S, int TH, int TW, int NWAVE, typename T>
+static int launch_mres_t(const MresArgs& a, int N, hipStream_t s)
+{
+    constexpr int RH = (TH - 1) * S + 3, RW = (TW - 1) * S + 3;
+    constexpr int XFULL = ((RH * RW + 15) / 16 + NWAVE - 1) / NWAVE;
+    constexpr int XEDGE = (((RH - 1) * RW > RH * (RW - 1) ? (RH - 1) * RW : RH * (RW - 1)) + 15) / 16;
+    constexpr int XBORDER = (XEDGE + NWAVE - 1) / NWAVE;
+    if constexpr (XBORDER < XFULL) {
+        if (mres_max_inimage(a.H, a.W, S, TH, TW) <= XBORDER * NWAVE * 16) return launch_mres_x<CIN, CEXP, COUT, RES, S, TH, TW, NWAVE, T, XBORDER>(a, N, s);
+        return launch_mres_x<CIN, CEXP, COUT, RES, S, TH, TW, NWAVE, T, 0>(a, N, s);
+    } else {
+        return launch_mres_x<CIN, CEXP, COUT, RES, S, TH, TW, NWAVE, T, XFULL>(a, N, s);
+    }
 }
 
 // producer / consumer wave counts of the two chained shapes.  Measured with the interior-only
