@@ -1,4 +1,4 @@
-"""The IoU-family box loss of one head (`yf_train_head_loss_box`: loss_cells_kernel<GRAD, true>, loss_final_box_kernel in
+"""The IoU-family box loss of one head (`yf_train_head_loss_box`: loss_cells_kernel<GRAD, true>, loss_final_kernel in
 csrc/yf_loss_kernels.hip), stated once as a dtype-generic torch function, with its case table and its comparator.  Shared by
 tests/test_cpu_box_loss.py (the definition alone) and tests/test_gpu_box_loss.py (the kernels).
 

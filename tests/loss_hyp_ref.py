@@ -1,4 +1,4 @@
-"""yolov5's objectness / class loss options on one head (`yf_train_head_loss_hyp`: loss_cells_kernel<GRAD, BOX, true>, loss_final_hyp_kernel
+"""yolov5's objectness / class loss options on one head (`yf_train_head_loss_hyp`: loss_cells_kernel<GRAD, BOX, true>, loss_final_kernel
 in csrc/yf_loss_kernels.hip, csrc/yf_loss_term.h), stated once as a dtype-generic torch function, with its option sets, its case table
 and its comparator.  Shared by tests/test_cpu_loss_hyp.py (the definition alone) and tests/test_gpu_loss_hyp.py (the kernels).
 

@@ -1,11 +1,11 @@
 """The IoU-family box loss of one head on the device -- loss_targets_kernel's gw / gh planes, loss_cells_kernel<GRAD, true>,
-loss_final_box_kernel (csrc/yf_loss_kernels.hip, csrc/yf_box_term.h) behind yf_train_head_loss_box_workspace_bytes /
+loss_final_kernel's box branch (csrc/yf_loss_kernels.hip, csrc/yf_box_term.h) behind yf_train_head_loss_box_workspace_bytes /
 yf_train_head_loss_box, called through ctypes -- against the float64 autograd model of tests/box_loss_ref.py (its docstring states the
 definition, the cases and the comparator; tests/test_cpu_box_loss.py shows on the CPU that the cases have their properties, that the
 kernel's per-cell function matches the model when compiled for the host, and that the comparator rejects every planted defect).
 
 Per case and kind: the workspace is exactly the reported size; it, d_losses[8] and d_grad_head sit between two 4 KiB guards of 0xA5
-bytes that must come back untouched (test_gpu_loss.py's Guarded); the gradient is pre-filled with a NaN pattern and must come back
+bytes that must come back untouched (tests/loss_run.py, the one runner); the gradient is pre-filled with a NaN pattern and must come back
 fully written.  The first 6 + C planes are bit for bit those yf_train_head_loss_ex leaves for the same inputs (and get_target's, by
 loss_cases.judge_planes); gw and gh bit for bit box_loss_ref.size_planes.  d_losses is recomputed exactly from the 16 doubles.  Losses
 and the `box` gradient are held to max(3 x the twin's distance, the ulp floor); box_off is exactly zero; the gradient of channels 4.. is
@@ -42,7 +42,8 @@ pytestmark = pytest.mark.gpu
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import box_loss_ref as br  # noqa: E402
 import loss_cases as lc  # noqa: E402
-import test_gpu_loss as tg  # noqa: E402  (Guarded, the NaN pre-fill and the run of yf_train_head_loss_ex)
+import loss_run as lr  # noqa: E402
+import test_gpu_loss as tg  # noqa: E402  (_check_acc: box_kind 0 is held to loss_final_kernel's arithmetic without a box)
 
 CASES = br.cases()
 LAM = br.LAMBDA_BOX
@@ -60,43 +61,9 @@ def lib():
     return _lib.lib()
 
 
-def _need(lib, c):
-    need = ctypes.c_size_t()
-    assert lib.yf_train_head_loss_box_workspace_bytes(c.N, c.fh, c.fw, c.A, c.C, ctypes.byref(need)) == 0
-    E = c.N * c.A * c.fh * c.fw
-    assert 16 * 8 + (8 + c.C) * E * 4 <= need.value <= 16 * 8 + (8 + c.C) * E * 4 + 64
-    return need.value
-
-
 def run(lib, dev, c, kind, lam=LAM, grad=True, stream=None):
-    """kind: 0 .. 3 -> (losses float32 [8], grad float32 like the logits or None, dense float32 [8 + C, E], acc float64 [16]); asserts the guards"""
-    E = c.N * c.A * c.fh * c.fw
-    need = _need(lib, c)
-    x = torch.from_numpy(c.logits).to(dev)
-    t = torch.from_numpy(c.targets).to(dev)
-    work, losses = tg.Guarded(need, dev), tg.Guarded(8 * 4, dev)
-    g = tg.Guarded(c.logits.size * 4, dev) if grad else None
-    if grad:
-        g.buf[tg.GUARD:tg.GUARD + g.nbytes].view(torch.int32).fill_(tg.NAN_BITS)
-    torch.cuda.synchronize(dev)
-    s = ctypes.c_void_p(stream.cuda_stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream)
-    rc = lib.yf_train_head_loss_box(0, c.H, c.W, x.data_ptr(), c.N, c.fh, c.fw, tg._anc(c), c.A, c.C, t.data_ptr(), c.T, lc.THRES, work.ptr, need,
-                                    losses.ptr, g.ptr if grad else None, s, kind, lam)
-    assert rc == 0, lib.yf_last_error_string()
-    torch.cuda.synchronize(dev)
-    for what, b in (("workspace", work), ("losses", losses), ("gradient", g)):
-        assert b is None or b.guards_untouched(), (c.name, what)
-    w = work.payload()
-    acc = w[:128].view(np.float64).copy()
-    dense = w[128:128 + (8 + c.C) * E * 4].view(np.float32).reshape(8 + c.C, E).copy()
-    assert (w[128 + (8 + c.C) * E * 4:] == 0xA5).all(), (c.name, "the reserved bytes behind the planes were written")
-    l8 = losses.payload().view(np.float32).copy()
-    gh = None
-    if grad:
-        gh = g.payload().view(np.float32).copy()
-        assert not (gh.view(np.int32) == np.int32(tg.NAN_BITS)).any(), (c.name, "gradient elements left unwritten")
-        gh = gh.reshape(c.logits.shape)
-    return l8, gh, dense, acc
+    """kind: 0 .. 3"""
+    return lr.run(lib, dev, c, "box", kind=kind, lam=lam, grad=grad, stream=stream)
 
 
 _results, _ex = {}, {}
@@ -111,7 +78,7 @@ def _result(lib, dev, c, kind):
 def _ex_result(lib, dev, c):
     """yf_train_head_loss_ex on the same inputs, once per case"""
     if c.name not in _ex:
-        _ex[c.name] = tg.run(lib, dev, c)
+        _ex[c.name] = lr.run(lib, dev, c, "ex")
     return _ex[c.name]
 
 
@@ -120,7 +87,7 @@ def _bits(a):
 
 
 def _check_acc(c, acc, l8, ref, lam=LAM):
-    """the workspace's 16 doubles as the header states them: d_losses is loss_final_box_kernel's float32 arithmetic on exactly these"""
+    """the workspace's 16 doubles as the header states them: d_losses is loss_final_kernel's float32 arithmetic (its box branch, both gains 1) on exactly these"""
     F = np.float32
     E = float(c.N * c.A * c.fh * c.fw)
     assert acc[7] == ref["n_pos"] and acc[8] == ref["counted"] and (acc[1:4] == 0).all() and (acc[9:] == 0).all(), (c.name, acc)
@@ -231,18 +198,17 @@ def test_lambda_box_scales_the_box_gradient_only(lib, dev):
 def test_refusals(lib, dev):
     from yolo_fastest_amd import _lib
     c = br.case_by_name("e17")
-    need = _need(lib, c)
+    need = lr.need(lib, c, "box")
     n = ctypes.c_size_t()
     assert lib.yf_train_head_loss_box_workspace_bytes(c.N, c.fh, c.fw, 9, c.C, ctypes.byref(n)) == _lib.YF_E_INVALID
     assert lib.yf_train_head_loss_box_workspace_bytes(c.N, c.fh, c.fw, c.A, 0, ctypes.byref(n)) == _lib.YF_E_INVALID
     assert lib.yf_train_head_loss_box_workspace_bytes(c.N, c.fh, c.fw, c.A, c.C, None) == _lib.YF_E_INVALID
     x, t = torch.from_numpy(c.logits).to(dev), torch.from_numpy(c.targets).to(dev)
-    work, losses = tg.Guarded(need + 8, dev), tg.Guarded(32, dev)
+    work, losses = lr.Guarded(need + 8, dev), lr.Guarded(32, dev)
     anc9 = (ctypes.c_double * 18)(*([16.0, 30.0] * 9))
 
-    def call(A=c.A, C=c.C, T=c.T, ptr=work.ptr, nbytes=need, anc=tg._anc(c), kind=3, lam=LAM):
-        return lib.yf_train_head_loss_box(0, c.H, c.W, x.data_ptr(), c.N, c.fh, c.fw, anc, A, C, t.data_ptr(), T, lc.THRES, ptr, nbytes, losses.ptr,
-                                          None, None, kind, lam)
+    def call(A=None, C=None, T=None, ptr=work.ptr, nbytes=need, anc=None, kind=3, lam=LAM):
+        return lr.call(lib, "box", c, x, t, ptr, nbytes, losses.ptr, None, None, kind, lam, A=A, C=C, T=T, anchors=anc)
     for kind in (-1, 4, 255):
         assert call(kind=kind) == _lib.YF_E_INVALID and b"box_kind" in lib.yf_last_error_string()
     for lam in (-1.0, -1e-300, float("nan"), float("inf"), float("-inf")):
@@ -252,7 +218,7 @@ def test_refusals(lib, dev):
     assert call(A=9, anc=anc9, nbytes=1 << 20) == _lib.YF_E_INVALID
     assert call(C=0) == _lib.YF_E_INVALID
     assert call(nbytes=need - 1) == _lib.YF_E_WORKSPACE
-    assert call(nbytes=tg._need(lib, c)) == _lib.YF_E_WORKSPACE          # yf_train_head_loss_ex's size is two planes short
+    assert call(nbytes=lr.need(lib, c, "ex")) == _lib.YF_E_WORKSPACE          # yf_train_head_loss_ex's size is two planes short
     assert call(ptr=work.ptr + 4) == _lib.YF_E_INVALID and b"aligned" in lib.yf_last_error_string()
     torch.cuda.synchronize(dev)
     assert (work.buf == 0xA5).all() and (losses.buf == 0xA5).all()          # a refused call launches nothing

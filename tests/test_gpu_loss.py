@@ -8,7 +8,7 @@ Per case: the dense target planes are read back from the workspace behind its 16
 include/yolo_fastest_hip.h states) and compared bit for bit with get_target (tw, th: one ulp); losses[7] exactly; the seven losses and the
 gradient per kind against max(3 x the twin's distance, the ulp floor).  The workspace is exactly the reported size; it, d_losses[8] and
 d_grad_head each sit between two 4 KiB guards of 0xA5 bytes that must come back untouched; the gradient is pre-filled with a NaN pattern
-and must come back fully written.
+and must come back fully written (tests/loss_run.py, the one runner of the three loss entries).
 
 Two runs of one case give the same gradient bits (no atomic feeds it: loss_cells_kernel<true> reads the finished n_pos) but NOT
 necessarily the same seven sums: those are double atomicAdds of one partial per workgroup, whose order differs from run to run; a
@@ -50,10 +50,9 @@ pytestmark = pytest.mark.gpu
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import loss_cases as lc  # noqa: E402
+import loss_run as lr  # noqa: E402
 
 CASES = lc.cases()
-GUARD = 4096
-NAN_BITS = 0x7FC0A5A5          # a quiet NaN no kernel computes
 
 
 @pytest.fixture(scope="module")
@@ -68,63 +67,8 @@ def lib():
     return _lib.lib()
 
 
-class Guarded:
-    """`nbytes` of device memory between two 4 KiB guards, everything 0xA5"""
-
-    def __init__(self, nbytes, dev):
-        self.nbytes = nbytes
-        self.buf = torch.full((GUARD + nbytes + GUARD,), 0xA5, dtype=torch.uint8, device=dev)
-        self.ptr = self.buf.data_ptr() + GUARD
-        assert self.ptr % 8 == 0
-
-    def payload(self):
-        return self.buf[GUARD:GUARD + self.nbytes].cpu().numpy()
-
-    def guards_untouched(self):
-        return bool((self.buf[:GUARD] == 0xA5).all()) and bool((self.buf[GUARD + self.nbytes:] == 0xA5).all())
-
-
-def _need(lib, c):
-    need = ctypes.c_size_t()
-    assert lib.yf_train_head_loss_workspace_bytes_ex(c.N, c.fh, c.fw, c.A, c.C, ctypes.byref(need)) == 0
-    E = c.N * c.A * c.fh * c.fw
-    assert 16 * 8 + (6 + c.C) * E * 4 <= need.value <= 16 * 8 + (6 + c.C) * E * 4 + 64
-    return need.value
-
-
-def _anc(c):
-    return (ctypes.c_double * (2 * c.A))(*[float(v) for a in c.anchors for v in a])
-
-
 def run(lib, dev, c, grad=True, stream=None):
-    """-> (losses float32 [8], grad float32 like the logits or None, dense float32 [6 + C, E], acc float64 [16]); asserts the guards"""
-    E = c.N * c.A * c.fh * c.fw
-    need = _need(lib, c)
-    x = torch.from_numpy(c.logits).to(dev)
-    t = torch.from_numpy(c.targets).to(dev)
-    work, losses = Guarded(need, dev), Guarded(8 * 4, dev)
-    g = Guarded(c.logits.size * 4, dev) if grad else None
-    if grad:
-        g.buf[GUARD:GUARD + g.nbytes].view(torch.int32).fill_(NAN_BITS)
-    torch.cuda.synchronize(dev)
-    s = ctypes.c_void_p(stream.cuda_stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream)
-    rc = lib.yf_train_head_loss_ex(0, c.H, c.W, x.data_ptr(), c.N, c.fh, c.fw, _anc(c), c.A, c.C, t.data_ptr(), c.T, lc.THRES, work.ptr, need,
-                                   losses.ptr, g.ptr if grad else None, s)
-    assert rc == 0, lib.yf_last_error_string()
-    torch.cuda.synchronize(dev)
-    for what, b in (("workspace", work), ("losses", losses), ("gradient", g)):
-        assert b is None or b.guards_untouched(), (c.name, what)
-    w = work.payload()
-    acc = w[:128].view(np.float64).copy()
-    dense = w[128:128 + (6 + c.C) * E * 4].view(np.float32).reshape(6 + c.C, E).copy()
-    assert (w[128 + (6 + c.C) * E * 4:] == 0xA5).all(), (c.name, "the reserved bytes behind the planes were written")
-    l8 = losses.payload().view(np.float32).copy()
-    gh = None
-    if grad:
-        gh = g.payload().view(np.float32).copy()
-        assert not (gh.view(np.int32) == np.int32(NAN_BITS)).any(), (c.name, "gradient elements left unwritten")
-        gh = gh.reshape(c.logits.shape)
-    return l8, gh, dense, acc
+    return lr.run(lib, dev, c, "ex", grad=grad, stream=stream)
 
 
 _results = {}
@@ -242,17 +186,16 @@ def test_through_YOLOLossV3(lib, dev):
 def test_refusals(lib, dev):
     from yolo_fastest_amd import _lib
     c = lc.case_by_name("e17")
-    need = _need(lib, c)
+    need = lr.need(lib, c, "ex")
     n = ctypes.c_size_t()
     assert lib.yf_train_head_loss_workspace_bytes_ex(c.N, c.fh, c.fw, 9, c.C, ctypes.byref(n)) == _lib.YF_E_INVALID
     assert lib.yf_train_head_loss_workspace_bytes_ex(c.N, c.fh, c.fw, c.A, 0, ctypes.byref(n)) == _lib.YF_E_INVALID
     x, t = torch.from_numpy(c.logits).to(dev), torch.from_numpy(c.targets).to(dev)
-    work, losses = Guarded(need + 8, dev), Guarded(32, dev)
+    work, losses = lr.Guarded(need + 8, dev), lr.Guarded(32, dev)
     anc9 = (ctypes.c_double * 18)(*([16.0, 30.0] * 9))
 
-    def call(A=c.A, C=c.C, T=c.T, ptr=work.ptr, nbytes=need, anc=_anc(c)):
-        return lib.yf_train_head_loss_ex(0, c.H, c.W, x.data_ptr(), c.N, c.fh, c.fw, anc, A, C, t.data_ptr(), T, lc.THRES, ptr, nbytes, losses.ptr,
-                                         None, None)
+    def call(A=None, C=None, T=None, ptr=work.ptr, nbytes=need, anc=None):
+        return lr.call(lib, "ex", c, x, t, ptr, nbytes, losses.ptr, None, None, A=A, C=C, T=T, anchors=anc)
     assert call(T=0) == _lib.YF_E_INVALID
     assert call(A=9, anc=anc9, nbytes=1 << 20) == _lib.YF_E_INVALID
     assert call(C=0) == _lib.YF_E_INVALID

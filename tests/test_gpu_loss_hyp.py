@@ -1,4 +1,4 @@
-"""yolov5's objectness / class loss options of one head on the device -- loss_cells_kernel<GRAD, BOX, true> and loss_final_hyp_kernel
+"""yolov5's objectness / class loss options of one head on the device -- loss_cells_kernel<GRAD, BOX, true> and loss_final_kernel
 (csrc/yf_loss_kernels.hip, csrc/yf_loss_term.h) behind yf_train_head_loss_hyp_workspace_bytes / yf_train_head_loss_hyp, called through
 ctypes -- against the float64 model of tests/loss_hyp_ref.py (its docstring states the definition, the option sets, the cases and the
 comparator; tests/test_cpu_loss_hyp.py shows on the CPU that the definition is yolov5's, that the model's closed-form gradient is float64
@@ -54,8 +54,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import box_loss_ref as br  # noqa: E402
 import loss_cases as lc  # noqa: E402
 import loss_hyp_ref as hr  # noqa: E402
-import test_gpu_box_loss as tb  # noqa: E402  (the run of yf_train_head_loss_box)
-import test_gpu_loss as tg  # noqa: E402  (Guarded, the NaN pre-fill and the run of yf_train_head_loss_ex)
+import loss_run as lr  # noqa: E402
 
 CASES = hr.cases()
 SUBSET = [hr.case_by_name(n) for n in hr.SUBSET]
@@ -77,44 +76,9 @@ def _kind(o):
     return br.KIND_ID[o.box] if o.box else 0
 
 
-def _need(lib, c):
-    need, box = ctypes.c_size_t(), ctypes.c_size_t()
-    assert lib.yf_train_head_loss_hyp_workspace_bytes(c.N, c.fh, c.fw, c.A, c.C, ctypes.byref(need)) == 0
-    assert lib.yf_train_head_loss_box_workspace_bytes(c.N, c.fh, c.fw, c.A, c.C, ctypes.byref(box)) == 0
-    assert need.value == box.value
-    return need.value
-
-
 def run(lib, dev, c, o, grad=True, stream=None):
-    """o: loss_hyp_ref.Opts -> (losses float32 [8], grad float32 like the logits or None, dense float32 [8 + C, E], acc float64 [16]); asserts
-    the guards"""
-    E = c.N * c.A * c.fh * c.fw
-    need = _need(lib, c)
-    x = torch.from_numpy(c.logits).to(dev)
-    t = torch.from_numpy(c.targets).to(dev)
-    work, losses = tg.Guarded(need, dev), tg.Guarded(8 * 4, dev)
-    g = tg.Guarded(c.logits.size * 4, dev) if grad else None
-    if grad:
-        g.buf[tg.GUARD:tg.GUARD + g.nbytes].view(torch.int32).fill_(tg.NAN_BITS)
-    torch.cuda.synchronize(dev)
-    s = ctypes.c_void_p(stream.cuda_stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream)
-    rc = lib.yf_train_head_loss_hyp(0, c.H, c.W, x.data_ptr(), c.N, c.fh, c.fw, tg._anc(c), c.A, c.C, t.data_ptr(), c.T, lc.THRES, work.ptr, need,
-                                    losses.ptr, g.ptr if grad else None, s, _kind(o), o.lambda_box, *o[:8])
-    assert rc == 0, lib.yf_last_error_string()
-    torch.cuda.synchronize(dev)
-    for what, b in (("workspace", work), ("losses", losses), ("gradient", g)):
-        assert b is None or b.guards_untouched(), (c.name, what)
-    w = work.payload()
-    acc = w[:128].view(np.float64).copy()
-    dense = w[128:128 + (8 + c.C) * E * 4].view(np.float32).reshape(8 + c.C, E).copy()
-    assert (w[128 + (8 + c.C) * E * 4:] == 0xA5).all(), (c.name, "the reserved bytes behind the planes were written")
-    l8 = losses.payload().view(np.float32).copy()
-    gh = None
-    if grad:
-        gh = g.payload().view(np.float32).copy()
-        assert not (gh.view(np.int32) == np.int32(tg.NAN_BITS)).any(), (c.name, "gradient elements left unwritten")
-        gh = gh.reshape(c.logits.shape)
-    return l8, gh, dense, acc
+    """o: loss_hyp_ref.Opts"""
+    return lr.run(lib, dev, c, "hyp", kind=_kind(o), lam=o.lambda_box, opts=o[:8], grad=grad, stream=stream)
 
 
 _results, _box = {}, {}
@@ -129,7 +93,7 @@ def _result(lib, dev, c, name):
 def _box_result(lib, dev, c, kind):
     """yf_train_head_loss_box on the same inputs, once per case and box_kind"""
     if (c.name, kind) not in _box:
-        _box[c.name, kind] = tb.run(lib, dev, c, kind)
+        _box[c.name, kind] = lr.run(lib, dev, c, "box", kind=kind, lam=br.LAMBDA_BOX)
     return _box[c.name, kind]
 
 
@@ -138,7 +102,7 @@ def _bits(a):
 
 
 def _check_acc(c, o, acc, l8):
-    """d_losses is loss_final_hyp_kernel's float32 arithmetic on exactly the workspace's 16 doubles"""
+    """d_losses is loss_final_kernel's float32 arithmetic on exactly the workspace's 16 doubles"""
     F = np.float32
     E = float(c.N * c.A * c.fh * c.fw)
     ref = lc.reference(c)
@@ -222,7 +186,7 @@ def test_neutral_options_are_the_box_entry_bit_for_bit(lib, dev, kind):
                 a, b = float(a), float(b)
                 assert (math.isnan(a) and math.isnan(b)) or abs(a - b) <= lc.ulp32(b), (c.name, a, b)
             if kind == 0:
-                el8, eg, edense, _ = tg.run(lib, dev, c)
+                el8, eg, edense, _ = lr.run(lib, dev, c, "ex")
                 assert np.array_equal(_bits(g), _bits(eg)) and np.array_equal(_bits(dense[:6 + c.C]), _bits(edense)), c.name
 
 
@@ -272,16 +236,15 @@ def test_on_a_stream_of_its_own(lib, dev, case):
 def test_refusals(lib, dev):
     from yolo_fastest_amd import _lib
     c = hr.case_by_name("e17")
-    need = _need(lib, c)
+    need = lr.need(lib, c, "hyp")
     n = ctypes.c_size_t()
     assert lib.yf_train_head_loss_hyp_workspace_bytes(c.N, c.fh, c.fw, 9, c.C, ctypes.byref(n)) == _lib.YF_E_INVALID
     assert lib.yf_train_head_loss_hyp_workspace_bytes(c.N, c.fh, c.fw, c.A, c.C, None) == _lib.YF_E_INVALID
     x, t = torch.from_numpy(c.logits).to(dev), torch.from_numpy(c.targets).to(dev)
-    work, losses, grad = tg.Guarded(need + 8, dev), tg.Guarded(32, dev), tg.Guarded(c.logits.size * 4, dev)
+    work, losses, grad = lr.Guarded(need + 8, dev), lr.Guarded(32, dev), lr.Guarded(c.logits.size * 4, dev)
 
     def call(o=hr.OPTION_SETS["all"], kind=None, lam=br.LAMBDA_BOX, ptr=work.ptr, nbytes=need, T=c.T):
-        return lib.yf_train_head_loss_hyp(0, c.H, c.W, x.data_ptr(), c.N, c.fh, c.fw, tg._anc(c), c.A, c.C, t.data_ptr(), T, lc.THRES, ptr, nbytes,
-                                          losses.ptr, grad.ptr, None, _kind(o) if kind is None else kind, lam, *o[:8])
+        return lr.call(lib, "hyp", c, x, t, ptr, nbytes, losses.ptr, grad.ptr, None, _kind(o) if kind is None else kind, lam, o[:8], T=T)
     nan, inf = float("nan"), float("inf")
     ok = hr.OPTION_SETS["all"]
     refused = [ok._replace(**{f: v}) for f in hr.OPTION_NAMES for v in (nan, inf, -inf)]
@@ -300,7 +263,7 @@ def test_refusals(lib, dev):
         assert call(lam=lam) == _lib.YF_E_INVALID and b"lambda_box" in lib.yf_last_error_string()
     assert call(T=0) == _lib.YF_E_INVALID
     assert call(nbytes=need - 1) == _lib.YF_E_WORKSPACE
-    assert call(nbytes=tg._need(lib, c)) == _lib.YF_E_WORKSPACE          # yf_train_head_loss_ex's size is two planes short
+    assert call(nbytes=lr.need(lib, c, "ex")) == _lib.YF_E_WORKSPACE          # yf_train_head_loss_ex's size is two planes short
     assert call(ptr=work.ptr + 4) == _lib.YF_E_INVALID and b"aligned" in lib.yf_last_error_string()
     torch.cuda.synchronize(dev)
     assert (work.buf == 0xA5).all() and (losses.buf == 0xA5).all() and (grad.buf == 0xA5).all()      # a refused call launches nothing
@@ -336,8 +299,8 @@ def test_through_YOLOLossV3(lib, dev):
         assert torch.equal(x.grad.cpu(), 3.0 * torch.from_numpy(g))
     # the defaults: yf_train_head_loss_ex, and with box_loss alone yf_train_head_loss_box
     default = val.YOLOLossV3(c.anchors, c.C, [c.H, c.W, 1], dev)                  # default-constructed: the parent's call, the parent's bits
-    for crit, want in ((default, tg.run(lib, dev, c)),
-                       (val.YOLOLossV3(c.anchors, c.C, [c.H, c.W, 1], dev, fl_alpha=0.9), tg.run(lib, dev, c)),
+    for crit, want in ((default, lr.run(lib, dev, c, "ex")),
+                       (val.YOLOLossV3(c.anchors, c.C, [c.H, c.W, 1], dev, fl_alpha=0.9), lr.run(lib, dev, c, "ex")),
                        (val.YOLOLossV3(c.anchors, c.C, [c.H, c.W, 1], dev, box_loss="ciou"), _box_result(lib, dev, c, 3)),
                        (val.YOLOLossV3(c.anchors, c.C, [c.H, c.W, 1], dev, box_loss="ciou", fl_alpha=0.9), _box_result(lib, dev, c, 3))):
         x = torch.from_numpy(c.logits).to(dev).requires_grad_(True)

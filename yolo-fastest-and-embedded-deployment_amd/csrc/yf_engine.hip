@@ -1328,6 +1328,12 @@ int yf_nms_sorted(yf_handle h, const int32_t* d_boxes, int n, double nms_thres, 
     return YF_OK;
 }
 
+// yolo_loss.py:52-56: strides and feature-map-scaled anchors are Python doubles, stored into FloatTensors (torch uses them as float32)
+static void scale_anchors(const double* anchors, int na, double stride_w, double stride_h, float* anc)
+{
+    for (int a = 0; a < na; ++a) { anc[2 * a] = (float)(anchors[2 * a] / stride_w); anc[2 * a + 1] = (float)(anchors[2 * a + 1] / stride_h); }
+}
+
 // Validation-time path.  anchors: HOST double[3][2] of THIS head, net-input pixels.
 int yf_val_decode_head(yf_handle h, const float* d_head, int N, int fh, int fw, const double* anchors, int M_total, int m_off,
                        float* d_out, void* stream)
@@ -1336,10 +1342,9 @@ int yf_val_decode_head(yf_handle h, const float* d_head, int N, int fh, int fw, 
     if (!h || !d_head || !anchors || !d_out || N <= 0 || fh <= 0 || fw <= 0 || m_off < 0 || m_off + na * fh * fw > M_total)
         return fail(YF_E_INVALID, "yf_val_decode_head: bad argument");
     HIP_OK(hipSetDevice(h->device));
-    // yolo_loss.py:52-56: strides and feature-map-scaled anchors are Python doubles, stored into FloatTensors
     const double stride_h = (double)h->H / fh, stride_w = (double)h->W / fw;
     float anc[2 * yf::POST_MAX_ANCHORS];
-    for (int a = 0; a < na; ++a) { anc[2 * a] = (float)(anchors[2 * a] / stride_w); anc[2 * a + 1] = (float)(anchors[2 * a + 1] / stride_h); }
+    scale_anchors(anchors, na, stride_w, stride_h, anc);
     yf::launch_val_decode(d_head, d_out, N, fh, fw, M_total, m_off, anc, na, h->num_cls, (float)stride_w, (float)stride_h, (hipStream_t)stream);
     HIP_OK(hipGetLastError());
     return YF_OK;
@@ -1432,6 +1437,15 @@ int yf_val_nms_v5(int device, const float* d_pred, int N, int M, int num_classes
 }
 
 // Training-time loss of ONE head (first slice).  anchors: HOST double[3][2] of this head, net-input pixels.
+// size_planes: 0 = the reference's terms alone (6 + C planes), 1 = the box and option entries (gw and gh behind them).
+static int loss_workspace_bytes(const char* who, int N, int fh, int fw, int num_anchors, int num_classes, int size_planes, size_t* out)
+{
+    if (!out || N <= 0 || fh <= 0 || fw <= 0 || num_anchors < 1 || num_anchors > yf::POST_MAX_ANCHORS || num_classes < 1)
+        return fail(YF_E_INVALID, "%s: bad argument", who);
+    *out = yf::train_loss_workspace_bytes(N, fh, fw, num_anchors, num_classes, size_planes);
+    return YF_OK;
+}
+
 int yf_train_loss_workspace_bytes(yf_handle h, int N, int fh, int fw, size_t* out)
 {
     if (!h) return fail(YF_E_INVALID, "yf_train_loss_workspace_bytes: null handle");
@@ -1442,9 +1456,57 @@ int yf_train_head_loss_workspace_bytes(int N, int fh, int fw, size_t* out) { ret
 
 int yf_train_head_loss_workspace_bytes_ex(int N, int fh, int fw, int num_anchors, int num_classes, size_t* out)
 {
-    if (!out || N <= 0 || fh <= 0 || fw <= 0 || num_anchors < 1 || num_anchors > yf::POST_MAX_ANCHORS || num_classes < 1)
-        return fail(YF_E_INVALID, "yf_train_head_loss_workspace_bytes: bad argument");
-    *out = yf::train_loss_workspace_bytes(N, fh, fw, num_anchors, num_classes);
+    return loss_workspace_bytes("yf_train_head_loss_workspace_bytes", N, fh, fw, num_anchors, num_classes, 0, out);
+}
+
+int yf_train_head_loss_box_workspace_bytes(int N, int fh, int fw, int num_anchors, int num_classes, size_t* out)
+{
+    return loss_workspace_bytes("yf_train_head_loss_box_workspace_bytes", N, fh, fw, num_anchors, num_classes, 1, out);
+}
+
+int yf_train_head_loss_hyp_workspace_bytes(int N, int fh, int fw, int num_anchors, int num_classes, size_t* out)
+{
+    return loss_workspace_bytes("yf_train_head_loss_hyp_workspace_bytes", N, fh, fw, num_anchors, num_classes, 1, out);
+}
+
+// The one body of the yf_train_*loss* entries.  who: the calling entry's name, for the messages.  box_entry false: the reference's terms
+// in their own workspace (yf_train_head_loss_ex; box_kind and lambda_box are not read); true: the box entry's workspace, box_kind 0 .. 3.
+// opt: nullptr, or the eight options of yf_train_head_loss_hyp in its order.
+static int head_loss(const char* who, int device, int H, int W, const float* d_head, int N, int fh, int fw, const double* anchors, int num_anchors,
+                     int num_classes, const float* d_targets, int T, double ignore_thres, void* d_work, size_t work_bytes, float* d_losses,
+                     float* d_grad_head, void* stream, bool box_entry, int box_kind, double lambda_box, const double* opt)
+{
+    static_assert((int)yf::BOX_REF == YF_BOX_REF && (int)yf::BOX_GIOU == YF_BOX_GIOU && (int)yf::BOX_DIOU == YF_BOX_DIOU &&
+                  (int)yf::BOX_CIOU == YF_BOX_CIOU && yf::BOX_WH_CLAMP == YF_BOX_WH_CLAMP, "yf_box_term.h and the header agree");
+    if (!d_head || !anchors || !d_targets || !d_work || !d_losses || N <= 0 || fh <= 0 || fw <= 0 || T <= 0 || H <= 0 || W <= 0 ||
+        num_anchors < 1 || num_anchors > yf::POST_MAX_ANCHORS || num_classes < 1)
+        return fail(YF_E_INVALID, "%s: bad argument", who);
+    if (box_entry) {
+        if (box_kind < YF_BOX_REF || box_kind > YF_BOX_CIOU) return fail(YF_E_INVALID, "%s: box_kind must be 0 .. 3", who);
+        if (!(lambda_box >= 0.0 && lambda_box < HUGE_VAL)) return fail(YF_E_INVALID, "%s: lambda_box must be finite and >= 0", who);
+    }
+    if (opt) {                                   // obj_pw, cls_pw, label_smoothing, fl_gamma, fl_alpha, obj_iou, lambda_conf, lambda_cls
+        for (int i = 0; i < 8; ++i)
+            if (!std::isfinite(opt[i])) return fail(YF_E_INVALID, "%s: every option must be finite", who);
+        if (!(opt[0] > 0.0 && opt[1] > 0.0)) return fail(YF_E_INVALID, "%s: obj_pw and cls_pw must be > 0", who);
+        if (!(opt[2] >= 0.0 && opt[2] <= 1.0)) return fail(YF_E_INVALID, "%s: label_smoothing must lie in 0 .. 1", who);
+        if (!(opt[3] == 0.0 || opt[3] >= 1.0))
+            return fail(YF_E_INVALID, "%s: fl_gamma must be 0 or >= 1 (the derivative is unbounded at p_t = 1 in between)", who);
+        if (!(opt[4] >= 0.0 && opt[4] <= 1.0)) return fail(YF_E_INVALID, "%s: fl_alpha must lie in 0 .. 1", who);
+        if (!(opt[5] >= 0.0 && opt[5] <= 1.0)) return fail(YF_E_INVALID, "%s: obj_iou must lie in 0 .. 1", who);
+        if (opt[5] > 0.0 && box_kind == YF_BOX_REF)
+            return fail(YF_E_INVALID, "%s: obj_iou > 0 needs an IoU-family box_kind (YF_BOX_REF has no IoU value)", who);
+        if (!(opt[6] >= 0.0 && opt[7] >= 0.0)) return fail(YF_E_INVALID, "%s: lambda_conf and lambda_cls must be >= 0", who);
+    }
+    if (work_bytes < yf::train_loss_workspace_bytes(N, fh, fw, num_anchors, num_classes, box_entry))
+        return fail(YF_E_WORKSPACE, "%s: workspace too small", who);
+    if (reinterpret_cast<uintptr_t>(d_work) & 7) return fail(YF_E_INVALID, "%s: workspace must be 8-byte aligned", who);
+    HIP_OK(hipSetDevice(device));
+    float anc[2 * yf::POST_MAX_ANCHORS];
+    scale_anchors(anchors, num_anchors, (double)W / fw, (double)H / fh, anc);
+    yf::launch_train_loss(d_head, N, fh, fw, anc, num_anchors, num_classes, d_targets, T, (float)ignore_thres, d_work, d_losses, d_grad_head,
+                          yf::LossSpec{box_entry ? box_kind : -1, lambda_box, opt}, (hipStream_t)stream);
+    HIP_OK(hipGetLastError());
     return YF_OK;
 }
 
@@ -1468,97 +1530,28 @@ int yf_train_head_loss_ex(int device, int H, int W, const float* d_head, int N, 
                           int num_classes, const float* d_targets, int T, double ignore_thres, void* d_work, size_t work_bytes, float* d_losses,
                           float* d_grad_head, void* stream)
 {
-    if (!d_head || !anchors || !d_targets || !d_work || !d_losses || N <= 0 || fh <= 0 || fw <= 0 || T <= 0 || H <= 0 || W <= 0 ||
-        num_anchors < 1 || num_anchors > yf::POST_MAX_ANCHORS || num_classes < 1)
-        return fail(YF_E_INVALID, "yf_train_head_loss: bad argument");
-    if (work_bytes < yf::train_loss_workspace_bytes(N, fh, fw, num_anchors, num_classes)) return fail(YF_E_WORKSPACE, "yf_train_head_loss: workspace too small");
-    if (reinterpret_cast<uintptr_t>(d_work) & 7) return fail(YF_E_INVALID, "yf_train_head_loss: workspace must be 8-byte aligned");
-    HIP_OK(hipSetDevice(device));
-    // yolo_loss.py:52-56: strides and feature-map-scaled anchors are Python doubles; torch uses them as float32
-    const double stride_h = (double)H / fh, stride_w = (double)W / fw;
-    float anc[2 * yf::POST_MAX_ANCHORS];
-    for (int a = 0; a < num_anchors; ++a) { anc[2 * a] = (float)(anchors[2 * a] / stride_w); anc[2 * a + 1] = (float)(anchors[2 * a + 1] / stride_h); }
-    yf::launch_train_loss(d_head, N, fh, fw, anc, num_anchors, num_classes, d_targets, T, (float)ignore_thres, d_work, d_losses, d_grad_head,
-                          (hipStream_t)stream);
-    HIP_OK(hipGetLastError());
-    return YF_OK;
+    return head_loss("yf_train_head_loss", device, H, W, d_head, N, fh, fw, anchors, num_anchors, num_classes, d_targets, T, ignore_thres, d_work,
+                     work_bytes, d_losses, d_grad_head, stream, false, 0, 0.0, nullptr);
 }
 
 // The same with the box regressed as one IoU-family term (yolo_fastest_hip.h); box_kind 0 runs the reference's terms.
-int yf_train_head_loss_box_workspace_bytes(int N, int fh, int fw, int num_anchors, int num_classes, size_t* out)
-{
-    if (!out || N <= 0 || fh <= 0 || fw <= 0 || num_anchors < 1 || num_anchors > yf::POST_MAX_ANCHORS || num_classes < 1)
-        return fail(YF_E_INVALID, "yf_train_head_loss_box_workspace_bytes: bad argument");
-    *out = yf::train_loss_box_workspace_bytes(N, fh, fw, num_anchors, num_classes);
-    return YF_OK;
-}
-
 int yf_train_head_loss_box(int device, int H, int W, const float* d_head, int N, int fh, int fw, const double* anchors, int num_anchors,
                            int num_classes, const float* d_targets, int T, double ignore_thres, void* d_work, size_t work_bytes, float* d_losses,
                            float* d_grad_head, void* stream, int box_kind, double lambda_box)
 {
-    if (!d_head || !anchors || !d_targets || !d_work || !d_losses || N <= 0 || fh <= 0 || fw <= 0 || T <= 0 || H <= 0 || W <= 0 ||
-        num_anchors < 1 || num_anchors > yf::POST_MAX_ANCHORS || num_classes < 1)
-        return fail(YF_E_INVALID, "yf_train_head_loss_box: bad argument");
-    static_assert((int)yf::BOX_REF == YF_BOX_REF && (int)yf::BOX_GIOU == YF_BOX_GIOU && (int)yf::BOX_DIOU == YF_BOX_DIOU &&
-                  (int)yf::BOX_CIOU == YF_BOX_CIOU && yf::BOX_WH_CLAMP == YF_BOX_WH_CLAMP, "yf_box_term.h and the header agree");
-    if (box_kind < YF_BOX_REF || box_kind > YF_BOX_CIOU) return fail(YF_E_INVALID, "yf_train_head_loss_box: box_kind must be 0 .. 3");
-    if (!(lambda_box >= 0.0 && lambda_box < HUGE_VAL)) return fail(YF_E_INVALID, "yf_train_head_loss_box: lambda_box must be finite and >= 0");
-    if (work_bytes < yf::train_loss_box_workspace_bytes(N, fh, fw, num_anchors, num_classes))
-        return fail(YF_E_WORKSPACE, "yf_train_head_loss_box: workspace too small");
-    if (reinterpret_cast<uintptr_t>(d_work) & 7) return fail(YF_E_INVALID, "yf_train_head_loss_box: workspace must be 8-byte aligned");
-    HIP_OK(hipSetDevice(device));
-    const double stride_h = (double)H / fh, stride_w = (double)W / fw;      // as in yf_train_head_loss_ex
-    float anc[2 * yf::POST_MAX_ANCHORS];
-    for (int a = 0; a < num_anchors; ++a) { anc[2 * a] = (float)(anchors[2 * a] / stride_w); anc[2 * a + 1] = (float)(anchors[2 * a + 1] / stride_h); }
-    yf::launch_train_loss_box(d_head, N, fh, fw, anc, num_anchors, num_classes, d_targets, T, (float)ignore_thres, d_work, d_losses, d_grad_head,
-                              box_kind, lambda_box, (hipStream_t)stream);
-    HIP_OK(hipGetLastError());
-    return YF_OK;
+    return head_loss("yf_train_head_loss_box", device, H, W, d_head, N, fh, fw, anchors, num_anchors, num_classes, d_targets, T, ignore_thres,
+                     d_work, work_bytes, d_losses, d_grad_head, stream, true, box_kind, lambda_box, nullptr);
 }
 
 // The same with yolov5's objectness / class options (yolo_fastest_hip.h); the neutral values run yf_train_head_loss_box's launches.
-int yf_train_head_loss_hyp_workspace_bytes(int N, int fh, int fw, int num_anchors, int num_classes, size_t* out)
-{
-    if (!out || N <= 0 || fh <= 0 || fw <= 0 || num_anchors < 1 || num_anchors > yf::POST_MAX_ANCHORS || num_classes < 1)
-        return fail(YF_E_INVALID, "yf_train_head_loss_hyp_workspace_bytes: bad argument");
-    *out = yf::train_loss_box_workspace_bytes(N, fh, fw, num_anchors, num_classes);
-    return YF_OK;
-}
-
 int yf_train_head_loss_hyp(int device, int H, int W, const float* d_head, int N, int fh, int fw, const double* anchors, int num_anchors,
                            int num_classes, const float* d_targets, int T, double ignore_thres, void* d_work, size_t work_bytes, float* d_losses,
                            float* d_grad_head, void* stream, int box_kind, double lambda_box, double obj_pw, double cls_pw, double label_smoothing,
                            double fl_gamma, double fl_alpha, double obj_iou, double lambda_conf, double lambda_cls)
 {
-    if (!d_head || !anchors || !d_targets || !d_work || !d_losses || N <= 0 || fh <= 0 || fw <= 0 || T <= 0 || H <= 0 || W <= 0 ||
-        num_anchors < 1 || num_anchors > yf::POST_MAX_ANCHORS || num_classes < 1)
-        return fail(YF_E_INVALID, "yf_train_head_loss_hyp: bad argument");
-    if (box_kind < YF_BOX_REF || box_kind > YF_BOX_CIOU) return fail(YF_E_INVALID, "yf_train_head_loss_hyp: box_kind must be 0 .. 3");
-    if (!(lambda_box >= 0.0 && lambda_box < HUGE_VAL)) return fail(YF_E_INVALID, "yf_train_head_loss_hyp: lambda_box must be finite and >= 0");
     const double opt[8] = {obj_pw, cls_pw, label_smoothing, fl_gamma, fl_alpha, obj_iou, lambda_conf, lambda_cls};
-    for (double v : opt)
-        if (!std::isfinite(v)) return fail(YF_E_INVALID, "yf_train_head_loss_hyp: every option must be finite");
-    if (!(obj_pw > 0.0 && cls_pw > 0.0)) return fail(YF_E_INVALID, "yf_train_head_loss_hyp: obj_pw and cls_pw must be > 0");
-    if (!(label_smoothing >= 0.0 && label_smoothing <= 1.0)) return fail(YF_E_INVALID, "yf_train_head_loss_hyp: label_smoothing must lie in 0 .. 1");
-    if (!(fl_gamma == 0.0 || fl_gamma >= 1.0))
-        return fail(YF_E_INVALID, "yf_train_head_loss_hyp: fl_gamma must be 0 or >= 1 (the derivative is unbounded at p_t = 1 in between)");
-    if (!(fl_alpha >= 0.0 && fl_alpha <= 1.0)) return fail(YF_E_INVALID, "yf_train_head_loss_hyp: fl_alpha must lie in 0 .. 1");
-    if (!(obj_iou >= 0.0 && obj_iou <= 1.0)) return fail(YF_E_INVALID, "yf_train_head_loss_hyp: obj_iou must lie in 0 .. 1");
-    if (obj_iou > 0.0 && box_kind == YF_BOX_REF)
-        return fail(YF_E_INVALID, "yf_train_head_loss_hyp: obj_iou > 0 needs an IoU-family box_kind (YF_BOX_REF has no IoU value)");
-    if (!(lambda_conf >= 0.0 && lambda_cls >= 0.0)) return fail(YF_E_INVALID, "yf_train_head_loss_hyp: lambda_conf and lambda_cls must be >= 0");
-    if (work_bytes < yf::train_loss_box_workspace_bytes(N, fh, fw, num_anchors, num_classes))
-        return fail(YF_E_WORKSPACE, "yf_train_head_loss_hyp: workspace too small");
-    if (reinterpret_cast<uintptr_t>(d_work) & 7) return fail(YF_E_INVALID, "yf_train_head_loss_hyp: workspace must be 8-byte aligned");
-    HIP_OK(hipSetDevice(device));
-    const double stride_h = (double)H / fh, stride_w = (double)W / fw;      // as in yf_train_head_loss_ex
-    float anc[2 * yf::POST_MAX_ANCHORS];
-    for (int a = 0; a < num_anchors; ++a) { anc[2 * a] = (float)(anchors[2 * a] / stride_w); anc[2 * a + 1] = (float)(anchors[2 * a + 1] / stride_h); }
-    yf::launch_train_loss_hyp(d_head, N, fh, fw, anc, num_anchors, num_classes, d_targets, T, (float)ignore_thres, d_work, d_losses, d_grad_head,
-                              box_kind, lambda_box, opt, (hipStream_t)stream);
-    HIP_OK(hipGetLastError());
-    return YF_OK;
+    return head_loss("yf_train_head_loss_hyp", device, H, W, d_head, N, fh, fw, anchors, num_anchors, num_classes, d_targets, T, ignore_thres,
+                     d_work, work_bytes, d_losses, d_grad_head, stream, true, box_kind, lambda_box, opt);
 }
 
 

@@ -361,17 +361,13 @@ struct IouvThresholds { float v[VAL_IOUV_MAX_THRESHOLDS]; };
 void launch_val_match_iouv(const float* det, const int32_t* counts, int N, int kmax, const float* targets, int T, const float* thr, int nthr,
                            const int64_t* base, int64_t* next, int32_t* records, int64_t cap, hipStream_t s);
 // training-time loss of one head and its gradient with respect to the head tensor (yf_loss_kernels.hip)
-size_t train_loss_workspace_bytes(int N, int fh, int fw, int na = 3, int nc = 3);
+// box_kind -1: the reference's terms in their own workspace (6 + nc planes).  0 .. 3 (yf_box_term.h's BOX_*): the box entry's workspace
+// (8 + nc planes, gw and gh written); 0 still runs the reference's terms, 1 .. 3 the IoU-family one, weighted lambda_box.
+// hyp: nullptr, or yolov5's objectness / class options (opt[8]: the options of yf_train_head_loss_hyp in its order; needs box_kind >= 0)
+struct LossSpec { int box_kind; double lambda_box; const double* hyp; };
+size_t train_loss_workspace_bytes(int N, int fh, int fw, int na, int nc, int size_planes);
 void launch_train_loss(const float* head, int N, int fh, int fw, const float* anc, int na, int nc, const float* targets, int T, float ignore_thres,
-                       void* work, float* losses, float* grad, hipStream_t s);
-// the same with an IoU-family box term (box_kind: yf_box_term.h's BOX_*; 0 = the reference's terms in the box entry's workspace)
-size_t train_loss_box_workspace_bytes(int N, int fh, int fw, int na, int nc);
-void launch_train_loss_box(const float* head, int N, int fh, int fw, const float* anc, int na, int nc, const float* targets, int T,
-                           float ignore_thres, void* work, float* losses, float* grad, int box_kind, double lambda_box, hipStream_t s);
-// the same with yolov5's objectness / class options (opt[8]: the options of yf_train_head_loss_hyp in its order); the box entry's workspace
-void launch_train_loss_hyp(const float* head, int N, int fh, int fw, const float* anc, int na, int nc, const float* targets, int T,
-                           float ignore_thres, void* work, float* losses, float* grad, int box_kind, double lambda_box, const double* opt,
-                           hipStream_t s);
+                       void* work, float* losses, float* grad, const LossSpec& spec, hipStream_t s);
 // training-step operators (yf_train_kernels.hip): NCHW fp32, correctness-first
 // BatchNorm's partial sums out of the conv's epilogue (the large maps): the caller sets part / cap_bytes (a region no concurrent kernel
 // uses: behind BatchNorm's own megabyte of the scratch), the conv launcher sets count (> 0: it left count pairs per channel in

@@ -9,10 +9,11 @@
 // writes the gradient.  The backward of the layers themselves is not part of this slice.
 //
 // yf_train_head_loss_box (opt-in) regresses the box as ONE IoU-family term per positive cell in place of the reference's four
-// (yf_box_term.h): two more target planes, loss_cells_kernel<GRAD, true> and loss_final_box_kernel, the same five launches.
+// (yf_box_term.h): two more target planes and loss_cells_kernel<GRAD, true>, the same five launches.
 //
 // yf_train_head_loss_hyp (opt-in) adds yolov5's objectness / class options to either: loss_cells_kernel<GRAD, BOX, true> evaluates the
-// BCE elements a non-neutral option touches through yf_loss_term.h, loss_final_hyp_kernel applies the two gains; five launches again.
+// BCE elements a non-neutral option touches through yf_loss_term.h, loss_final_kernel applies the two gains; five launches again.
+// One launcher (launch_train_loss) and one loss_final_kernel serve all three entries.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -219,35 +220,16 @@ __global__ void __launch_bounds__(256) loss_cells_kernel(const float* __restrict
     }
 }
 
-// losses[0..6] = total, x, y, w, h, conf, cls (float32, combined like yolo_loss.py:90-92); losses[7] = targets skipped: cell outside the map or class outside 0 .. nc-1
-__global__ void loss_final_kernel(const double* __restrict__ acc, long E, int nc, float* __restrict__ losses)
+// losses[0..7] = total, x, y, w, h, conf, cls (float32, combined like yolo_loss.py:90-92), targets skipped (cell outside the map or class
+// outside 0 .. nc-1).  box: total, box, 0, 0, 0, conf, cls, targets skipped; total = lambda * box + conf + cls in float32, left to right.
+// lambda_conf / lambda_cls: the gains of yf_train_head_loss_hyp on conf and cls in the total (1.0f elsewhere: x * 1.0f is x); [5] and [6]
+// stay unweighted
+__global__ void loss_final_kernel(const double* __restrict__ acc, long E, int nc, int box, float lambda, float lambda_conf, float lambda_cls,
+                                  float* __restrict__ losses)
 {
     const float lx = (float)(acc[0] / (double)E), ly = (float)(acc[1] / (double)E), lw = (float)(acc[2] / (double)E), lh = (float)(acc[3] / (double)E);
     const float lconf = (float)(acc[4] / (double)E) + 0.5f * (float)(acc[5] / (double)E);
     const float lcls = (float)(acc[6] / ((double)nc * acc[7]));     // no positive cell: 0 / 0 = nan, like the mean of an empty tensor
-    losses[0] = lx * 2.5f + ly * 2.5f + lw * 2.5f + lh * 2.5f + lconf * 1.0f + lcls * 1.0f;
-    losses[1] = lx; losses[2] = ly; losses[3] = lw; losses[4] = lh; losses[5] = lconf; losses[6] = lcls;
-    losses[7] = (float)acc[8];
-}
-
-// losses[0..7] = total, box, 0, 0, 0, conf, cls, targets skipped; total = lambda * box + conf + cls in float32, left to right
-__global__ void loss_final_box_kernel(const double* __restrict__ acc, long E, int nc, float lambda, float* __restrict__ losses)
-{
-    const float lbox = (float)(acc[0] / (double)E);
-    const float lconf = (float)(acc[4] / (double)E) + 0.5f * (float)(acc[5] / (double)E);
-    const float lcls = (float)(acc[6] / ((double)nc * acc[7]));     // no positive cell: nan, as in loss_final_kernel
-    losses[0] = lambda * lbox + lconf * 1.0f + lcls * 1.0f;
-    losses[1] = lbox; losses[2] = 0.f; losses[3] = 0.f; losses[4] = 0.f; losses[5] = lconf; losses[6] = lcls;
-    losses[7] = (float)acc[8];
-}
-
-// yf_train_head_loss_hyp: either of the two above with the gains on conf and cls in the total; [5] and [6] stay unweighted
-__global__ void loss_final_hyp_kernel(const double* __restrict__ acc, long E, int nc, int box, float lambda, float lambda_conf, float lambda_cls,
-                                      float* __restrict__ losses)
-{
-    const float lx = (float)(acc[0] / (double)E), ly = (float)(acc[1] / (double)E), lw = (float)(acc[2] / (double)E), lh = (float)(acc[3] / (double)E);
-    const float lconf = (float)(acc[4] / (double)E) + 0.5f * (float)(acc[5] / (double)E);
-    const float lcls = (float)(acc[6] / ((double)nc * acc[7]));     // no positive cell: nan, as in loss_final_kernel
     if (box) {
         losses[0] = lambda * lx + lconf * lambda_conf + lcls * lambda_cls;
         losses[1] = lx; losses[2] = 0.f; losses[3] = 0.f; losses[4] = 0.f;
@@ -259,88 +241,53 @@ __global__ void loss_final_hyp_kernel(const double* __restrict__ acc, long E, in
     losses[7] = (float)acc[8];
 }
 
-size_t train_loss_box_workspace_bytes(int N, int fh, int fw, int na, int nc) { return train_loss_workspace_bytes(N, fh, fw, na, nc + 2); }
-
-size_t train_loss_workspace_bytes(int N, int fh, int fw, int na, int nc)
+size_t train_loss_workspace_bytes(int N, int fh, int fw, int na, int nc, int size_planes)
 {
-    return ((size_t)(LT_C0 + nc) * N * na * fh * fw) * sizeof(float) + 16 * sizeof(double) + 64;
+    return ((size_t)(LT_C0 + nc + 2 * size_planes) * N * na * fh * fw) * sizeof(float) + 16 * sizeof(double) + 64;
 }
 
-// box_kind < 0: the reference's loss in its own workspace (6 + nc planes).  0 .. 3: the box entry's workspace (8 + nc planes, gw and
-// gh written); 0 still runs the reference's terms, 1 .. 3 the IoU-family one.
-static void launch_loss(const float* head, int N, int fh, int fw, const float* anc, int na, int nc, const float* targets, int T, float ignore_thres,
-                        void* work, float* losses, float* grad, int box_kind, double lambda_box, hipStream_t s)
+// the forward pass over all cells, then (grad) the backward one, of one of the four (BOX, HYP) pairs
+template <bool BOX, bool HYP>
+static void launch_cells(const float* head, const float* dense, long E, int fh, int fw, int nc, double* acc, float* grad, const LossBoxHyp& lb,
+                         hipStream_t s)
 {
-    const long E = (long)N * na * fh * fw;
-    LossBox lb{};
-    LossAnchors& la = lb.anc;
-    for (int a = 0; a < na && a < LOSS_MAX_ANCHORS; ++a) { la.w[a] = anc[2 * a]; la.h[a] = anc[2 * a + 1]; }
-    lb.na = na; lb.kind = box_kind; lb.lambda = lambda_box;
-    double* acc = reinterpret_cast<double*>(work);                       // 16 doubles first (8-byte aligned), the dense planes behind
-    float* dense = reinterpret_cast<float*>(static_cast<char*>(work) + 16 * sizeof(double));
+    const typename LossArgs<HYP>::type& arg = lb;
     const unsigned nb = (unsigned)((E + 255) / 256);
-    const int sizes = box_kind >= 0;
-    hipLaunchKernelGGL(loss_init_kernel, dim3(nb), dim3(256), 0, s, dense, E, LT_C0 + nc + 2 * sizes, acc);
-    hipLaunchKernelGGL(loss_targets_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, s, targets, T, dense, E, N, fh, fw, la, na, nc,
-                       ignore_thres, acc, sizes);
-    if (box_kind > 0) {
-        hipLaunchKernelGGL((loss_cells_kernel<false, true>), dim3(nb), dim3(256), 0, s, head, dense, E, fh, fw, nc, acc, (float*)nullptr, lb);
-        if (grad) hipLaunchKernelGGL((loss_cells_kernel<true, true>), dim3(nb), dim3(256), 0, s, head, dense, E, fh, fw, nc, acc, grad, lb);
-        hipLaunchKernelGGL(loss_final_box_kernel, dim3(1), dim3(1), 0, s, acc, E, nc, (float)lambda_box, losses);
-    } else {
-        hipLaunchKernelGGL((loss_cells_kernel<false, false>), dim3(nb), dim3(256), 0, s, head, dense, E, fh, fw, nc, acc, (float*)nullptr, lb);
-        if (grad) hipLaunchKernelGGL((loss_cells_kernel<true, false>), dim3(nb), dim3(256), 0, s, head, dense, E, fh, fw, nc, acc, grad, lb);
-        hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(1), 0, s, acc, E, nc, losses);
-    }
+    hipLaunchKernelGGL((loss_cells_kernel<false, BOX, HYP>), dim3(nb), dim3(256), 0, s, head, dense, E, fh, fw, nc, acc, (float*)nullptr, arg);
+    if (grad) hipLaunchKernelGGL((loss_cells_kernel<true, BOX, HYP>), dim3(nb), dim3(256), 0, s, head, dense, E, fh, fw, nc, acc, grad, arg);
 }
 
+// spec.hyp: opt[8] = obj_pw, cls_pw, label_smoothing, fl_gamma, fl_alpha, obj_iou, lambda_conf, lambda_cls (validated by the entry).  With
+// every option neutral (or no options) the plain instantiations run: the same kernels as without options, hence the same bits.
 void launch_train_loss(const float* head, int N, int fh, int fw, const float* anc, int na, int nc, const float* targets, int T, float ignore_thres,
-                       void* work, float* losses, float* grad, hipStream_t s)
+                       void* work, float* losses, float* grad, const LossSpec& spec, hipStream_t s)
 {
-    launch_loss(head, N, fh, fw, anc, na, nc, targets, T, ignore_thres, work, losses, grad, -1, 0.0, s);
-}
-
-void launch_train_loss_box(const float* head, int N, int fh, int fw, const float* anc, int na, int nc, const float* targets, int T,
-                           float ignore_thres, void* work, float* losses, float* grad, int box_kind, double lambda_box, hipStream_t s)
-{
-    launch_loss(head, N, fh, fw, anc, na, nc, targets, T, ignore_thres, work, losses, grad, box_kind, lambda_box, s);
-}
-
-// opt[8] = obj_pw, cls_pw, label_smoothing, fl_gamma, fl_alpha, obj_iou, lambda_conf, lambda_cls (validated by the entry).  With every
-// option neutral this IS launch_train_loss_box: the same kernels, hence the same bits.
-void launch_train_loss_hyp(const float* head, int N, int fh, int fw, const float* anc, int na, int nc, const float* targets, int T,
-                           float ignore_thres, void* work, float* losses, float* grad, int box_kind, double lambda_box, const double* opt,
-                           hipStream_t s)
-{
-    const bool focal = opt[3] > 0.0;
-    LossHyp hp{};
-    hp.obj_pw = opt[0]; hp.cls_pw = opt[1]; hp.gamma = opt[3]; hp.alpha = opt[4]; hp.obj_iou = opt[5]; hp.lambda_conf = opt[6]; hp.lambda_cls = opt[7];
-    hp.cp = (float)(1.0 - 0.5 * opt[2]); hp.cn = (float)(0.5 * opt[2]);
-    hp.conf_plain = opt[0] == 1.0 && !focal && opt[5] == 0.0;
-    hp.cls_plain = opt[1] == 1.0 && !focal && opt[2] == 0.0;
-    if (hp.conf_plain && hp.cls_plain && opt[6] == 1.0 && opt[7] == 1.0) {
-        launch_loss(head, N, fh, fw, anc, na, nc, targets, T, ignore_thres, work, losses, grad, box_kind, lambda_box, s);
-        return;
-    }
     const long E = (long)N * na * fh * fw;
+    const bool box = spec.box_kind > 0;
+    const int sizes = spec.box_kind >= 0;
     LossBoxHyp lb{};
     for (int a = 0; a < na && a < LOSS_MAX_ANCHORS; ++a) { lb.anc.w[a] = anc[2 * a]; lb.anc.h[a] = anc[2 * a + 1]; }
-    lb.na = na; lb.kind = box_kind; lb.lambda = lambda_box; lb.hyp = hp;
-    double* acc = reinterpret_cast<double*>(work);
-    float* dense = reinterpret_cast<float*>(static_cast<char*>(work) + 16 * sizeof(double));
-    const unsigned nb = (unsigned)((E + 255) / 256);
-    hipLaunchKernelGGL(loss_init_kernel, dim3(nb), dim3(256), 0, s, dense, E, LT_C0 + nc + 2, acc);
-    hipLaunchKernelGGL(loss_targets_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, s, targets, T, dense, E, N, fh, fw, lb.anc, na, nc,
-                       ignore_thres, acc, 1);
-    if (box_kind > 0) {
-        hipLaunchKernelGGL((loss_cells_kernel<false, true, true>), dim3(nb), dim3(256), 0, s, head, dense, E, fh, fw, nc, acc, (float*)nullptr, lb);
-        if (grad) hipLaunchKernelGGL((loss_cells_kernel<true, true, true>), dim3(nb), dim3(256), 0, s, head, dense, E, fh, fw, nc, acc, grad, lb);
-    } else {
-        hipLaunchKernelGGL((loss_cells_kernel<false, false, true>), dim3(nb), dim3(256), 0, s, head, dense, E, fh, fw, nc, acc, (float*)nullptr, lb);
-        if (grad) hipLaunchKernelGGL((loss_cells_kernel<true, false, true>), dim3(nb), dim3(256), 0, s, head, dense, E, fh, fw, nc, acc, grad, lb);
+    lb.na = na; lb.kind = spec.box_kind; lb.lambda = spec.lambda_box;
+    bool plain = true;
+    float lambda_conf = 1.0f, lambda_cls = 1.0f;
+    if (const double* opt = spec.hyp) {
+        const bool focal = opt[3] > 0.0;
+        LossHyp& hp = lb.hyp;
+        hp.obj_pw = opt[0]; hp.cls_pw = opt[1]; hp.gamma = opt[3]; hp.alpha = opt[4]; hp.obj_iou = opt[5]; hp.lambda_conf = opt[6]; hp.lambda_cls = opt[7];
+        hp.cp = (float)(1.0 - 0.5 * opt[2]); hp.cn = (float)(0.5 * opt[2]);
+        hp.conf_plain = opt[0] == 1.0 && !focal && opt[5] == 0.0;
+        hp.cls_plain = opt[1] == 1.0 && !focal && opt[2] == 0.0;
+        plain = hp.conf_plain && hp.cls_plain && opt[6] == 1.0 && opt[7] == 1.0;
+        lambda_conf = (float)opt[6]; lambda_cls = (float)opt[7];
     }
-    hipLaunchKernelGGL(loss_final_hyp_kernel, dim3(1), dim3(1), 0, s, acc, E, nc, (int)(box_kind > 0), (float)lambda_box, (float)hp.lambda_conf,
-                       (float)hp.lambda_cls, losses);
+    double* acc = reinterpret_cast<double*>(work);                       // 16 doubles first (8-byte aligned), the dense planes behind
+    float* dense = reinterpret_cast<float*>(static_cast<char*>(work) + 16 * sizeof(double));
+    hipLaunchKernelGGL(loss_init_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, s, dense, E, LT_C0 + nc + 2 * sizes, acc);
+    hipLaunchKernelGGL(loss_targets_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, s, targets, T, dense, E, N, fh, fw, lb.anc, na, nc,
+                       ignore_thres, acc, sizes);
+    if (plain) (box ? launch_cells<true, false> : launch_cells<false, false>)(head, dense, E, fh, fw, nc, acc, grad, lb, s);
+    else       (box ? launch_cells<true, true> : launch_cells<false, true>)(head, dense, E, fh, fw, nc, acc, grad, lb, s);
+    hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(1), 0, s, acc, E, nc, (int)box, (float)spec.lambda_box, lambda_conf, lambda_cls, losses);
 }
 
 }  // namespace yf

@@ -3,7 +3,7 @@
     model.train()
     optimizer.zero_grad()
     pred = model(imgs)                                   # train-mode forward: BatchNorm on batch statistics, running stats updated
-    loss = sum(model_loss[i](pred[i], targets)[0] ...)   # validation.YOLOLossV3 (yf_train_loss)
+    loss = sum(model_loss[i](pred[i], targets)[0] ...)   # validation.YOLOLossV3 (yf_train_head_loss_ex / _box / _hyp)
     loss.backward()                                      # backward of every layer -> param.grad
     optimizer.step()                                     # training.Adam / training.SGD (yf_train_opt_multi_pinned) -- or any torch optimizer
     ema.update(model)                                    # opt-in, yolov5's: training.ModelEMA, inside the optimizer's launch (step(ema=...))

@@ -2,7 +2,7 @@
   `YOLOLossV3(anchors, num_classes, input_shape, device)(input)`   src/model_training/loss/yolo_loss.py:27-141 (decode branch)
   `non_max_suppression(prediction, num_classes, conf_thres, nms_thres)`   src/model_training/utils/general.py:87-143
 With targets, `YOLOLossV3(...)(input, targets)` is the reference's TRAINING loss of that head (yolo_loss.py:70-97, :144-196) with an
-analytic backward to the head tensor (yf_train_loss; SURVEY.md 8(f).4, first slice -- the layers' backward is not built).  All need an engine handle (it carries the device; the decode also needs
+analytic backward to the head tensor (yf_train_head_loss_ex, or yf_train_head_loss_box / _hyp with the opt-in options; SURVEY.md 8(f).4, first slice -- the layers' backward is not built).  All need an engine handle (it carries the device; the decode also needs
 H and W, which come from `input_shape`).  The model is passed explicitly (`model=` / `loss.model = m`); `bind(model)` sets the
 default used when none is given.  The engine is chosen by (H, W, device of the tensor) -- never "whichever exists"."""
 import ctypes
@@ -116,7 +116,8 @@ class YOLOLossV3(torch.nn.Module):
 
 
 class _TrainLossFn(torch.autograd.Function):
-    """total loss of one head with its analytic gradient (yf_train_loss): `loss.backward()` reaches the head tensor."""
+    """total loss of one head with its analytic gradient (yf_train_head_loss_ex, _box with `box_loss`, _hyp with
+    a non-neutral option): `loss.backward()` reaches the head tensor."""
 
     @staticmethod
     def forward(ctx, x, targets, loss_mod):
@@ -130,30 +131,24 @@ class _TrainLossFn(torch.autograd.Function):
         hyp = loss_mod.loss_hyp
         if all(v == d for v, (name, d) in zip(hyp, LOSS_HYP_DEFAULTS) if name != "fl_alpha"):
             hyp = None                                       # every option neutral: exactly the entries below
+        # the workspace size, the entry and what it takes behind the stream
         if hyp is not None:
-            _lib.check(lib.yf_train_head_loss_hyp_workspace_bytes(bs, fh, fw, na, nc, ctypes.byref(need)))
+            size_fn, loss_fn = lib.yf_train_head_loss_hyp_workspace_bytes, lib.yf_train_head_loss_hyp
+            tail = (BOX_KINDS[box] if box else 0, loss_mod.lambda_box) + tuple(hyp)
         elif box is None:
-            _lib.check(lib.yf_train_head_loss_workspace_bytes_ex(bs, fh, fw, na, nc, ctypes.byref(need)))
+            size_fn, loss_fn, tail = lib.yf_train_head_loss_workspace_bytes_ex, lib.yf_train_head_loss_ex, ()
         else:
-            _lib.check(lib.yf_train_head_loss_box_workspace_bytes(bs, fh, fw, na, nc, ctypes.byref(need)))
+            size_fn, loss_fn = lib.yf_train_head_loss_box_workspace_bytes, lib.yf_train_head_loss_box
+            tail = (BOX_KINDS[box], loss_mod.lambda_box)
+        _lib.check(size_fn(bs, fh, fw, na, nc, ctypes.byref(need)))
         work = torch.empty((need.value + 7) // 8, dtype=torch.float64, device=x.device)     # 8-byte aligned scratch
         losses = torch.empty(8, dtype=torch.float32, device=x.device)
         grad = torch.empty_like(x)
         anc = (ctypes.c_double * (2 * na))(*[float(v) for a in loss_mod.anchors for v in a[:2]])
         stream = torch.cuda.current_stream(x.device).cuda_stream
-        if hyp is not None:
-            _lib.check(lib.yf_train_head_loss_hyp(dev_index, H, W, x.data_ptr(), bs, fh, fw, anc, na, nc, targets.data_ptr(), targets.shape[1],
-                                                  float(loss_mod.ignore_threshold), work.data_ptr(), work.numel() * 8, losses.data_ptr(),
-                                                  grad.data_ptr(), ctypes.c_void_p(stream), BOX_KINDS[box] if box else 0, loss_mod.lambda_box,
-                                                  *hyp))
-        elif box is None:
-            _lib.check(lib.yf_train_head_loss_ex(dev_index, H, W, x.data_ptr(), bs, fh, fw, anc, na, nc, targets.data_ptr(), targets.shape[1],
-                                                 float(loss_mod.ignore_threshold), work.data_ptr(), work.numel() * 8, losses.data_ptr(),
-                                                 grad.data_ptr(), ctypes.c_void_p(stream)))
-        else:
-            _lib.check(lib.yf_train_head_loss_box(dev_index, H, W, x.data_ptr(), bs, fh, fw, anc, na, nc, targets.data_ptr(), targets.shape[1],
-                                                  float(loss_mod.ignore_threshold), work.data_ptr(), work.numel() * 8, losses.data_ptr(),
-                                                  grad.data_ptr(), ctypes.c_void_p(stream), BOX_KINDS[box], loss_mod.lambda_box))
+        _lib.check(loss_fn(dev_index, H, W, x.data_ptr(), bs, fh, fw, anc, na, nc, targets.data_ptr(), targets.shape[1],
+                           float(loss_mod.ignore_threshold), work.data_ptr(), work.numel() * 8, losses.data_ptr(), grad.data_ptr(),
+                           ctypes.c_void_p(stream), *tail))
         ctx.save_for_backward(grad)
         ctx.mark_non_differentiable(losses)
         return losses[0].clone(), losses
