@@ -507,8 +507,8 @@ int yf_preprocess_u8(yf_handle h, const uint8_t *d_u8, int N, int src_h, int src
  *     first kernel's loads -- bit-identical to yf_preprocess_u8 followed by yf_forward, one pass and 3-15 bytes per pixel less HBM traffic;
  *   any other size: one extra pass (yf_cv_preprocess_u8: cv::resize's 8-bit INTER_LINEAR) into net-sized u8 frames at the end of the
  *     workspace, then the fused entry.  The first call for a new source size builds cv::resize's coefficient tables with one small
- *     kernel on `stream` (round 6: no allocation or host synchronisation on this path -- the first resize of an engine allocates the table
- *     pool once; 32 distinct source sizes are kept, a 33rd evicts behind a device synchronisation). */
+ *     kernel on `stream` (no allocation or host synchronisation on this path -- yf_create_ex allocates the table pool; 32 distinct
+ *     source sizes are kept, a 33rd evicts behind a device synchronisation).  Stream capture: the rules at yf_cv_preprocess_u8. */
 int yf_forward_u8(yf_handle h, const uint8_t *d_u8, int N, int src_h, int src_w, float *d_head_large, float *d_head_small,
                   void *d_workspace, size_t workspace_bytes, void *stream);
 
@@ -519,11 +519,22 @@ int yf_forward_u8(yf_handle h, const uint8_t *d_u8, int N, int src_h, int src_w,
  * OpenCV's published 8-bit arithmetic is restated: gray = (B*BY + G*GY + R*RY + half) >> shift with gray_bits 15 (9798/19235/3735: OpenCV 4.x;
  * 0 means 15) or 14 (4899/9617/1868: OpenCV 2.x / 3.x); resize with 11-bit coefficients, dst = (((b0*(r0>>4))>>16) + ((b1*(r1>>4))>>16) + 2) >> 2.
  * Bit-exact against oracle/cv_oracle.py; parity with an actual OpenCV build is UNPINNED (cv2 is not available where this was built, and an
- * IPP / vendor-HAL build may round differently). */
+ * IPP / vendor-HAL build may round differently).
+ *
+ * Stream capture (this entry, yf_forward_bgr_u8 and yf_forward_u8 at a source size that is neither the net's nor twice it).  The resize
+ * reads per-size coefficient tables out of a pool of 32 slots that the engine owns (allocated and zeroed by yf_create_ex).  A table is
+ * built only by an EAGER call; under capture the call refers to a table that exists:
+ *   - the first sight of a source size while `stream` is capturing returns YF_E_INVALID ("run once eagerly at this source size before
+ *     capturing") and changes nothing: nothing is launched, no slot is taken, the capture stays valid;
+ *   - a size seen before is captured once its eager build has finished on the device -- synchronise with that call's stream before the
+ *     capture begins; a build still in flight returns YF_E_INVALID -- and its slot is PINNED for the engine's lifetime, because the graph
+ *     keeps the slot's addresses.  Replays and eager calls at that size may then be mixed freely, from any stream;
+ *   - the 33rd distinct size evicts the least recently used UNPINNED slot; with all 32 slots pinned a new size returns YF_E_INVALID. */
 int yf_cv_preprocess_u8(yf_handle h, const uint8_t *d_src, int N, int src_h, int src_w, int src_c, int gray_bits, uint8_t *d_dst, void *stream);
 
 /* yf_forward on cv2.imread's frames (uint8 [N,src_h,src_w,3], BGR) of any size: yf_cv_preprocess_u8 + the fused (v-128)/255 entry.  What
- * `Detect_YOLO.batch_detect` does per image (detect.py:108-127, 152), batched.  A 3-channel net: identical to yf_forward_u8. */
+ * `Detect_YOLO.batch_detect` does per image (detect.py:108-127, 152), batched.  A 3-channel net: identical to yf_forward_u8.
+ * Stream capture: yf_cv_preprocess_u8's rules (a source size is run once eagerly before it is captured). */
 int yf_forward_bgr_u8(yf_handle h, const uint8_t *d_bgr, int N, int src_h, int src_w, int gray_bits, float *d_head_large, float *d_head_small,
                       void *d_workspace, size_t workspace_bytes, void *stream);
 

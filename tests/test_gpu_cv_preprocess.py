@@ -197,3 +197,96 @@ def test_cv_preprocess_argument_errors(yf, gray_model, dev, golden):
     m3, io3 = _rgb_model(yf, dev, golden)
     with pytest.raises(RuntimeError, match="cannot take"):
         m3.cv_preprocess_u8(torch.zeros((1, 8, 8), dtype=torch.uint8, device=dev), io3["input_shape"])
+
+
+# ---- resize tables and captured graphs (the rules are in include/yolo_fastest_hip.h at yf_cv_preprocess_u8) -----------------------
+
+def _fresh_gray_model(yf, dev):
+    """An engine of its own: the tests below count on which sizes it has seen."""
+    io = yf.io_params_for(256)
+    m = yf.YoloFastest(io).to(dev).eval()
+    m.load_state_dict(torch.load(WEIGHTS[256], map_location=dev))
+    m.engine(256, 320, 1, dev)                 # the engine exists before anything is captured
+    return m, io
+
+
+def _want(g):
+    from oracle import cv_oracle as cv
+    return np.stack([cv.resize_linear_u8(f, (320, 256)) for f in g])
+
+
+def _capture(m, io, x):
+    """cv_preprocess_u8(x) captured on torch's capture stream -> (graph, the tensor every replay writes)."""
+    graph = torch.cuda.CUDAGraph()
+    keep = torch.zeros(16, dtype=torch.uint8, device=x.device)
+    with torch.cuda.graph(graph):
+        keep.add_(1)                           # (a graph with a node of its own, whatever the engine does)
+        out = m.cv_preprocess_u8(x, io["input_shape"])
+    return graph, out
+
+
+def test_capture_as_first_sight_of_a_size_is_refused_and_changes_nothing(yf, dev):
+    """A captured build kernel has not run: the slot it claimed would be read unwritten by the next eager call at that size.  So the first
+    sight of a size under capture is a clean error; the engine is as before (another size stays exact, the refused size is built by the
+    eager call that follows, and is then capturable)."""
+    m, io = _fresh_gray_model(yf, dev)
+    rng = np.random.default_rng(61)
+    other = rng.integers(0, 256, (2, 90, 130), dtype=np.uint8)
+    g = rng.integers(0, 256, (2, 123, 211), dtype=np.uint8)
+    xo, x = torch.from_numpy(other).to(dev), torch.from_numpy(g).to(dev)
+    assert np.array_equal(m.cv_preprocess_u8(xo, io["input_shape"]).cpu().numpy(), _want(other))
+    torch.cuda.synchronize(dev)
+    with pytest.raises(RuntimeError, match="run once eagerly at this source size before capturing"):
+        _capture(m, io, x)
+    torch.cuda.synchronize(dev)
+    assert np.array_equal(m.cv_preprocess_u8(xo, io["input_shape"]).cpu().numpy(), _want(other))
+    assert np.array_equal(m.cv_preprocess_u8(x, io["input_shape"]).cpu().numpy(), _want(g))
+    torch.cuda.synchronize(dev)
+    graph, out = _capture(m, io, x)
+    graph.replay()
+    torch.cuda.synchronize(dev)
+    assert np.array_equal(out.cpu().numpy(), _want(g))
+
+
+def test_a_captured_size_keeps_its_tables_through_40_other_sizes(yf, dev):
+    """A graph keeps the addresses of its slot.  Eager once, capture, then 40 other sizes (the pool holds 32: the oldest unpinned are evicted),
+    then a replay on new pixels: still exact; all 40 sizes and the first one are exact again afterwards."""
+    m, io = _fresh_gray_model(yf, dev)
+    rng = np.random.default_rng(62)
+    g0 = rng.integers(0, 256, (2, 333, 217), dtype=np.uint8)
+    x = torch.from_numpy(g0).to(dev)
+    assert np.array_equal(m.cv_preprocess_u8(x, io["input_shape"]).cpu().numpy(), _want(g0))
+    torch.cuda.synchronize(dev)
+    graph, out = _capture(m, io, x)
+    others = []
+    for k in range(40):
+        g = rng.integers(0, 256, (1, 40 + 3 * k, 50 + 5 * k), dtype=np.uint8)
+        others.append((g, _want(g)))
+        assert np.array_equal(m.cv_preprocess_u8(torch.from_numpy(g).to(dev), io["input_shape"]).cpu().numpy(), others[-1][1]), g.shape
+    g1 = rng.integers(0, 256, g0.shape, dtype=np.uint8)
+    x.copy_(torch.from_numpy(g1).to(dev))
+    graph.replay()
+    torch.cuda.synchronize(dev)
+    assert np.array_equal(out.cpu().numpy(), _want(g1))
+    for g, want in others:
+        assert np.array_equal(m.cv_preprocess_u8(torch.from_numpy(g).to(dev), io["input_shape"]).cpu().numpy(), want), g.shape
+    assert np.array_equal(m.cv_preprocess_u8(torch.from_numpy(g0).to(dev), io["input_shape"]).cpu().numpy(), _want(g0))
+    graph.replay()
+    torch.cuda.synchronize(dev)
+    assert np.array_equal(out.cpu().numpy(), _want(g1))
+
+
+def test_eager_call_between_capture_and_first_replay(yf, dev):
+    """Capture, no replay, then an eager call at the same size (this read indices nobody had written), then the replay."""
+    m, io = _fresh_gray_model(yf, dev)
+    rng = np.random.default_rng(63)
+    g0 = rng.integers(0, 256, (3, 77, 301), dtype=np.uint8)
+    x = torch.from_numpy(g0).to(dev)
+    assert np.array_equal(m.cv_preprocess_u8(x, io["input_shape"]).cpu().numpy(), _want(g0))
+    torch.cuda.synchronize(dev)
+    graph, out = _capture(m, io, x)
+    g1 = rng.integers(0, 256, g0.shape, dtype=np.uint8)
+    assert np.array_equal(m.cv_preprocess_u8(torch.from_numpy(g1).to(dev), io["input_shape"]).cpu().numpy(), _want(g1))
+    graph.replay()
+    torch.cuda.synchronize(dev)
+    assert np.array_equal(out.cpu().numpy(), _want(g0))

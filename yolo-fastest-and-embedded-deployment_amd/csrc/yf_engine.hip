@@ -148,10 +148,11 @@ struct yf_engine {
     hipEvent_t ev_probe[3] = {nullptr, nullptr, nullptr};
     size_t head_l_elems = 0, head_s_elems = 0;
     // cv::resize's per-column / per-row tables of the source sizes seen so far (cv_tables; a handful per engine, LRU)
-    // one pool of CV_SLOTS x (W + H) entries, allocated at the first resize; a slot is built by a kernel on the caller's stream (no host
-    // synchronisation, capturable) and guarded by an event for callers on another stream
+    // one pool of CV_SLOTS x (W + H) entries, allocated and zeroed by yf_create_ex with the slots' events (an entry nobody built indexes
+    // inside the frame); a slot is built by a kernel on the caller's stream, eagerly only (no host synchronisation), and guarded by an event
+    // for callers on another stream.  A captured graph keeps its slot's addresses: a hit while capturing pins the slot for the engine's lifetime
     enum { CV_SLOTS = 32 };
-    struct CvTab { int sh = 0, sw = 0; bool built = false; hipStream_t stream = nullptr; hipEvent_t ready = nullptr; long used = 0; } cvtab[CV_SLOTS];
+    struct CvTab { int sh = 0, sw = 0; bool built = false, pinned = false; hipStream_t stream = nullptr; hipEvent_t ready = nullptr; long used = 0; } cvtab[CV_SLOTS];
     int4* d_cvpool = nullptr;
     // post_split_kernel (dense frames: one workgroup per frame AND class) writes one scratch row per (frame, class), which post_assemble_kernel
     // concatenates in a second launch; grown on demand
@@ -1004,6 +1005,15 @@ int yf_create_ex(const void* blob, size_t nbytes, int H, int W, int max_batch, i
             return fail(YF_E_HIP, "hipStreamCreate/hipEventCreate (branch) failed");
         }
     }
+    {   // cv_tables' pool, zeroed (an entry nobody built reads pixel 0 with weight 0), and its slots' events: nothing is allocated on the call path
+        const size_t bytes = (size_t)yf_engine::CV_SLOTS * ((size_t)W + H) * sizeof(int4);
+        bool ok = hipMalloc(&e->d_cvpool, bytes) == hipSuccess && hipMemset(e->d_cvpool, 0, bytes) == hipSuccess;
+        for (auto& t : e->cvtab) ok = ok && hipEventCreateWithFlags(&t.ready, hipEventDisableTiming) == hipSuccess;
+        if (!ok || hipDeviceSynchronize() != hipSuccess) {
+            (void)yf_destroy(e);
+            return fail(YF_E_HIP, "hipMalloc / hipMemset / hipEventCreate (resize tables) failed");
+        }
+    }
     *out = e;
     return YF_OK;
 }
@@ -1155,29 +1165,49 @@ static int u8_mode(yf_handle h, int src_h, int src_w, int* down2)
 // cv::resize(INTER_LINEAR, 8-bit) reads per-column / per-row tables (yf_cv_kernels.hip: cv_tables_kernel).  A source size seen before costs
 // nothing; a new one costs ONE small kernel on the caller's stream into a free slot of the engine's pool -- no hipMalloc / hipFree / synchronous
 // copy on the hot path (the 4-slot host-built version paid a device-wide hipFree + 2 hipMalloc + 2 blocking hipMemcpy per evicted
-// size and could not run under stream capture).  Only the 33rd distinct size evicts, behind a device synchronisation (the evicted tables may
-// still be read by earlier launches on other streams).
+// size and could not run under stream capture; the pool and the events are yf_create_ex's).  Only the 33rd distinct size evicts, behind a
+// device synchronisation (the evicted tables may still be read by earlier launches on other streams).
+// Under stream capture nothing is built: a captured build kernel has not run, so a slot it "built" would be read unwritten by
+// the next eager call, and an event recorded in a capture cannot be waited for outside it.  A miss while capturing is refused; a hit is
+// taken only once its eager build has FINISHED (the replay is ordered behind nothing but its own launch) and pins the slot, whose addresses
+// the graph keeps: eviction chooses among unpinned slots.
 static int cv_tables(yf_engine* e, int sh, int sw, const int4** dx, const int4** dy, hipStream_t s)
 {
     const size_t per = (size_t)e->W + e->H;
-    if (!e->d_cvpool) HIP_OK(hipMalloc(&e->d_cvpool, (size_t)yf_engine::CV_SLOTS * per * sizeof(int4)));
-    int hit = -1, free_slot = -1, lru = 0;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    const bool capturing = hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone;
+    int hit = -1, free_slot = -1, lru = -1;
     for (int i = 0; i < yf_engine::CV_SLOTS; ++i) {
         auto& t = e->cvtab[i];
         if (t.built && t.sh == sh && t.sw == sw) { hit = i; break; }
         if (!t.built && free_slot < 0) free_slot = i;
-        if (t.used < e->cvtab[lru].used) lru = i;
+        if (!t.pinned && (lru < 0 || t.used < e->cvtab[lru].used)) lru = i;
     }
     int k = hit;
     if (hit < 0) {
+        if (capturing)
+            return fail(YF_E_INVALID, "the caller's stream is capturing and the resize tables of %dx%d source frames are not built yet: "
+                                      "run once eagerly at this source size before capturing", sh, sw);
         k = free_slot >= 0 ? free_slot : lru;
+        if (k < 0)
+            return fail(YF_E_INVALID, "all %d resize-table slots are pinned by captured graphs: no room for %dx%d source frames",
+                        (int)yf_engine::CV_SLOTS, sh, sw);
         auto& t = e->cvtab[k];
         if (free_slot < 0) HIP_OK(hipDeviceSynchronize());
-        if (!t.ready) HIP_OK(hipEventCreateWithFlags(&t.ready, hipEventDisableTiming));
         yf::launch_cv_tables(sh, sw, e->H, e->W, e->d_cvpool + k * per, e->d_cvpool + k * per + e->W, s);
         HIP_OK(hipGetLastError());
         HIP_OK(hipEventRecord(t.ready, s));
         t.sh = sh; t.sw = sw; t.built = true; t.stream = s;
+    } else if (capturing) {
+        hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;     // a query is no part of the capture: not to be held against a global-mode one
+        HIP_OK(hipThreadExchangeStreamCaptureMode(&mode));
+        const hipError_t q = hipEventQuery(e->cvtab[k].ready);
+        HIP_OK(hipThreadExchangeStreamCaptureMode(&mode));
+        if (q == hipErrorNotReady)
+            return fail(YF_E_INVALID, "the caller's stream is capturing and the resize tables of %dx%d source frames are still being built: "
+                                      "synchronise with the eager call at this source size before capturing", sh, sw);
+        HIP_OK(q);
+        e->cvtab[k].pinned = true;
     } else if (e->cvtab[k].stream != s) {
         HIP_OK(hipStreamWaitEvent(s, e->cvtab[k].ready, 0));
     }

@@ -165,6 +165,16 @@ void launch_tconv_bwd_data(const float* dy, const float* w, float* dx, int N, in
     }
     hipLaunchKernelGGL(tconv_bwd_data_kernel, dim3(nblk((long)N * Cin * H * W)), dim3(256), 0, s, dy, w, dx, N, Cin, H, W, Cout, Ho, Wo, k, stride, depthwise);
 }
+// zeros in front of the atomics fallbacks of the weight gradients, as a KERNEL: a hipMemsetAsync captured into a pass graph (the trainer
+// replays its passes as graphs) came back wrong on replay -- a quarter of such a gradient's elements held garbage of 1e13 .. 1e34, another
+// layer's every time, while the same launches issued plainly were exact (tests/test_gpu_poison_train.py found it at 64x96 and 96x160, whose
+// stride-32 maps have H * W % 4 != 0).  A kernel node is ordered with its neighbours like every other launch of the pass.
+__global__ void __launch_bounds__(256) tzero_kernel(float* __restrict__ p, long n)
+{
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) p[i] = 0.f;
+}
+static inline void tzero(float* p, long n, hipStream_t s) { hipLaunchKernelGGL(tzero_kernel, dim3(nblk(n)), dim3(256), 0, s, p, n); }
 // waves per workgroup of the weight-gradient GEMM: fill the chip (>= 16 waves per CU) when the slab limit keeps the grid small and a
 // slice is long enough to deal out
 static inline int twgrad_waves(long workgroups, long q_per)
@@ -326,7 +336,7 @@ void launch_tconv_bwd_weight(const float* x, const float* dy, float* dw, int N, 
         tsum_finish(out, scratch, chunks, nw, dw, s, defer);
         return;
     }
-    (void)hipMemsetAsync(dw, 0, (size_t)nw * sizeof(float), s);        // the fallbacks below accumulate with atomics
+    tzero(dw, nw, s);                                                  // the fallbacks below accumulate with atomics
     if (!depthwise) {
         const int R = Cin * k * k, tiles = ((R + 63) / 64) * ((Cout + 63) / 64);
         long nsplit = (P + 255) / 256;                                  // >= 8 staged tiles per workgroup ...
@@ -433,7 +443,7 @@ void launch_tdeconv_bwd_weight(const float* x, const float* dy, float* dw, int N
     }
     int nchunk = (int)((P + 4095) / 4096);
     while ((long)nchunk * nw > 262144 && nchunk > 1) nchunk /= 2;
-    (void)hipMemsetAsync(dw, 0, (size_t)nw * sizeof(float), s);
+    tzero(dw, nw, s);
     hipLaunchKernelGGL(tdeconv_bwd_weight_kernel, dim3((unsigned)(nw * nchunk)), dim3(256), 0, s, x, dy, dw, N, Cin, H, W, Cout, nchunk);
 }
 // one scratch for the split reductions of a stream: BatchNorm partial pairs (256 KB) or weight-gradient slabs (all of it)
