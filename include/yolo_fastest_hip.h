@@ -801,6 +801,63 @@ int yf_set_fusion(yf_handle h, int level);        /* 2 (default) = block-fused k
                                                      conv4_1_1 one launch); 1 = block-fused kernels (bitwise the same heads);
                                                      0 = one launch per layer, every named tensor probe-able (bring-up / parity) */
 
+/* yolov5's autoanchor (utils/autoanchor.py: check_anchors' metric, kmean_anchors' anchor_fitness and its evolution loop) on label shapes
+ * that stay on the device.  Not in the reference.  No engine; anchors.py is the caller.
+ *   wh float32 [n,2]: label (w, h) in net-input pixels, each in [0, 2^15).  k float32 [A,2]: anchors, finite and positive.
+ *   thr in [1, 256]; t = (float)(1.0 / thr) -- torch compares its float32 tensor with the Python scalar 1 / thr in float32.
+ *   Metric, per (label, anchor), all IEEE float32: rw = w / aw, rh = h / ah, x = min(min(rw, 1 / rw), min(rh, 1 / rh)); best = the max of
+ *       x over the anchors.  1 / r is a second correctly rounded division of the QUOTIENT: aw / w and w * (1 / aw) round differently and
+ *       are not the rule.  A zero side gives x = 0.
+ *   Sums, exact integers, so that nothing depends on the order of execution:
+ *       cnt_best = #{labels: best > t};   cnt_x = sum over labels of #{anchors: x > t};
+ *       fit = sum over the labels with best > t of best * 2^(23+m), m the smallest integer with 2^-m <= t (m <= 8).  A float32 at or
+ *       above 2^-m is an integer multiple of 2^-(23+m), so every term is an exact integer <= 2^31 and, n being an int, the sum fits 64 bits.
+ *       yolov5's bpr = cnt_best / n, aat = cnt_x / n, anchor_fitness = fit / (n * 2^(23+m)) -- yolov5 forms that mean in float32, and
+ *       its value depends on torch's summation order; DECISIONS here compare the integer fit only.
+ *   Evolution, yolov5's loop with the mutation table as an INPUT: k float64 [A,2], f = fit((float)k).  For g = 0 .. gen-1 in turn:
+ *       kg = max(k * v[g], 2.0) in double, fg = fit((float)kg); if fg > f (strict) then k = kg, f = fg.  The entry scores
+ *       YF_ANCHOR_BATCH consecutive generations against the current k in one pass over the labels and accepts the FIRST that improves;
+ *       the generations behind it are scored again against the new k in the next pass, so k, f and the accepted set are exactly the
+ *       sequential chain's.
+ *   k-means -- this library's definition, not scipy's (whose sequential float32 means a parallel sum cannot reproduce):
+ *       q int32 [n,2] = rint(wh * 64), quantised once by the caller; s = two doubles, the float32 wh.std(0) yolov5 whitens by.  An
+ *       observation is o = ((double)q / 64.0) / s; the squared distance to a centroid c is (o_w - c_w)^2 + (o_h - c_h)^2 in double, every
+ *       operation rounded on its own; a label goes to the nearest centroid, the lowest index on ties.  Per cluster the exact 64-bit
+ *       sums of q_w, q_h and the count are kept; the new centroid is ((double)sum / (64.0 * count)) / s.  Restart r starts from the
+ *       observations of the label rows init[r][0..A).  All R restarts run in lock step, one pass over the labels per iteration.  A
+ *       restart stops after the pass whose (sums, count) triples all equal those of its previous pass, or after max_iter passes; its
+ *       centroids are those of its last pass' sums, and iters_out[r] = the passes it ran.  A restart that ever has an empty cluster, or
+ *       whose de-whitened centroids (float)(c * s) are not all finite and positive, is discarded: iters_out[r] = -1.  The winner is
+ *       the surviving restart whose de-whitened centroids have the greatest fit, the earliest on ties (yolov5 lets scipy pick by
+ *       distortion instead); k_out = its c * s in double, not sorted.  winner_out = -1 when no restart survives; k_out is then not written.
+ *   yf_anchor_metric: S anchor sets d_anchors float32 [S,A,2] in one launch; d_out uint64 [S,3] = (fit, cnt_best, cnt_x) per set.
+ *       Stream-ordered, no allocation, no synchronisation.
+ *   yf_anchor_evolve: k0, v, k_out, fit_out and accepted_out (int32 [gen]: 1 where generation g was accepted, else 0; may be NULL) are HOST
+ *       memory; d_work: yf_anchor_evolve_work_bytes(A) bytes of device scratch, 8-byte aligned.  It SYNCHRONISES on `stream` once per pass
+ *       (1 + at most gen passes; about a tenth of gen on yolov5's draws) and must not be called inside a stream capture.
+ *   yf_anchor_kmeans: s, init (int32 [R,A], label rows), k_out, winner_out, iters_out (int32 [R]) are HOST memory; d_wh = the same labels
+ *       as float32, for the winner's fit; d_work: yf_anchor_kmeans_work_bytes(R, A) bytes, 8-byte aligned.  It synchronises once per
+ *       iteration and once for the fit.
+ *   The kernels hold one label per lane and the candidates in LDS; partial sums cross workgroups as 64-bit integer vector atomics on
+ *   accumulators the entry zeroes in-stream.  No workgroup waits on another; the launch boundary is the only exchange.
+ *   YF_E_INVALID before any launch: a null pointer, n < 1, A < 1 or > YF_ANCHOR_MAX_A, S < 1, R < 1, S * A or R * A or YF_ANCHOR_BATCH * A
+ *   above 1024, thr outside [1, 256] or NaN, gen < 1, max_iter < 1, an init row outside [0, n), s or an anchor of k0 not finite and positive,
+ *   a mutation factor that is not finite; YF_E_WORKSPACE: work_bytes below the helper's value (the helpers return 0 for arguments refused
+ *   here).  Arrays that live on the device cannot be inspected without a synchronisation: yf_anchor_check_host checks HOST copies --
+ *   wh float32 [n,2] (n may be 0), anchors float32 [num_anchors,2] (may be 0) -- and returns YF_E_INVALID for a label side that is
+ *   negative, not finite or >= 2^15 and for an anchor side that is not finite and positive; anchors.py calls it before every upload.
+ *   Values it would refuse make the sums meaningless but no access out of bounds. */
+#define YF_ANCHOR_BATCH 32   /* generations yf_anchor_evolve scores per pass */
+#define YF_ANCHOR_MAX_A 32   /* anchors per set */
+int yf_anchor_check_host(const float *wh, int n, const float *anchors, int num_anchors);
+int yf_anchor_metric(int device, const float *d_wh, int n, const float *d_anchors, int S, int A, double thr, uint64_t *d_out, void *stream);
+size_t yf_anchor_evolve_work_bytes(int A);
+int yf_anchor_evolve(int device, const float *d_wh, int n, const double *k0, const double *v, int A, int gen, double thr, void *d_work,
+                     size_t work_bytes, double *k_out, uint64_t *fit_out, int32_t *accepted_out, void *stream);
+size_t yf_anchor_kmeans_work_bytes(int R, int A);
+int yf_anchor_kmeans(int device, const int32_t *d_q, int n, const double *s, const int32_t *init, int R, int A, int max_iter, double thr,
+                     const float *d_wh, void *d_work, size_t work_bytes, double *k_out, int32_t *winner_out, int32_t *iters_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,7 @@ YF_OPT_ADAM, YF_OPT_SGD, YF_OPT_MAX_GROUPS, YF_OPT_TABLE_ENTRY_BYTES = 0, 1, 8, 
 YF_OPT_EMA_TABLE_ENTRY_BYTES, YF_EMA_TABLE_ENTRY_BYTES = 64, 32                        # yf_train_opt_ema_multi_pinned, yf_train_ema_multi_pinned
 YF_LB_TABLE_ENTRY_BYTES, YF_LB_MAX_SIDE = 40, 8192                                     # yf_cv_letterbox_u8
 YF_VAL_NMS_V5_LDS_BUDGET, YF_VAL_NMS_V5_LDS_STATIC = 163840, 256                       # yf_val_nms_v5: where an image's key table sits
+YF_ANCHOR_BATCH, YF_ANCHOR_MAX_A = 32, 32                                              # yf_anchor_evolve: generations per pass; anchors per set
 
 
 class OptGroup(_c.Structure):
@@ -183,6 +184,14 @@ _SIGS = {
     "yf_op_dispatches": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(_c.c_int)]),
     "yf_post_dispatches": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(_c.c_int)]),
     "yf_profile_head_offsets": (_c.c_int, [_c.c_void_p, _c.c_int, _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_size_t)]),
+    "yf_anchor_check_host": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int]),
+    "yf_anchor_metric": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_double, _c.c_void_p, _c.c_void_p]),
+    "yf_anchor_evolve_work_bytes": (_c.c_size_t, [_c.c_int]),
+    "yf_anchor_evolve": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_double, _c.c_void_p,
+                                    _c.c_size_t, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),   # ... k0, v (host), A, gen, thr, work, k_out, fit_out, accepted_out
+    "yf_anchor_kmeans_work_bytes": (_c.c_size_t, [_c.c_int, _c.c_int]),
+    "yf_anchor_kmeans": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_double,
+                                    _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
 }
 EXPORTS = tuple(_SIGS)
 _lib = None

@@ -897,7 +897,8 @@ LOSS_HYP_KEYS = {"obj": "lambda_conf", "cls": "lambda_cls", "obj_pw": "obj_pw", 
 
 
 def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, logger=None, val_match="host", optimizer=None,
-          branch_weight=False, ema=False, box_loss=None, lambda_box=5.0, val_metrics=False, val_nms="reference", loss_hyp=None):
+          branch_weight=False, ema=False, box_loss=None, lambda_box=5.0, val_metrics=False, val_nms="reference", loss_hyp=None,
+          autoanchor=False):
     """The reference's `train(params, device, tbwriter)` (train.py:44-160) with the iteration on the GPU kernels of this package.
     Same control flow and arithmetic: one YOLOLossV3 per stride (:50-53), the model from `pretrained_pth` or initialize_weights()
     (:58-65), DataLoader(batch_size, drop_last, shuffle) (:71-73), Adam(lr0, betas (0.9, 0.999), eps 1e-8) (:84), the cosine
@@ -939,6 +940,13 @@ def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, l
     state-dict to `YOLO-Fastest_best.pth` whenever the fitness (0.1 mAP@.5 + 0.9 mAP@.5:.95) strictly improves.  With False none of it runs.
     `val_nms` is get_metrics' `nms` ("reference", the default, or "yolov5": the detections get_metrics scores come from yolov5's own NMS,
     yf_val_nms_v5); it needs val_metrics=True, anything else with it raises ValueError.  get_mAP is the reference's either way.
+    `autoanchor=True`, opt-in like these: yolov5's check_anchors (anchors.check_anchors, thr 4.0) runs on `train_dataset` before the
+    losses are built -- on every rank, which must therefore share numpy's and `random`'s seeds -- and the io_params it returns (the
+    configured anchors if their best possible recall is above 0.98, else anchors fitted on the device, if they recall more) are used for
+    the losses and for Validation; the caller's `params` is not modified.  Rank 0 writes them as `YOLO-Fastest_anchors.json`
+    ({"anchors": [[[w, h], ...] per head], "strides": [...]}) into save_path.  The checkpoint is a plain state-dict and carries NO
+    anchors: whoever decodes with it (detect.py's io_params, YOLO_post_process) must put the written anchors into io_params["anchors"],
+    or the boxes are decoded against the wrong shapes.  With False the `anchors` module is not imported.
     Returns the trained model."""
     import logging
     import os
@@ -975,6 +983,15 @@ def train(params, device, tbwriter=None, train_dataset=None, val_dataset=None, l
             raise ValueError("train_params['branch_weight'] has %d entries, io_params['strides'] %d" % (len(head_weights), len(io["strides"])))
     save_path = io["save_path"]
     os.makedirs(save_path, exist_ok=True)
+    if autoanchor:
+        import json
+        import torch.distributed as tdist
+        from . import anchors as autoanchors
+        io = autoanchors.check_anchors(train_dataset, io, thr=4.0, logger=logger, device=device)
+        params = dict(params, io_params=io)                   # Validation reads params["io_params"]; the caller's dict stays as it was
+        if not tdist.is_initialized() or tdist.get_rank() == 0:
+            with open(os.path.join(save_path, "YOLO-Fastest_anchors.json"), "w") as f:
+                json.dump({"anchors": io["anchors"], "strides": list(io["strides"])}, f)
     total_epochs, batch_size = tp["total_epochs"], tp["batch_size"]
     model = YoloFastest(io).to(device)
     model_loss = [validation.YOLOLossV3(anchors=io["anchors"][i], num_classes=io["num_cls"], input_shape=io["input_shape"], device=device,
