@@ -556,7 +556,8 @@ int yf_forward_bgr_u8(yf_handle h, const uint8_t *d_bgr, int N, int src_h, int s
  *     gain = min(H / h, W / w);  pad_w = (W - w * gain) / 2;  pad_h = (H - h * gain) / 2
  *     x' = round_half_even(clip((x - pad_w) / gain, 0, w));   y' = round_half_even(clip((y - pad_h) / gain, 0, h))
  * -- yolov5's FLOAT pad, not the integer left / top the pixels were placed with (they differ by less than one source pixel).
- * Not covered: auto=True (the minimal rectangle), scaleFill, scaleup=False.
+ * Not covered: auto=True (the minimal rectangle), scaleFill, scaleup=False.  Training and validation items on letterboxed frames:
+ * yf_augment_letterbox_u8 below.
  *
  * yf_letterbox_geometry: host only, never touches a GPU.  out = new_h, new_w, top, bottom, left, right.  YF_E_INVALID for a size <= 0.
  *
@@ -617,6 +618,44 @@ int yf_augment_u8(int device, const uint8_t *d_src, int src_h, int src_w, int sr
 int yf_augment_warp_u8(int device, const uint8_t *d_src, int src_h, int src_w, int src_c, const int *d_index, int n_src, int N, const void *d_xtab,
                        const void *d_ytab, int dst_h, int dst_w, int dst_c, int gray_bits, const int *d_params, const double *d_warp,
                        uint8_t *d_scratch, uint8_t *d_u8, float *d_x, void *stream);
+/* Training items on LETTERBOXED frames of mixed sizes (opt-in: DetectDataset(letterbox=True)): the ragged twin of yf_augment_warp_u8, the
+ * squashing resize replaced by the letterbox of the block above.  The rule, once.  The frame is uint8 [h, w, 3] BGR, the net input
+ * H x W x C with C 1 or 3:
+ *     x = flipud?(fliplr?(GaussianBlur_k(warp?(letterbox(cvtColor_BGR2GRAY?(frame))))))
+ *   letterbox exactly yf_cv_letterbox_u8's: the geometry in double with round-half-even, the 11-bit cv2.resize arithmetic, the copy /
+ *             2x2-mean / linear decision on (h, w) against (new_h, new_w), a border of 114
+ *   blur, flips, warp: those of yf_augment_u8 / yf_augment_warp_u8, on the WHOLE H x W letterboxed image, border included: the blur
+ *             mixes 114 into the image's edge rows and columns and reflects (101) at the H x W bounds, not at the image's; the warp
+ *             samples the border as image and fills with the same 114 outside
+ *   With every parameter 0 the u8 output is yf_cv_letterbox_u8's bytes: what the net trains on is what it detects on.
+ * Labels (host only, dataset.py `_labels`): yolov5's LoadImagesAndLabels.__getitem__, non-mosaic branch, in float64 --
+ *     rows  = xyxy2xywh(pixel boxes) / (w, h)                      the frame's OWN size
+ *     r = min(H / h, W / w);  new_w, new_h = int(round(w * r)), int(round(h * r));  dw, dh = (W - new_w) / 2, (H - new_h) / 2
+ *     xyxy  = xywhn2xyxy(rows, r * w, r * h, padw=dw, padh=dh)     x1 = (r * w) * (xc - bw / 2) + dw, ...
+ *     rows' = xyxy2xywhn(xyxy, w=W, h=H, clip=True, eps=1e-3)      corners clipped to [0, W - 1e-3] x [0, H - 1e-3]
+ * -- yolov5's FLOAT pad again, not the integer left / top of the pixels.
+ * Not covered: auto=True / rectangular batches, scaleFill, scaleup=False, the INTER_AREA choice of yolov5's load_image, HSV; mosaic tiles
+ * are letterboxed frames (yolov5's are unpadded), so a tile that is not of the net's aspect ratio brings its 114 bars into the canvas.
+ *
+ * yf_augment_letterbox_u8: d_frames / heights / widths, gray_bits, the table and its protocol: yf_cv_letterbox_u8's (HOST arrays of N
+ * device pointers of any alignment; the 40-byte entries filled into the caller's pinned copy and uploaded on `stream`).
+ *   d_params  int32 [N] on the device: yf_augment_warp_u8's bits (k, 8 fliplr, 9 flipud, 10 warp, 11 perspective)
+ *   geometric NOT in the argument list one would write first: d_params lives on the device and is not read back, so the caller, who drew
+ *             the parameters on the host, says whether any frame carries bit 9 or 10.  0: launch 2 is yf_augment_u8's kernel and bits
+ *             9 .. 11 are NOT read (a frame that carries them anyway comes out unflipped and unwarped); nonzero: launch 2 is
+ *             yf_augment_warp_u8's second kernel, which honours them.
+ *   d_scratch caller-owned u8 [N, dst_h, dst_w, C] (may not overlap an output): the letterboxed frames between the two launches
+ *   d_warp    float64 [N, 8]: read with `geometric` only, else may be NULL
+ *   outputs   d_u8 u8 [N, dst_h, dst_w, C] and / or d_x float32 [N, C, dst_h, dst_w] = (v - 128) / 255
+ * TWO launches on `stream`: yf_cv_letterbox_u8's kernel into d_scratch, then the blur / flip (/ warp) kernel over the scratch as N same-size
+ * sources -- the calls yf_cv_letterbox_u8 + yf_augment_u8 (or yf_augment_warp_u8) would make, behind one validation and one table upload.
+ * A fused single launch (letterbox staged straight into the blur's LDS tile) was built and measured: not faster, so it went.
+ * YF_E_INVALID before any launch, and before the pinned table is written, for everything yf_cv_letterbox_u8 refuses, and for: no output,
+ * d_params or d_scratch NULL, `geometric` while d_warp is NULL, rows too wide for the LDS tile.  No allocation or synchronisation;
+ * stream-ordered. */
+int yf_augment_letterbox_u8(int device, int N, const void *const *d_frames, const int *heights, const int *widths, int gray_bits, int dst_h,
+                            int dst_w, const int *d_params, int geometric, const double *d_warp, uint8_t *d_scratch, uint8_t *d_u8,
+                            float *d_x, void *d_table, size_t table_bytes, void *h_table_pinned, void *stream);
 /* yolov5's mixup over frames that are ALREADY resized (and gray): per output frame the first frame, warped or not, blended with a partner
  * frame under the partner's own warp, then yf_augment_warp_u8's blur and flips on the mixture:
  *     x = flipud?(fliplr?(GaussianBlur_k(mix(warp?(first), warp?(partner), r))))

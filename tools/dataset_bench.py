@@ -18,7 +18,14 @@
                                                       four frames under a perspective draw) beside the warp call and the plain launch at
                                                       batch 16 and 512, in interleaved rounds: median and spread of each
     python tools/dataset_bench.py --train --mosaic    train() at batch 16, cache="device", geometric keys active: DetectDataset(mosaic=True)
-                                                      with mosaic 1.0 and 0.0 beside the flag-unset data set and the no-data loop"""
+                                                      with mosaic 1.0 and 0.0 beside the flag-unset data set and the no-data loop
+    python tools/dataset_bench.py --letterbox         DetectDataset(letterbox=True)'s launch against its yardsticks: 256 BGR frames into the
+                                                      320 x 256 gray net, blur / flip drawn like the reference, HIP events around every
+                                                      repeat, 30 repeats, the candidates interleaved in one process, on a ragged batch
+                                                      (the 8 sizes of tools/cv_pre_bench.py --letterbox) and on a uniform 512 x 640 one:
+                                                      (a) yf_augment_letterbox_u8, one call   (b) yf_cv_letterbox_u8 into a scratch, then
+                                                      yf_augment_u8 on the same-size scratch, two launches   (c) the default squash path:
+                                                      one yf_augment_u8 launch per source size plus an index_copy_ per size group"""
 import argparse
 import csv
 import glob
@@ -44,6 +51,7 @@ ap.add_argument("--profile", action="store_true")
 ap.add_argument("--train", action="store_true")
 ap.add_argument("--mixup", action="store_true", help="the mixup variant of --kernel / --train")
 ap.add_argument("--mosaic", action="store_true", help="the mosaic variant of --kernel / --train")
+ap.add_argument("--letterbox", action="store_true", help="yf_augment_letterbox_u8 against its two-launch and squash yardsticks")
 ap.add_argument("--reps", type=int, default=50)
 ap.add_argument("--steps", type=int, default=30)
 ap.add_argument("--rounds", type=int, default=3)
@@ -256,6 +264,90 @@ def kernel_bench_mosaic():
     return res
 
 
+def letterbox_bench(repeats=30):
+    """(a), (b), (c) of the module docstring: median / min / max of `repeats` event-timed calls each, interleaved; (a) against (b) with
+    the min-max spread of the two as the margin."""
+    import ctypes
+    from yolo_fastest_amd.training import _PinnedTable
+    lib = _lib.lib()
+    H, W, N = 256, 320, 256
+    sizes = [(512, 640), (480, 640), (360, 640), (511, 640), (512, 1280), (640, 360), (101, 640), (253, 317)]
+    g = torch.Generator().manual_seed(0)
+    rng = random.Random(0)
+    prm = []
+    for _ in range(N):            # the reference's draws at its default probabilities (gussian_filter 0.3, fliplr 0.5)
+        k = (7 if rng.random() < 0.4 else 3) if rng.random() < 0.3 else 0
+        prm.append(k | (int(rng.random() < 0.5) << 8))
+    res = {}
+    for name, mix in (("ragged", sizes), ("uniform", [(512, 640)])):
+        per = N // len(mix)
+        stacks = [torch.randint(0, 256, (per,) + hw + (3,), dtype=torch.uint8, generator=g).to(dev) for hw in mix]
+        pos = [[j * len(mix) + i for j in range(per)] for i in range(len(mix))]           # member j of stack i sits at batch position pos[i][j]
+        ptrs, hs, ws = [0] * N, [0] * N, [0] * N
+        for i, st in enumerate(stacks):
+            for j, p in enumerate(pos[i]):
+                ptrs[p], hs[p], ws[p] = st.data_ptr() + j * st[0].numel(), st.shape[1], st.shape[2]
+        host = ((ctypes.c_void_p * N)(*ptrs), (ctypes.c_int * N)(*hs), (ctypes.c_int * N)(*ws))
+        d_prm = torch.tensor(prm, dtype=torch.int32, device=dev)
+        d_pos = [torch.tensor(p, device=dev) for p in pos]
+        d_prm_group = [torch.tensor([prm[p] for p in ps], dtype=torch.int32, device=dev) for ps in pos]
+        x = torch.empty((N, 1, H, W), dtype=torch.float32, device=dev)
+        scratch = torch.empty((N, H, W, 1), dtype=torch.uint8, device=dev)
+        table = _PinnedTable(_lib.YF_LB_TABLE_ENTRY_BYTES * N, dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        tabs = []
+        for st in stacks:
+            hw = tuple(st.shape[1:3])
+            if hw in ((H, W), (2 * H, 2 * W)):
+                tabs.append((None, None))
+                continue
+            t = torch.empty(((W + H) * 16,), dtype=torch.uint8, device=dev)
+            _lib.check(lib.yf_cv_resize_tables(dev.index, hw[0], hw[1], H, W, t.data_ptr(), t.data_ptr() + W * 16, stream))
+            tabs.append((t, t.data_ptr() + W * 16))
+
+        def fused():
+            _lib.check(lib.yf_augment_letterbox_u8(dev.index, N, *host, 15, H, W, d_prm.data_ptr(), 0, None, scratch.data_ptr(), None, x.data_ptr(), *table.args,
+                                                   ctypes.c_void_p(stream)))
+
+        def two_launches():
+            _lib.check(lib.yf_cv_letterbox_u8(dev.index, N, *host, 15, H, W, scratch.data_ptr(), *table.args, ctypes.c_void_p(stream)))
+            _lib.check(lib.yf_augment_u8(dev.index, scratch.data_ptr(), H, W, 1, None, N, N, None, None, H, W, 1, 0, d_prm.data_ptr(), None,
+                                         x.data_ptr(), stream))
+
+        def squash():
+            for st, (t, yt), ps, pg in zip(stacks, tabs, d_pos, d_prm_group):
+                whole = len(stacks) == 1
+                dst = x if whole else torch.empty((per, 1, H, W), dtype=torch.float32, device=dev)
+                _lib.check(lib.yf_augment_u8(dev.index, st.data_ptr(), st.shape[1], st.shape[2], 3, None, per, per, None if t is None else t.data_ptr(),
+                                             yt, H, W, 1, 15, pg.data_ptr(), None, dst.data_ptr(), stream))
+                if not whole:
+                    x.index_copy_(0, ps, dst)
+        cands = {"(a) yf_augment_letterbox_u8, 1 call": fused, "(b) yf_cv_letterbox_u8 + yf_augment_u8, 2 launches": two_launches,
+                 "(c) squash: %d launches + %d index_copy_" % (len(stacks), 0 if len(stacks) == 1 else len(stacks)): squash}
+        times = {k: [] for k in cands}
+        for r in range(repeats + 3):
+            for k, fn in cands.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize(); e0.record(); fn(); e1.record(); torch.cuda.synchronize()   # (the sync also lets the pinned table be refilled)
+                if r >= 3:
+                    times[k].append(e0.elapsed_time(e1) * 1e3)
+        res[name] = {}
+        for k, v in times.items():
+            v.sort()
+            res[name][k] = {"median_us": round(float(np.median(v)), 1), "min_us": round(v[0], 1), "max_us": round(v[-1], 1)}
+            print("%-8s %-58s median %8.1f us   min %8.1f   max %8.1f   (%d repeats)" % (name, k, float(np.median(v)), v[0], v[-1], len(v)))
+        ka, kb = list(cands)[:2]
+        ra, rb = res[name][ka], res[name][kb]
+        spread = max(ra["max_us"] - ra["min_us"], rb["max_us"] - rb["min_us"])
+        gain = rb["median_us"] - ra["median_us"]
+        print("%-8s (b) - (a) = %.1f us of medians; min-max spread of the two: %.1f us -> (a) %s" % (
+            name, gain, spread, "is faster by more than the spread" if gain > spread else "is NOT faster by more than the spread"))
+        res[name]["b_minus_a_us"], res[name]["spread_us"] = round(gain, 1), round(spread, 1)
+    print("(c) allocates its per-group outputs inside the timed region, as dataset.py's default path does: its figure includes the allocator")
+    print("source bytes per frame vary; torch %s, HIP %s, %s" % (torch.__version__, torch.version.hip, torch.cuda.get_device_name(0)))
+    return res
+
+
 def profile():
     out = a.out or tempfile.mkdtemp(prefix="dataset_bench_")
     os.makedirs(out, exist_ok=True)
@@ -359,7 +451,9 @@ def train_bench():
 
 
 out = {}
-if a.kernel and a.profile:
+if a.letterbox:
+    out["letterbox"] = letterbox_bench()
+elif a.kernel and a.profile:
     profile()
 elif a.kernel and a.mosaic:
     out["kernel_mosaic"] = kernel_bench_mosaic()

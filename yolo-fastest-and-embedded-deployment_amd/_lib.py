@@ -161,6 +161,9 @@ _SIGS = {
     "yf_augment_warp_u8": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p,
                                       _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
                                       _c.c_void_p]),
+    "yf_augment_letterbox_u8": (_c.c_int, [_c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p,
+                                           _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p,
+                                           _c.c_void_p]),   # device, N, frames / heights / widths (host), gray_bits, H, W, params, geometric, warp, scratch, u8, x, table ...
     "yf_augment_mix_u8": (_c.c_int, [_c.c_int, _c.c_void_p] + [_c.c_int] * 5 + [_c.c_void_p] * 8),
     "yf_augment_mosaic_u8": (_c.c_int, [_c.c_int, _c.c_void_p] + [_c.c_int] * 5 + [_c.c_void_p] * 7),
     "yf_cv_resize_tables": (_c.c_int, [_c.c_int] * 5 + [_c.c_void_p] * 3),

@@ -14,7 +14,9 @@
 //   flip: after the blur (the taps and reflect-101 are symmetric, so the two commute; tests/test_gpu_dataset.py shows it).
 // yf_augment_warp_u8 adds yolov5's geometric warp between the resize and the blur (warp_kernel, a second launch over the resized frames);
 // yf_augment_mix_u8 adds yolov5's mixup of two resized, warped frames before the blur (mix_kernel, one launch; see below);
-// yf_augment_mosaic_u8 yolov5's mosaic of four resized frames, warped and cropped back to the frame size (mosaic_kernel, one launch).
+// yf_augment_mosaic_u8 yolov5's mosaic of four resized frames, warped and cropped back to the frame size (mosaic_kernel, one launch);
+// yf_augment_letterbox_u8 is the ragged twin: frames of ANY sizes, letterboxed instead of squashed -- cv_letterbox_kernel (yf_cv_kernels.hip)
+// into a scratch, then aug_kernel or warp_kernel over it: a fused single launch was measured and was not faster.
 // One workgroup owns `tr` destination rows of one frame: it stages those rows plus a 3-row halo of the resized (gray) image in LDS (computed
 // straight from the source bytes, as cv_pre_kernel does), runs the row pass into a uint16 LDS buffer and the column pass out of it.  A frame
 // whose k is 0 stages no halo and skips both passes (k is uniform per workgroup).  Integer arithmetic only on the byte path.
@@ -779,6 +781,47 @@ int yf_augment_warp_u8(int device, const uint8_t* d_src, int src_h, int src_w, i
     const unsigned grid = (unsigned)((long)N * ((dst_h + a.tr - 1) / a.tr));
     if (dst_c == 1) hipLaunchKernelGGL((warp_kernel<1>), dim3(grid), dim3(256), lds, s, w);
     else hipLaunchKernelGGL((warp_kernel<3>), dim3(grid), dim3(256), lds, s, w);
+    HIP_OK(hipGetLastError());
+    return YF_OK;
+}
+
+int yf_augment_letterbox_u8(int device, int N, const void* const* d_frames, const int* heights, const int* widths, int gray_bits, int dst_h,
+                            int dst_w, const int* d_params, int geometric, const double* d_warp, uint8_t* d_scratch, uint8_t* d_u8, float* d_x,
+                            void* d_table, size_t table_bytes, void* h_table_pinned, void* stream)
+{
+    const char* who = "yf_augment_letterbox_u8";
+    if (!d_u8 && !d_x) return fail(YF_E_INVALID, "%s: no output", who);
+    if (!d_params || !d_scratch) return fail(YF_E_INVALID, "%s: null d_params or d_scratch", who);
+    if (geometric && !d_warp) return fail(YF_E_INVALID, "%s: a frame with bit 9 or 10 needs d_warp", who);
+    if (gray_bits != 0 && gray_bits != 14 && gray_bits != 15) return fail(YF_E_INVALID, "%s: gray_bits must be 0 (three channels), 14 or 15", who);
+    if (N <= 0 || dst_h <= 0 || dst_w <= 0 || dst_h > YF_LB_MAX_SIDE || dst_w > YF_LB_MAX_SIDE)
+        return fail(YF_E_INVALID, "%s: N %d, destination %dx%d", who, N, dst_h, dst_w);
+    const int C = gray_bits ? 1 : 3;
+    AugArgs a{};
+    size_t lds;
+    if (int rc = aug_tile(who, N, dst_h, dst_w, C, a.tr, a.pitch, lds)) return rc;
+    if ((long)N * ((dst_h + yf::LB_TR - 1) / yf::LB_TR) > 0x7fffffffL)         // launch 1's grid: refused here, before the table is written
+        return fail(YF_E_INVALID, "%s: %d frames of %d rows are more workgroups than one launch takes", who, N, dst_h);
+    const hipStream_t s = (hipStream_t)stream;
+    if (int rc = yf::lb_upload_table(who, device, N, d_frames, heights, widths, gray_bits, dst_h, dst_w, d_table, table_bytes, h_table_pinned, s))
+        return rc;
+    // launch 1: the letterboxed (gray) frames, into the scratch
+    if (yf::launch_cv_letterbox(static_cast<const yf::LbEntry*>(d_table), N, gray_bits, dst_h, dst_w, d_scratch, s))
+        return fail(YF_E_INVALID, "%s: %d frames of %d rows are more workgroups than one launch takes", who, N, dst_h);
+    HIP_OK(hipGetLastError());
+    // launch 2 over the scratch as N same-size sources: yf_augment_u8's kernel, or with a warped / flipud frame yf_augment_warp_u8's second
+    if (!geometric) {
+        a.src = d_scratch; a.index = nullptr; a.n_src = N; a.n = N; a.sh = dst_h; a.sw = dst_w; a.sc = C; a.dh = dst_h; a.dw = dst_w; a.dc = C;
+        a.mode = 0; a.gray = 0; a.params = d_params; a.u8 = d_u8; a.x = d_x;
+        launch_aug(a, lds, s);
+    } else {
+        WarpArgs w{};
+        w.img = d_scratch; w.index = nullptr; w.n_src = N; w.n = N; w.dh = dst_h; w.dw = dst_w; w.params = d_params; w.warp = d_warp;
+        w.u8 = d_u8; w.x = d_x; w.tr = a.tr; w.pitch = a.pitch;
+        const unsigned grid = (unsigned)((long)N * ((dst_h + a.tr - 1) / a.tr));
+        if (C == 1) hipLaunchKernelGGL((warp_kernel<1>), dim3(grid), dim3(256), lds, s, w);
+        else hipLaunchKernelGGL((warp_kernel<3>), dim3(grid), dim3(256), lds, s, w);
+    }
     HIP_OK(hipGetLastError());
     return YF_OK;
 }

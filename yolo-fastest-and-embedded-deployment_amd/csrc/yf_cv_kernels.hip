@@ -300,7 +300,7 @@ int launch_cv_pre(const CvArgs& a, hipStream_t s)
 // with the coefficients cv_tables_kernel would put into a table computed here, per thread (a batch may hold as many sizes as frames, so
 // there is nothing to cache).  The copy / 2x2-mean / linear decision is per frame, hence uniform in the workgroup.  Source bytes are
 // gathered one by one: frame pointers and row strides of arbitrary sizes have no alignment to rely on.
-constexpr int LB_TR = 4;          // destination rows per workgroup
+// (LB_TR, the destination rows per workgroup, is in yf_kernels.h: yf_augment_letterbox_u8 bounds this kernel's grid before it uploads)
 
 template <int GRAY>   // 0: the three channels kept; 14 / 15: BGR -> gray
 __global__ void __launch_bounds__(256) cv_letterbox_kernel(const LbEntry* __restrict__ tab, uint8_t* __restrict__ dst, int dh, int dw)

@@ -781,6 +781,53 @@ float logit_threshold(double thres)
 
 }  // namespace
 
+// yolov5's letterbox(auto=False, scaleFill=False, scaleup=True) geometry in double, Python's round = rint in the default rounding mode
+static void letterbox_geometry(int h, int w, int H, int W, int32_t out[6])
+{
+    const double r = fmin((double)H / (double)h, (double)W / (double)w);
+    const int new_w = (int)rint((double)w * r), new_h = (int)rint((double)h * r);
+    const double dw = (double)(W - new_w) / 2.0, dh = (double)(H - new_h) / 2.0;
+    out[0] = new_h; out[1] = new_w;
+    out[2] = (int)rint(dh - 0.1); out[3] = (int)rint(dh + 0.1);
+    out[4] = (int)rint(dw - 0.1); out[5] = (int)rint(dw + 0.1);
+}
+
+namespace yf {
+
+int lb_upload_table(const char* who, int device, int N, const void* const* d_frames, const int* heights, const int* widths, int gray_bits,
+                    int dst_h, int dst_w, void* d_table, size_t table_bytes, void* h_table_pinned, hipStream_t s)
+{
+    static_assert(sizeof(LbEntry) == YF_LB_TABLE_ENTRY_BYTES, "the kernel's table entry (yf_kernels.h)");
+    if (N <= 0 || !d_frames || !heights || !widths || !d_table || !h_table_pinned) return fail(YF_E_INVALID, "%s: bad argument", who);
+    if (gray_bits != 0 && gray_bits != 14 && gray_bits != 15) return fail(YF_E_INVALID, "%s: gray_bits must be 0 (three channels), 14 or 15", who);
+    if (dst_h <= 0 || dst_w <= 0 || dst_h > YF_LB_MAX_SIDE || dst_w > YF_LB_MAX_SIDE) return fail(YF_E_INVALID, "%s: destination %dx%d", who, dst_h, dst_w);
+    if (table_bytes < (size_t)N * YF_LB_TABLE_ENTRY_BYTES)
+        return fail(YF_E_INVALID, "%s: the table holds %zu bytes, %d frames need %zu", who, table_bytes, N, (size_t)N * YF_LB_TABLE_ENTRY_BYTES);
+    for (int i = 0; i < N; ++i) {
+        if (!d_frames[i]) return fail(YF_E_INVALID, "%s: frame %d: null pointer", who, i);
+        if (heights[i] <= 0 || widths[i] <= 0 || heights[i] > YF_LB_MAX_SIDE || widths[i] > YF_LB_MAX_SIDE)
+            return fail(YF_E_INVALID, "%s: frame %d: size %dx%d (1 .. %d)", who, i, heights[i], widths[i], YF_LB_MAX_SIDE);
+    }
+    // every refusal comes before the pinned copy is written: a refused call leaves the previous table as it was
+    int32_t g[6];
+    for (int i = 0; i < N; ++i) {
+        letterbox_geometry(heights[i], widths[i], dst_h, dst_w, g);
+        if (g[0] < 1 || g[1] < 1)
+            return fail(YF_E_INVALID, "%s: frame %d: %dx%d letterboxed into %dx%d is %dx%d (cv2.resize raises on an empty size)", who, i, heights[i],
+                        widths[i], dst_h, dst_w, g[0], g[1]);
+    }
+    LbEntry* const host = static_cast<LbEntry*>(h_table_pinned);
+    for (int i = 0; i < N; ++i) {
+        letterbox_geometry(heights[i], widths[i], dst_h, dst_w, g);
+        host[i] = LbEntry{static_cast<const uint8_t*>(d_frames[i]), heights[i], widths[i], g[0], g[1], g[2], g[3], g[4], g[5]};
+    }
+    HIP_OK(hipSetDevice(device));
+    HIP_OK(hipMemcpyAsync(d_table, host, (size_t)N * sizeof(LbEntry), hipMemcpyHostToDevice, s));
+    return YF_OK;
+}
+
+}  // namespace yf
+
 extern "C" {
 
 int yf_abi_version(void) { return YF_ABI_VERSION; }
@@ -1281,17 +1328,6 @@ int yf_forward_bgr_u8(yf_handle h, const uint8_t* d_bgr, int N, int src_h, int s
     return forward_via_cv(h, d_bgr, N, src_h, src_w, 3, gray_bits, d_hl, d_hs, ws, ws_bytes, stream);
 }
 
-// yolov5's letterbox(auto=False, scaleFill=False, scaleup=True) geometry in double, Python's round = rint in the default rounding mode
-static void letterbox_geometry(int h, int w, int H, int W, int32_t out[6])
-{
-    const double r = fmin((double)H / (double)h, (double)W / (double)w);
-    const int new_w = (int)rint((double)w * r), new_h = (int)rint((double)h * r);
-    const double dw = (double)(W - new_w) / 2.0, dh = (double)(H - new_h) / 2.0;
-    out[0] = new_h; out[1] = new_w;
-    out[2] = (int)rint(dh - 0.1); out[3] = (int)rint(dh + 0.1);
-    out[4] = (int)rint(dw - 0.1); out[5] = (int)rint(dw + 0.1);
-}
-
 int yf_letterbox_geometry(int src_h, int src_w, int dst_h, int dst_w, int32_t out[6])
 {
     if (!out || src_h <= 0 || src_w <= 0 || dst_h <= 0 || dst_w <= 0) return fail(YF_E_INVALID, "yf_letterbox_geometry: bad argument");
@@ -1302,33 +1338,11 @@ int yf_letterbox_geometry(int src_h, int src_w, int dst_h, int dst_w, int32_t ou
 int yf_cv_letterbox_u8(int device, int N, const void* const* d_frames, const int* heights, const int* widths, int gray_bits, int dst_h, int dst_w,
                        uint8_t* d_dst, void* d_table, size_t table_bytes, void* h_table_pinned, void* stream)
 {
-    static_assert(sizeof(yf::LbEntry) == YF_LB_TABLE_ENTRY_BYTES, "the kernel's table entry (yf_kernels.h)");
     const char* who = "yf_cv_letterbox_u8";
-    if (N <= 0 || !d_frames || !heights || !widths || !d_dst || !d_table || !h_table_pinned) return fail(YF_E_INVALID, "%s: bad argument", who);
-    if (gray_bits != 0 && gray_bits != 14 && gray_bits != 15) return fail(YF_E_INVALID, "%s: gray_bits must be 0 (three channels), 14 or 15", who);
-    if (dst_h <= 0 || dst_w <= 0 || dst_h > YF_LB_MAX_SIDE || dst_w > YF_LB_MAX_SIDE) return fail(YF_E_INVALID, "%s: destination %dx%d", who, dst_h, dst_w);
-    if (table_bytes < (size_t)N * YF_LB_TABLE_ENTRY_BYTES)
-        return fail(YF_E_INVALID, "%s: the table holds %zu bytes, %d frames need %zu", who, table_bytes, N, (size_t)N * YF_LB_TABLE_ENTRY_BYTES);
-    for (int i = 0; i < N; ++i) {
-        if (!d_frames[i]) return fail(YF_E_INVALID, "%s: frame %d: null pointer", who, i);
-        if (heights[i] <= 0 || widths[i] <= 0 || heights[i] > YF_LB_MAX_SIDE || widths[i] > YF_LB_MAX_SIDE)
-            return fail(YF_E_INVALID, "%s: frame %d: size %dx%d (1 .. %d)", who, i, heights[i], widths[i], YF_LB_MAX_SIDE);
-    }
-    // every refusal comes before the pinned copy is written: a refused call leaves the previous table as it was
-    int32_t g[6];
-    for (int i = 0; i < N; ++i) {
-        letterbox_geometry(heights[i], widths[i], dst_h, dst_w, g);
-        if (g[0] < 1 || g[1] < 1)
-            return fail(YF_E_INVALID, "%s: frame %d: %dx%d letterboxed into %dx%d is %dx%d (cv2.resize raises on an empty size)", who, i, heights[i],
-                        widths[i], dst_h, dst_w, g[0], g[1]);
-    }
-    yf::LbEntry* const host = static_cast<yf::LbEntry*>(h_table_pinned);
-    for (int i = 0; i < N; ++i) {
-        letterbox_geometry(heights[i], widths[i], dst_h, dst_w, g);
-        host[i] = yf::LbEntry{static_cast<const uint8_t*>(d_frames[i]), heights[i], widths[i], g[0], g[1], g[2], g[3], g[4], g[5]};
-    }
-    HIP_OK(hipSetDevice(device));
-    HIP_OK(hipMemcpyAsync(d_table, host, (size_t)N * sizeof(yf::LbEntry), hipMemcpyHostToDevice, (hipStream_t)stream));
+    if (!d_dst) return fail(YF_E_INVALID, "%s: bad argument", who);
+    if (int rc = yf::lb_upload_table(who, device, N, d_frames, heights, widths, gray_bits, dst_h, dst_w, d_table, table_bytes, h_table_pinned,
+                                     (hipStream_t)stream))
+        return rc;
     if (yf::launch_cv_letterbox(static_cast<const yf::LbEntry*>(d_table), N, gray_bits, dst_h, dst_w, d_dst, (hipStream_t)stream))
         return fail(YF_E_INVALID, "%s: %d frames of %d rows are more workgroups than one launch takes", who, N, dst_h);
     HIP_OK(hipGetLastError());

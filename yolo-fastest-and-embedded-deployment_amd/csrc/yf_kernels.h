@@ -212,7 +212,13 @@ struct LbEntry {
     int h, w;
     int new_h, new_w, top, bottom, left, right;  // yf_letterbox_geometry
 };
+constexpr int LB_TR = 4;                         // destination rows per workgroup of cv_letterbox_kernel
 int launch_cv_letterbox(const LbEntry* d_table, int n, int gray, int dh, int dw, uint8_t* dst, hipStream_t s);   // gray 0 (3 channels) | 14 | 15
+// The argument checks of yf_cv_letterbox_u8 (every refusal before the pinned copy is written), the table filled into the caller's pinned
+// copy and its upload on `s` (yf_engine.hip); yf_augment_letterbox_u8 shares it.  -> YF_OK or the error already set for `who`.
+int lb_upload_table(const char* who, int device, int N, const void* const* d_frames, const int* heights, const int* widths, int gray_bits,
+                    int dst_h, int dst_w, void* d_table, size_t table_bytes, void* h_table_pinned, hipStream_t s);
+
 // yolov5's scale_boxes + round, in place (yf_scale_boxes)
 void launch_scale_boxes(int32_t* boxes, long frame_stride, const int32_t* counts, long count_stride, int n, int kmax, int net_h, int net_w,
                         const int32_t* frame_hw, hipStream_t s);

@@ -41,6 +41,37 @@ one hit is one resize launch per source size into a u8 scratch and ONE `yf_augme
 building it: bit for bit Pillow's Image.transform of the materialised canvas.  A miss costs one draw and goes on as above.  Not built:
 mosaic together with mixup (both probabilities above 0: ValueError; yolov5 blends two mosaics there), mosaic9, segments, copy-paste.
 
+`letterbox` is OPT-IN as well: with `letterbox=True` the items are yolov5's letterboxed frames instead of the reference's squashed ones, so
+that a tree of MIXED frame sizes trains on what `Detect_YOLO(..., letterbox=True)` later feeds the net.  The rule stands in
+include/yolo_fastest_hip.h (yf_augment_letterbox_u8) and here.  The frame is uint8 [h, w, 3] BGR, the net input H x W x C:
+  Pixels.  x = flipud?(fliplr?(GaussianBlur_k(warp?(letterbox(BGR2GRAY?(frame)))))): `letterbox` exactly yf_cv_letterbox_u8's (geometry in
+    double with round-half-even, the 11-bit cv2.resize arithmetic, copy / 2x2 mean / linear decided on (h, w) against (new_h, new_w), a
+    border of 114); blur, flips and warp those of the squashed items, on the WHOLE H x W letterboxed image, border included -- the blur
+    mixes 114 into the image's edge rows and reflects (101) at the H x W bounds.  CPU statement:
+    aug_ref.gaussian_blur_u8(letterbox_ref.letterbox_u8(...)), then the flips (tests/).  With augment=False an item's bytes are
+    model.letterbox_u8's for that frame.
+  Labels.  yolov5's LoadImagesAndLabels.__getitem__, non-mosaic branch, in float64, in place of the division by origin_img_shape (_labels):
+        rows  = xyxy2xywh(xml pixel boxes) / (w, h)                  # the frame's OWN size: a yolov5 label-file row
+        r     = min(H / h, W / w)
+        new_w, new_h = int(round(w * r)), int(round(h * r))
+        dw, dh = (W - new_w) / 2, (H - new_h) / 2                    # yolov5's FLOAT pad, not the integer left / top of the pixels
+        xyxy  = xywhn2xyxy(rows, r * w, r * h, padw=dw, padh=dh)
+        rows' = xyxy2xywhn(xyxy, w=W, h=H, clip=True, eps=1e-3)
+    Everything behind _labels -- the warp, the mixup partner's rows, the mosaic tiles' rows, both flips, the max_boxes fill,
+    anchors.label_wh, check_anchors -- takes rows' unchanged, and the order and number of `random` draws do not change.
+    `origin_img_shape` is not read (as in Detect_YOLO), _check_size's rule does not apply.
+  Frame sizes.  Labels stay host-only, so the constructor records each frame's (h, w): the XML's <size> when both values are positive
+    integers, else the image header (PIL's Image.open(path).size, which decodes nothing).  A frame that decodes to another size, on the
+    host or on the device, raises ValueError naming the file.
+  Mosaic and mixup compose by the same substitution: tiles and partners are LETTERBOXED frames.  For mosaic this deviates from yolov5, whose
+    tiles are unpadded load_image frames: a tile that is not of the net's aspect ratio brings its 114 bars into the canvas.
+  Launches.  A batch, whatever its frame sizes and however many stacks they sit in, is ONE yf_augment_letterbox_u8 call (two launches:
+    the letterbox into a u8 scratch, then blur / flips / warp over it): no per-size loop, no resize-table pool, no index_copy_.  With mixup or mosaic hits the distinct frames
+    are letterboxed by ONE yf_cv_letterbox_u8 launch into the u8 scratch, then yf_augment_mix_u8 / yf_augment_mosaic_u8 run unchanged.
+  Validation needs no change: its targets are normalised in the net image, now the letterboxed one; get_mAP and get_metrics score in net
+    coordinates (scoring in each frame's native coordinates -- yolov5's val applies scale_boxes to predictions and labels -- is not built).
+  Not built: auto=True / rectangular batches, scaleFill, scaleup=False, the INTER_AREA choice of yolov5's load_image, HSV.
+
 Deviation: the reference cannot return an image without objects -- `np.array([])` is 1-D, so a flip raises IndexError (`labels[:, 1]`,
 :143) and otherwise the box copy raises ValueError (:159); here such an image is blurred / flipped as drawn and gets all-zero boxes (the
 draws stay in the reference's order, so the items after it are the reference's)."""
@@ -104,17 +135,18 @@ class DetectBatch:
 
 class DetectDataset(torch.utils.data.Dataset):
     def __init__(self, input_shape, origin_img_shape, logger, augment=True, aug_params=None, max_boxes=64, val=False, device=None,
-                 gray_bits=15, cache=None, class_names=None, decode="host", progressive=False, mixup=False, mosaic=False):
+                 gray_bits=15, cache=None, class_names=None, decode="host", progressive=False, mixup=False, mosaic=False, letterbox=False):
         if aug_params is None:
             aug_params = config_params["augment_params"]
         self.aug_params = aug_params
-        self.origin_img_shape = list(origin_img_shape)
+        self.letterbox = bool(letterbox)                    # yolov5's letterboxed items; `origin_img_shape` is not read in this mode
+        self.origin_img_shape = None if self.letterbox else list(origin_img_shape)
         self.input_shape = list(input_shape)
         if len(self.input_shape) != 3 or self.input_shape[2] not in (1, 3):
             raise ValueError("input_shape[2] must be 1 or 3: image files decode to 3 channels (cv2.imread) and a 1-channel net gets them as gray")
-        if self.input_shape[2] == 1 and self.origin_img_shape[2] == 1:
+        if not self.letterbox and self.input_shape[2] == 1 and self.origin_img_shape[2] == 1:
             raise ValueError("input_shape[2] == origin_img_shape[2] == 1: the reference skips BGR2GRAY then and yields [H, W, 3, 1] images")
-        if self.input_shape[0] <= 0 or self.input_shape[1] <= 0 or self.origin_img_shape[0] <= 0 or self.origin_img_shape[1] <= 0:
+        if self.input_shape[0] <= 0 or self.input_shape[1] <= 0 or (not self.letterbox and (self.origin_img_shape[0] <= 0 or self.origin_img_shape[1] <= 0)):
             raise ValueError("image shapes must be positive")
         if gray_bits not in (14, 15):
             raise ValueError("gray_bits must be 14 or 15")
@@ -173,6 +205,7 @@ class DetectDataset(torch.utils.data.Dataset):
         self.file_path_img = os.path.join(self.dataset_dir, "img")
         self.file_path_xml = os.path.join(self.dataset_dir, "xml")
         self.dataset_dict = {}
+        self._frame_hw = {}   # letterbox: image path -> the frame's (h, w), from the XML's <size> or the image header
         pathDir = os.listdir(self.file_path_xml)
         for idx in range(len(pathDir)):
             if idx % 1000 == 0:
@@ -189,11 +222,31 @@ class DetectDataset(torch.utils.data.Dataset):
                 _labels.append([self.classes.index(obj.find("name").text), x1, y1, x2, y2])
             _image_name = os.path.join(self.file_path_img, os.path.splitext(filename)[0] + ".jpg")
             self.dataset_dict.update({_image_name: _labels})
+            if self.letterbox:
+                self._frame_hw[_image_name] = self._xml_size(tree) or self._header_size(_image_name)
         self.img_list = list(self.dataset_dict.keys())
         logger.info("Loading finish！ dataset contain %d items" % (self.__len__()))
         self._stacks = {}     # cache="device": (h, w) -> [uint8 tensor [cap, h, w, 3], filled count]
         self._slot = {}       # cache="device": index -> ((h, w), slot in that stack)
         self._tables = {}     # (h, w) -> uint8 device tensor holding cv::resize's int4 tables [dw + dh]
+        self._lb_table = None # letterbox: training._PinnedTable of yf_cv_letterbox_u8 / yf_augment_letterbox_u8
+
+    @staticmethod
+    def _xml_size(tree):
+        """(h, w) of the XML's <size>, or None unless both values are positive integers."""
+        try:
+            h, w = int(tree.findtext("size/height").strip()), int(tree.findtext("size/width").strip())
+        except (AttributeError, ValueError):
+            return None
+        return (h, w) if h > 0 and w > 0 else None
+
+    @staticmethod
+    def _header_size(path):
+        """(h, w) from the image header: PIL reads it without decoding a pixel."""
+        from PIL import Image
+        with Image.open(path) as im:
+            w, h = im.size
+        return int(h), int(w)
 
     def __len__(self):
         return len(self.img_list)
@@ -303,9 +356,32 @@ class DetectDataset(torch.utils.data.Dataset):
         return self.draw_mix(index)[:5]
 
     def _labels(self, index):
-        """The reference's normalised (cls, xc, yc, w, h) rows of one item, by the configured origin_img_shape (:126-131)."""
+        """The reference's normalised (cls, xc, yc, w, h) rows of one item, by the configured origin_img_shape (:126-131); with
+        letterbox=True yolov5's rows in the letterboxed net image instead (the module docstring has the rule): the label-file row by the
+        frame's own size, xywhn2xyxy with letterbox's ratio and float pad, xyxy2xywhn(clip=True, eps=1e-3).  float64 throughout."""
         labels = np.array(self.dataset_dict[self.img_list[index]])
-        if len(labels):
+        if len(labels) and self.letterbox:
+            h, w = self._frame_hw[self.img_list[index]]
+            H, W = self.input_shape[0], self.input_shape[1]
+            labels[:, 1:5] = xyxy2xywh(labels[:, 1:5])
+            labels[:, [2, 4]] /= h
+            labels[:, [1, 3]] /= w
+            r = min(H / h, W / w)
+            new_w, new_h = int(round(w * r)), int(round(h * r))
+            dw, dh = (W - new_w) / 2, (H - new_h) / 2
+            x = labels[:, 1:5].copy()
+            box = np.zeros_like(x)                                                   # xywhn2xyxy(x, r * w, r * h, dw, dh)
+            box[:, 0] = (r * w) * (x[:, 0] - x[:, 2] / 2) + dw
+            box[:, 1] = (r * h) * (x[:, 1] - x[:, 3] / 2) + dh
+            box[:, 2] = (r * w) * (x[:, 0] + x[:, 2] / 2) + dw
+            box[:, 3] = (r * h) * (x[:, 1] + x[:, 3] / 2) + dh
+            box[:, [0, 2]] = box[:, [0, 2]].clip(0, W - 1e-3)                        # xyxy2xywhn(box, W, H, clip=True, eps=1e-3)
+            box[:, [1, 3]] = box[:, [1, 3]].clip(0, H - 1e-3)
+            labels[:, 1] = ((box[:, 0] + box[:, 2]) / 2) / W
+            labels[:, 2] = ((box[:, 1] + box[:, 3]) / 2) / H
+            labels[:, 3] = (box[:, 2] - box[:, 0]) / W
+            labels[:, 4] = (box[:, 3] - box[:, 1]) / H
+        elif len(labels):
             labels[:, 1:5] = xyxy2xywh(labels[:, 1:5])
             labels[:, [2, 4]] /= self.origin_img_shape[0]
             labels[:, [1, 3]] /= self.origin_img_shape[1]
@@ -406,6 +482,12 @@ class DetectDataset(torch.utils.data.Dataset):
         return bgr
 
     def _check_size(self, index, hw):
+        if self.letterbox:
+            want = self._frame_hw[self.img_list[index]]
+            if tuple(hw) != tuple(want):
+                raise ValueError("%s decodes to %dx%d, but %dx%d was recorded for it (the XML's <size>, else the image header): its "
+                                 "labels were letterboxed for that size" % (self.img_list[index], hw[0], hw[1], want[0], want[1]))
+            return
         if list(self.input_shape[0:2]) == list(self.origin_img_shape[0:2]) and list(hw) != list(self.input_shape[0:2]):
             raise ValueError("%s is %dx%d, but origin_img_shape[:2] == input_shape[:2] = %s: the reference does not resize then and "
                              "would yield a mis-shaped image" % (self.img_list[index], hw[0], hw[1], self.input_shape[0:2]))
@@ -501,6 +583,14 @@ class DetectDataset(torch.utils.data.Dataset):
         H, W, C = self.input_shape
         dev, lib = self.device, _lib.lib()
         scratch = torch.empty((len(distinct), H, W, C), dtype=torch.uint8, device=dev)
+        if self.letterbox:                                   # ONE yf_cv_letterbox_u8 launch over all of them, whatever their sizes
+            keep, ptrs, hs, ws = self._frame_pointers(distinct)
+            n, table = len(distinct), self._pinned_table(len(distinct))
+            _lib.check(lib.yf_cv_letterbox_u8(dev.index, n, (ctypes.c_void_p * n)(*ptrs), (ctypes.c_int * n)(*hs), (ctypes.c_int * n)(*ws),
+                                              0 if C == 3 else self.gray_bits, H, W, scratch.data_ptr(), *table.args, ctypes.c_void_p(stream)))
+            table.uploaded(n, torch.cuda.current_stream(dev))
+            del keep
+            return scratch, {i: j for j, i in enumerate(distinct)}
         where, base = {}, 0                                  # item -> its frame in the scratch
         for stack, slots, pos in self._groups(distinct):
             hw = tuple(stack.shape[1:3])
@@ -514,6 +604,52 @@ class DetectDataset(torch.utils.data.Dataset):
                 where[distinct[p]] = base + j
             base += len(pos)
         return scratch, where
+
+    def _frame_pointers(self, indices):
+        """letterbox: where each frame of `indices` starts, from however many stacks _groups returns: a member's pointer is its stack's
+        plus slot * h * w * 3.  -> (the stacks, to be kept until the launch is queued; pointers, heights, widths in batch order)."""
+        n = len(indices)
+        keep, ptrs, hs, ws = [], [0] * n, [0] * n, [0] * n
+        for stack, slots, pos in self._groups(indices):
+            stack = stack.contiguous()
+            h, w = int(stack.shape[1]), int(stack.shape[2])
+            keep.append(stack)
+            for j, p in enumerate(pos):
+                ptrs[p], hs[p], ws[p] = stack.data_ptr() + (j if slots is None else slots[j]) * h * w * 3, h, w
+        return keep, ptrs, hs, ws
+
+    def _pinned_table(self, n):
+        """letterbox: the per-frame table of the two letterbox entries, as model.letterbox_u8 keeps it: every call uploads, so the previous
+        upload must have left the pinned copy before the entry refills it."""
+        from .training import _PinnedTable
+        table = self._lb_table
+        if table is not None and table.event is not None:
+            table.event.synchronize()
+        if table is None or table.args[1] < _lib.YF_LB_TABLE_ENTRY_BYTES * n:
+            table = self._lb_table = _PinnedTable(_lib.YF_LB_TABLE_ENTRY_BYTES * max(n, 256), self.device)
+        return table
+
+    def _letterbox_images(self, indices, packed, warps, out, out_u8, stream):
+        """letterbox, a batch without mixup or mosaic hits: ONE yf_augment_letterbox_u8 call for all of it, mixed sizes or not."""
+        H, W, C = self.input_shape
+        dev, n = self.device, len(indices)
+        if not n:
+            return
+        keep, ptrs, hs, ws = self._frame_pointers(indices)
+        prm = torch.tensor(packed, dtype=torch.int32).to(dev)
+        geometric = any(p >> 9 for p in packed)
+        warp = None
+        scratch = torch.empty((n, H, W, C), dtype=torch.uint8, device=dev)
+        if geometric:
+            neutral = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0)
+            warp = torch.tensor([neutral if w is None else [float(v) for v in w] for w in warps], dtype=torch.float64).to(dev)
+        table = self._pinned_table(n)
+        _lib.check(_lib.lib().yf_augment_letterbox_u8(
+            dev.index, n, (ctypes.c_void_p * n)(*ptrs), (ctypes.c_int * n)(*hs), (ctypes.c_int * n)(*ws), 0 if C == 3 else self.gray_bits, H, W,
+            prm.data_ptr(), int(geometric), None if warp is None else warp.data_ptr(), scratch.data_ptr(),
+            out.data_ptr() if out_u8 else None, None if out_u8 else out.data_ptr(), *table.args, ctypes.c_void_p(stream)))
+        table.uploaded(n, torch.cuda.current_stream(dev))
+        del keep
 
     def _mix_images(self, indices, packed, warps, mixes, out, out_u8, stream):
         """A batch with at least one mixup hit: every distinct frame of items and partners resized once (_resize_distinct), then one
@@ -558,6 +694,8 @@ class DetectDataset(torch.utils.data.Dataset):
         by yf_augment_u8 (one launch per source size) into one u8 scratch, then ONE yf_augment_mix_u8 for the whole batch.
         Extended once more by draw_mosaic's ninth value (None, or (xc, yc, tiles, coeffs)): with at least one mosaic, the distinct
         frames of items and tiles resized the same way, then ONE yf_augment_mosaic_u8 for the whole batch.
+        With letterbox=True a batch without partners or mosaics is ONE yf_augment_letterbox_u8 call whatever its frame sizes; with them
+        the distinct frames are letterboxed by one yf_cv_letterbox_u8 launch in place of the per-size resizes.
         -> float32 device [N, C, H, W] ((v - 128) / 255), or uint8 device [N, H, W, C] with out_u8."""
         self._need_gpu()
         H, W, C = self.input_shape
@@ -586,6 +724,9 @@ class DetectDataset(torch.utils.data.Dataset):
             return out
         if any(m is not None for m in mixes):
             self._mix_images(indices, packed, warps, mixes, out, out_u8, stream)
+            return out
+        if self.letterbox:
+            self._letterbox_images(indices, packed, warps, out, out_u8, stream)
             return out
         groups = self._groups(indices)
         for stack, slots, pos in groups:
